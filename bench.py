@@ -14,6 +14,10 @@ Modes:
 
 Launch (driver): python -m torch.distributed.run --nnodes=1 --nproc-per-node N
   --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+  --dump-outputs DIR  also writes the last timed step's outputs as .npy
+  --full              adds the secondary measurements (none at present)
 """
 
 from __future__ import annotations
@@ -52,6 +56,16 @@ def parse_args():
     # random-init path the serving bench uses).
     p.add_argument("--cold-start", action="store_true")
     p.add_argument("--ckpt-dir", default="/tmp/arks_ckpt")
+    # After the timed steps, write what the last timed engine step returned
+    # (and the logits it sampled from) as DIR/<name>.npy, so two builds can
+    # be compared output for output. Inputs depend only on the arguments.
+    p.add_argument("--dump-outputs", metavar="DIR", default=None)
+    # A plain run does only what the headline figure needs. Secondary
+    # measurements that would take runs of their own belong behind --full;
+    # today there are none inside a plain run (cold start, fp8 and
+    # speculation are separate invocations selected by their own options),
+    # so --full currently adds nothing.
+    p.add_argument("--full", action="store_true")
     return p.parse_args()
 
 
@@ -71,13 +85,18 @@ def run_cold_start(args):
         save_random_checkpoint(mcfg, ckpt, seed=args.seed)
     nbytes = sum(os.path.getsize(f)
                  for f in glob.glob(os.path.join(ckpt, "*.safetensors")))
-    # drop the page cache so the read really comes from disk
+    # evict the checkpoint's pages from the page cache so the read really
+    # comes from disk (per file: needs no privilege, touches no host setting)
     try:
         subprocess.run(["sync"], check=False)
-        with open("/proc/sys/vm/drop_caches", "w") as f:
-            f.write("3\n")
+        for path in glob.glob(os.path.join(ckpt, "*.safetensors")):
+            fd = os.open(path, os.O_RDONLY)
+            try:
+                os.posix_fadvise(fd, 0, 0, os.POSIX_FADV_DONTNEED)
+            finally:
+                os.close(fd)
         cache_dropped = True
-    except OSError:
+    except (OSError, AttributeError):
         cache_dropped = False
     cfg = EngineConfig(
         model_path=ckpt,
@@ -112,6 +131,44 @@ def run_cold_start(args):
         },
     }
     print(json.dumps(result))
+
+
+# --dump-outputs stays well under 64 MB in all: logits above this many
+# float32 bytes are cut to a fixed, seeded sample of vocabulary columns.
+DUMP_LOGITS_MAX_BYTES = 48 * 1024 * 1024
+
+
+def dump_outputs(args, engine, out):
+    """Write the last timed step's results as DIR/<name>.npy (float64 ids,
+    float32 logits), rows ordered by request so runs compare row for row."""
+    import numpy as np
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    # request ids are "bench-<i>"; a step returns them in scheduling order
+    req = [int(o.request_id.rsplit("-", 1)[1]) for o in out]
+    order = sorted(range(len(out)), key=lambda j: req[j])  # stable
+    arrays = {
+        "request_index": np.array([req[j] for j in order], dtype=np.float64),
+        "new_token_ids": np.array(
+            [out[j].new_token_id for j in order], dtype=np.float64),
+    }
+    # The logits the step sampled those tokens from are still in the decode
+    # graph's output buffer (one row per sequence, in scheduling order).
+    graphs = getattr(engine.runner, "_graphs", None) or {}
+    sizes = [s for s in sorted(graphs) if s >= len(out)]
+    if sizes and not args.speculative and len(set(req)) == len(out):
+        logits = graphs[sizes[0]].logits[: len(out)].float().cpu()
+        logits = logits[torch.tensor(order)]
+        vocab = logits.shape[1]
+        keep = DUMP_LOGITS_MAX_BYTES // (4 * max(len(out), 1))
+        if keep < vocab:
+            g = torch.Generator().manual_seed(args.seed)
+            cols = torch.randperm(vocab, generator=g)[:keep].sort().values
+            logits = logits[:, cols]
+            arrays["logits_columns"] = cols.numpy().astype(np.float64)
+        arrays["logits"] = logits.numpy().astype(np.float32)
+    for name, arr in arrays.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
 
 def main():
@@ -195,6 +252,7 @@ def main():
         if s.first_token_time is not None
     )
     ttft_ms = ttfts[len(ttfts) // 2] if ttfts else None
+    out = []
     for _ in range(args.warmup):
         out = engine.step()
     barrier()
@@ -230,6 +288,9 @@ def main():
         assert tokens == expect, (
             "a sequence finished or was preempted inside the timed region"
         )
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args, engine, out)
 
     if rank == 0:
         n_gpus = world if use_gpu else args.gpus

@@ -14,6 +14,9 @@ import pytest
 def test_bench_dp2_gloo():
     env = dict(os.environ)
     env.setdefault("MASTER_ADDR", "127.0.0.1")
+    # gloo/CPU on every machine: the ranks see no GPU, so a host with fewer
+    # GPUs than ranks runs this exactly as a host with none
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     out = subprocess.run(
         [
             sys.executable, "-m", "torch.distributed.run",

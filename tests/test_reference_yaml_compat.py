@@ -1,17 +1,16 @@
-"""API compatibility: the REFERENCE's own sample YAMLs (read from
-/root/reference at test time — public untrusted content used only as parse
-fixtures) must load into our pydantic CRD types with their fields intact.
-Skipped where the reference checkout is absent."""
+"""API compatibility: the REFERENCE's own sample YAMLs (stored under
+tests/golden/reference_yaml — public untrusted content used only as parse
+fixtures) must load into our pydantic CRD types with their fields intact."""
 
 import glob
 import os
 
-import pytest
 import yaml
 
 from arks_amd.crd import types as T
 
-REF = "/root/reference"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                   "golden", "reference_yaml")
 
 KIND_MAP = {
     "ArksModel": T.ArksModel,
@@ -22,10 +21,6 @@ KIND_MAP = {
     "ArksQuota": T.ArksQuota,
 }
 
-pytestmark = pytest.mark.skipif(
-    not os.path.isdir(REF), reason="reference checkout not present"
-)
-
 
 def _load_docs(path):
     with open(path) as f:
@@ -34,7 +29,7 @@ def _load_docs(path):
 
 def test_reference_quickstart_parses():
     parsed = {}
-    for doc in _load_docs(os.path.join(REF, "examples/quickstart/quickstart.yaml")):
+    for doc in _load_docs(os.path.join(REF, "quickstart.yaml")):
         cls = KIND_MAP.get(doc.get("kind"))
         if cls is None:
             continue
@@ -56,7 +51,7 @@ def test_reference_quickstart_parses():
 
 def test_all_reference_samples_parse():
     n = 0
-    for path in glob.glob(os.path.join(REF, "config/samples/arks_v1_*.yaml")):
+    for path in glob.glob(os.path.join(REF, "samples/arks_v1_*.yaml")):
         for doc in _load_docs(path):
             cls = KIND_MAP.get(doc.get("kind"))
             if cls is None:
@@ -70,7 +65,7 @@ def test_all_reference_samples_parse():
 def test_reference_app_sample_drives_command_builder():
     """A reference vLLM sample must round-trip through our command builder
     with the documented flag contract."""
-    path = os.path.join(REF, "config/samples/arks_v1_arksapplication_vllm.yaml")
+    path = os.path.join(REF, "samples/arks_v1_arksapplication_vllm.yaml")
     doc = _load_docs(path)[0]
     app = T.ArksApplication.model_validate(doc)
     from arks_amd.controlplane import commands, manifests

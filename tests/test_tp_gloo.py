@@ -12,6 +12,15 @@ PROMPTS = [[1, 5, 9, 20, 31, 7], [3, 3, 7, 90]]
 MAX_TOKENS = 6
 
 
+@pytest.fixture(autouse=True)
+def _cpu_only_workers(monkeypatch):
+    """These are gloo/CPU tests on every machine: the spawned ranks inherit
+    an environment that hides any GPU, so a host with fewer GPUs than ranks
+    runs them exactly as a host with none."""
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "-1")
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
