@@ -466,6 +466,46 @@ class EngineConfig:
     device: str = "cuda"
     dtype: str = "bfloat16"
     seed: int = 0
+    # multi-LoRA serving (off by default): PEFT adapters of the base model
+    # loaded at start-up into max_loras fixed GPU slots, zero-padded to
+    # max_lora_rank (16, 32 or 64), selected per request by model name.
+    # lora_modules maps adapter name -> PEFT directory.
+    enable_lora: bool = False
+    max_loras: int = 4
+    max_lora_rank: int = 16
+    lora_modules: dict[str, str] | None = None
+
+    def __post_init__(self):
+        if not self.enable_lora:
+            if self.lora_modules:
+                raise ValueError("lora_modules given without enable_lora")
+            return
+        if self.quantization == "fp8":
+            raise ValueError(
+                "enable_lora with quantization='fp8' is not supported: the "
+                "fp8 layers receive pre-quantised activations"
+            )
+        if self.speculative == "draft":
+            raise ValueError(
+                "enable_lora with speculative='draft' is not supported "
+                "(n-gram speculation is)"
+            )
+        if self.max_lora_rank not in (16, 32, 64):
+            raise ValueError(
+                f"max_lora_rank must be 16, 32 or 64, got {self.max_lora_rank}"
+            )
+        if self.max_loras < 1:
+            raise ValueError(f"max_loras must be >= 1, got {self.max_loras}")
+        mods = self.lora_modules or {}
+        if self.served_model_name in mods:
+            raise ValueError(
+                f"LoRA adapter name {self.served_model_name!r} clashes with "
+                "served_model_name"
+            )
+        if len(mods) > self.max_loras:
+            raise ValueError(
+                f"{len(mods)} lora_modules exceed max_loras={self.max_loras}"
+            )
 
     def model_config(self) -> ModelConfig:
         if self.model_path:

@@ -31,6 +31,8 @@ class LLMEngine:
         self.runner = ModelRunner(cfg, self.model_cfg)
         t0 = time.time()
         self.runner.load_weights()
+        for name, path in (cfg.lora_modules or {}).items():
+            self.load_lora(name, path)
         self.load_seconds = time.time() - t0
         allocator = self.runner.init_kv_cache()
         self.scheduler = Scheduler(
@@ -68,12 +70,31 @@ class LLMEngine:
         request_id: str | None = None,
         arrival_time: float | None = None,
         hold_pages: bool = False,
+        lora: str | None = None,
     ) -> Sequence:
         seq = Sequence(prompt_token_ids, sampling, request_id, arrival_time)
         seq.hold_pages = hold_pages
+        if lora is not None:
+            if lora not in self.runner.lora_slots:
+                raise ValueError(f"unknown LoRA adapter {lora!r}")
+            seq.lora_name = lora
+            seq.lora_slot = self.runner.lora_slots[lora]
         self.scheduler.add(seq)
         self.total_prompt_tokens += seq.num_prompt_tokens
         return seq
+
+    def load_lora(self, name: str, path: str) -> None:
+        """Load a PEFT-format adapter into a free GPU slot under `name`
+        (used at start-up for each entry of lora_modules)."""
+        if name == self.cfg.served_model_name:
+            raise ValueError(
+                f"LoRA adapter name {name!r} clashes with served_model_name"
+            )
+        self.runner.load_lora(name, path)
+
+    @property
+    def lora_names(self) -> list[str]:
+        return list(self.runner.lora_slots)
 
     def abort_request(self, request_id: str) -> bool:
         return self.scheduler.abort(request_id)
@@ -295,9 +316,12 @@ class LLMEngine:
 
     # ---- convenience: run to completion (tests / offline use) ----
     def generate(
-        self, prompts: list[list[int]], sampling: SamplingParams | None = None
+        self, prompts: list[list[int]], sampling: SamplingParams | None = None,
+        lora: list[str | None] | None = None,
     ) -> list[list[int]]:
-        seqs = [self.add_request(p, sampling) for p in prompts]
+        loras = lora or [None] * len(prompts)
+        seqs = [self.add_request(p, sampling, lora=l)
+                for p, l in zip(prompts, loras)]
         while self.has_work():
             self.step()
         return [s.output_token_ids for s in seqs]

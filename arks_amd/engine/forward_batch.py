@@ -25,6 +25,10 @@ class ForwardBatch:
     # rows of the hidden states from which logits are needed (last token of
     # each sequence for prefill; everything for decode)
     logits_indices: torch.Tensor | None = None
+    # multi-LoRA: int32 [ntiles, 3] (row0, nrows, slot) work table shared by
+    # every adapted layer (ops.build_lora_tiles). None = no adapter rows in
+    # this batch, so no LoRA kernel is launched.
+    lora_tiles: torch.Tensor | None = None
 
     @property
     def num_tokens(self) -> int:

@@ -47,11 +47,13 @@ class BlockAllocator:
         self._free.extend(b for b in reversed(blocks) if b >= 0)
 
     # --- prefix-caching hooks (no-ops here) ---
-    def match_prefix(self, token_ids: list[int], max_tokens: int) -> tuple[list[int], int]:
+    def match_prefix(self, token_ids: list[int], max_tokens: int,
+                     salt: bytes = b"") -> tuple[list[int], int]:
         """Return (referenced cached blocks, number of cached tokens)."""
         return [], 0
 
-    def register_prefix(self, token_ids: list[int], blocks: list[int], start_block: int) -> None:
+    def register_prefix(self, token_ids: list[int], blocks: list[int],
+                        start_block: int, salt: bytes = b"") -> None:
         """Content-register full blocks of a just-allocated sequence."""
 
     @staticmethod
@@ -76,9 +78,14 @@ class PrefixCachingAllocator(BlockAllocator):
         self.hit_tokens = 0
 
     # --- digests ---
-    def _block_digests(self, token_ids: list[int], nblocks: int) -> list[bytes]:
+    def _block_digests(self, token_ids: list[int], nblocks: int,
+                       salt: bytes = b"") -> list[bytes]:
+        """Chained per-block digests. `salt` seeds the first block's digest
+        (and through the chain every later one): KV computed under a LoRA
+        adapter is keyed apart from the base model's and other adapters'.
+        The empty salt gives the unsalted digests."""
         out = []
-        h_parent = b""
+        h_parent = salt
         bs = self.block_size
         for i in range(nblocks):
             h = hashlib.blake2b(digest_size=16)
@@ -128,7 +135,8 @@ class PrefixCachingAllocator(BlockAllocator):
                     self._virgin.append(b)
 
     # --- prefix caching ---
-    def match_prefix(self, token_ids: list[int], max_tokens: int) -> tuple[list[int], int]:
+    def match_prefix(self, token_ids: list[int], max_tokens: int,
+                     salt: bytes = b"") -> tuple[list[int], int]:
         """Longest chain of cached full blocks covering <= max_tokens tokens.
         Matched blocks are ref'd (and pulled out of the LRU pool)."""
         bs = self.block_size
@@ -136,7 +144,7 @@ class PrefixCachingAllocator(BlockAllocator):
         self.query_tokens += len(token_ids)
         if limit == 0:
             return [], 0
-        digests = self._block_digests(token_ids, limit)
+        digests = self._block_digests(token_ids, limit, salt)
         blocks: list[int] = []
         for d in digests:
             b = self._cached.get(d)
@@ -150,7 +158,8 @@ class PrefixCachingAllocator(BlockAllocator):
         self.hit_tokens += len(blocks) * bs
         return blocks, len(blocks) * bs
 
-    def register_prefix(self, token_ids: list[int], blocks: list[int], start_block: int) -> None:
+    def register_prefix(self, token_ids: list[int], blocks: list[int],
+                        start_block: int, salt: bytes = b"") -> None:
         """Register the full blocks of `blocks[start_block:]` (newly
         allocated) under their content digests. Earlier digests for the same
         content keep priority (no override)."""
@@ -158,7 +167,7 @@ class PrefixCachingAllocator(BlockAllocator):
         nfull = len(token_ids) // bs
         if nfull <= start_block:
             return
-        digests = self._block_digests(token_ids, nfull)
+        digests = self._block_digests(token_ids, nfull, salt)
         for i in range(start_block, nfull):
             b = blocks[i]
             d = digests[i]

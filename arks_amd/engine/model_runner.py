@@ -50,6 +50,11 @@ class ModelRunner:
         self.kv_caches: list[tuple[torch.Tensor, torch.Tensor]] = []
         self.num_blocks = 0
         self._graphs: dict[int, "_DecodeGraph"] = {}
+        # decode graphs with the LoRA launches in them, captured lazily per
+        # padded batch size the first time a step has an adapter request
+        self._lora_graphs: dict[int, "_DecodeGraph"] = {}
+        self.lora_slots: dict[str, int] = {}  # adapter name -> GPU slot
+        self.lora_bytes = 0
         self._graph_pool = None
         self._graph_bufs: dict | None = None
         self.use_graphs = (
@@ -98,7 +103,48 @@ class ModelRunner:
         # every reachable position (OOB table reads fault on GPU)
         if hasattr(self.model, "extend_rope_table"):
             self.model.extend_rope_table(self.cfg.max_model_len)
+        if self.cfg.enable_lora:
+            # slot tensors come before the KV pool is sized, so
+            # profile_num_blocks accounts for them
+            from ..loader.lora_loader import allocate_lora_slots
+
+            rows = max(
+                self.cfg.max_num_batched_tokens,
+                self.cfg.max_num_seqs * (self.cfg.num_speculative_tokens + 1),
+                self.GRAPH_SIZES[-1],
+            )
+            self.lora_bytes = allocate_lora_slots(
+                self.model, self.cfg.max_loras, self.cfg.max_lora_rank,
+                self.device, rows,
+            )
         self._weights_loaded = True
+
+    def load_lora(self, name: str, path: str) -> int:
+        """Load a PEFT adapter into the next free slot (a known name reloads
+        its slot in place). Returns the slot."""
+        if not self.cfg.enable_lora:
+            raise ValueError("load_lora needs enable_lora=True")
+        from ..loader.lora_loader import load_adapter_into_slot
+
+        slot = self.lora_slots.get(name, len(self.lora_slots))
+        if slot >= self.cfg.max_loras:
+            raise ValueError(
+                f"no free LoRA slot for {name!r} (max_loras="
+                f"{self.cfg.max_loras})"
+            )
+        load_adapter_into_slot(self.model, self.model_cfg, path, slot,
+                               self.cfg.max_lora_rank)
+        self.lora_slots[name] = slot
+        return slot
+
+    def _lora_tiles(self, q_lens: list[int], seqs: list[Sequence]):
+        """Tile table of a packed batch, or None when no row has an adapter
+        (then no LoRA kernel is launched)."""
+        if not self.cfg.enable_lora or all(s.lora_slot < 0 for s in seqs):
+            return None
+        return ops.build_lora_tiles(
+            q_lens, [s.lora_slot for s in seqs], self.device
+        )
 
     def profile_num_blocks(self) -> int:
         """Size the KV pool from free HBM after weights (or the override)."""
@@ -277,6 +323,7 @@ class ModelRunner:
                 seq_lens=seq_lens,
                 ext_tiles=ext_tiles,
                 logits_indices=torch.tensor(logits_idx, dtype=torch.int64, device=dev),
+                lora_tiles=self._lora_tiles(q_lens, sb.seqs),
             )
         # decode
         input_ids = [s.last_token() for s in sb.seqs]
@@ -301,6 +348,7 @@ class ModelRunner:
             slot_mapping=torch.tensor(slot_mapping, dtype=torch.int64, device=dev),
             block_tables=bt.to(dev),
             seq_lens=torch.tensor(seq_lens, dtype=torch.int32, device=dev),
+            lora_tiles=self._lora_tiles([1] * len(sb.seqs), sb.seqs),
         )
 
     # ---------------- hipGraph decode ----------------
@@ -332,8 +380,19 @@ class ModelRunner:
         }
         for name in ("input_ids", "positions", "slot_mapping", "block_tables", "seq_lens"):
             self._graph_bufs["np_" + name] = self._graph_bufs["h_" + name].numpy()
+        if self.cfg.enable_lora:
+            # static LoRA tile table: row i is (i, 1, slot_i); padding rows
+            # and base requests carry slot -1 and are skipped by the kernels
+            tab = torch.zeros(self._bmax, 3, dtype=torch.int32)
+            tab[:, 0] = torch.arange(self._bmax, dtype=torch.int32)
+            tab[:, 1] = 1
+            tab[:, 2] = -1
+            self._graph_bufs["h_lora_tiles"] = tab.pin_memory()
+            self._graph_bufs["np_lora_tiles"] = (
+                self._graph_bufs["h_lora_tiles"].numpy())
+            self._graph_bufs["lora_tiles"] = tab.to(dev)
 
-    def _capture(self, bs: int) -> "_DecodeGraph":
+    def _capture(self, bs: int, lora: bool = False) -> "_DecodeGraph":
         b = self._graph_bufs
         fb = ForwardBatch(
             is_prefill=False,
@@ -342,6 +401,7 @@ class ModelRunner:
             slot_mapping=b["slot_mapping"][:bs],
             block_tables=b["block_tables"][:bs],
             seq_lens=b["seq_lens"][:bs],
+            lora_tiles=b["lora_tiles"][:bs] if lora else None,
         )
         # warmup (materializes workspaces outside the graph)
         self.model(fb, self.kv_caches)
@@ -361,8 +421,12 @@ class ModelRunner:
     def _graph_decode(self, sb: ScheduledBatch) -> torch.Tensor:
         B = len(sb.seqs)
         bs = next(s for s in self.GRAPH_SIZES if s >= B)
-        if bs not in self._graphs:
-            self._graphs[bs] = self._capture(bs)
+        # a step whose requests are all base requests replays the graph
+        # without LoRA launches — the only one a LoRA-less engine captures
+        lora = self.cfg.enable_lora and any(s.lora_slot >= 0 for s in sb.seqs)
+        graphs = self._lora_graphs if lora else self._graphs
+        if bs not in graphs:
+            graphs[bs] = self._capture(bs, lora)
         b = self._graph_bufs
         bsz = self.cfg.block_size
         # numpy views of the pinned staging buffers: scalar stores are ~50x
@@ -390,7 +454,13 @@ class ModelRunner:
         for name in ("input_ids", "positions", "slot_mapping", "seq_lens"):
             b[name][:bs].copy_(b["h_" + name][:bs], non_blocking=True)
         b["block_tables"][:bs].copy_(b["h_block_tables"][:bs], non_blocking=True)
-        gr = self._graphs[bs]
+        if lora:
+            np_tiles = b["np_lora_tiles"]
+            for i, seq in enumerate(sb.seqs):
+                np_tiles[i, 2] = seq.lora_slot
+            np_tiles[B:bs, 2] = -1
+            b["lora_tiles"][:bs].copy_(b["h_lora_tiles"][:bs], non_blocking=True)
+        gr = graphs[bs]
         gr.graph.replay()
         return gr.logits[:B]
 
@@ -484,6 +554,7 @@ class ModelRunner:
             seq_lens=torch.tensor(kv_lens, dtype=torch.int32, device=dev),
             # logits at EVERY row, not just the last per seq
             logits_indices=torch.arange(cu[-1], dtype=torch.int64, device=dev),
+            lora_tiles=self._lora_tiles(q_lens, sb.seqs),
         )
         logits = self.model(fb, self.kv_caches)  # [rows, vocab]
         greedy = ops.greedy_sample(logits.contiguous()).tolist()

@@ -146,7 +146,8 @@ class Scheduler:
                 if seq.sampling.prompt_logprobs:
                     reused, ncached = [], 0
                 else:
-                    reused, ncached = self.allocator.match_prefix(toks, n - 1)
+                    reused, ncached = self.allocator.match_prefix(
+                        toks, n - 1, **self._salt(seq))
                 seq.num_cached_tokens = ncached
             else:
                 # Continuation of a chunked prefill: pages for the covered
@@ -171,7 +172,8 @@ class Scheduler:
             if need > 0:
                 seq.block_table.extend(self.allocator.allocate(need))
             self.allocator.register_prefix(
-                toks[:covered], seq.block_table, len(reused)
+                toks[:covered], seq.block_table, len(reused),
+                **self._salt(seq)
             )
             if not partial:
                 self.waiting.popleft()
@@ -187,6 +189,15 @@ class Scheduler:
         # enter the decode set
         self.running.extend(s for s in seqs if s.status is SeqStatus.RUNNING)
         return ScheduledBatch(seqs=seqs, is_prefill=True, num_new_tokens=ntoks)
+
+    @staticmethod
+    def _salt(seq: Sequence) -> dict:
+        """Prefix-cache salt of a request: KV computed under a LoRA adapter
+        must never be matched by another adapter or by the base model. Base
+        requests pass nothing, so their digests are the unsalted ones."""
+        if seq.lora_name is None:
+            return {}
+        return {"salt": b"lora:" + seq.lora_name.encode()}
 
     def _schedule_decode(self) -> ScheduledBatch | None:
         if not self.running:

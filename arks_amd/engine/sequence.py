@@ -62,6 +62,10 @@ class Sequence:
         # Disaggregated prefill: keep KV pages allocated after finish so the
         # decode instance can pull them (scheduler.held).
         self.hold_pages = False
+        # multi-LoRA: the adapter this request runs under (None = base
+        # model) and its GPU slot (-1 = base)
+        self.lora_name: str | None = None
+        self.lora_slot = -1
         self.num_cached_tokens = 0  # tokens whose KV is already in cache
         # prompt-token logprobs (sampling.prompt_logprobs): value at index
         # q-1 scores prompt token q given tokens < q (first token unscored)

@@ -81,7 +81,7 @@ class Attention(nn.Module):
 
     def forward(self, x, batch: ForwardBatch, kv_cache) -> torch.Tensor:
         T = (x[0] if isinstance(x, tuple) else x).shape[0]
-        qkv = self.qkv_proj(x)
+        qkv = self.qkv_proj(x, batch.lora_tiles)
         # Strided views into the fused QKV buffer — RoPE/cache/attention
         # kernels take row strides, so no .contiguous() copies on the hot path.
         q, k, v = self.qkv_proj.split_qkv(qkv)
@@ -127,7 +127,7 @@ class Attention(nn.Module):
                 q, k_cache, v_cache, batch.block_tables, batch.seq_lens,
                 self.scale, window=self.window,
             )
-        return self.o_proj(out.view(T, -1))
+        return self.o_proj(out.view(T, -1), batch.lora_tiles)
 
 
 class MLP(nn.Module):
@@ -142,11 +142,12 @@ class MLP(nn.Module):
 
     fp8 = False
 
-    def forward(self, x):
-        gate_up = self.gate_up_proj(x)
+    def forward(self, x, batch: ForwardBatch | None = None):
+        tiles = batch.lora_tiles if batch is not None else None
+        gate_up = self.gate_up_proj(x, tiles)
         if self.fp8:
             return self.down_proj(ops.silu_mul_fp8(gate_up))
-        return self.down_proj(ops.silu_mul(gate_up))
+        return self.down_proj(ops.silu_mul(gate_up), tiles)
 
 
 _ARANGE_CACHE: dict[tuple[int, int, str], torch.Tensor] = {}
@@ -372,6 +373,8 @@ class DecoderLayer(nn.Module):
         self.mlp = (
             MoEMLP(cfg, dtype) if cfg.num_local_experts > 0 else MLP(cfg, dtype)
         )
+        # MoE blocks take no adapters (attention-projection LoRA only)
+        self._dense_mlp = isinstance(self.mlp, MLP)
 
     def forward(self, x, residual, batch: ForwardBatch, kv_cache):
         if residual is None:
@@ -381,7 +384,7 @@ class DecoderLayer(nn.Module):
             x, residual = self.input_layernorm(x, residual)
         x = self.self_attn(x, batch, kv_cache)
         x, residual = self.post_attention_layernorm(x, residual)
-        x = self.mlp(x)
+        x = self.mlp(x, batch) if self._dense_mlp else self.mlp(x)
         return x, residual
 
 

@@ -485,6 +485,57 @@ def quant_fp8_rows(x):
     return ref.quant_fp8_rows(x)
 
 
+LORA_TILE_ROWS = 16  # token rows per LoRA tile (one MFMA M tile)
+
+
+def build_lora_tiles(q_lens: list[int], slots: list[int],
+                     device=None) -> torch.Tensor:
+    """int32 [ntiles, 3] of (row0, nrows, slot) for the LoRA kernels: runs of
+    consecutive packed rows on one adapter slot, cut into tiles of at most 16
+    rows. Neighbouring sequences on the same slot share tiles; rows of
+    slot -1 (base-model requests) are covered by no tile. Build once per
+    batch and reuse across all layers."""
+    tiles: list[tuple[int, int, int]] = []
+    row = 0
+    run_start, run_slot = 0, -1
+    for n, slot in list(zip(q_lens, slots)) + [(0, -2)]:
+        if slot != run_slot:
+            if run_slot >= 0:
+                for r0 in range(run_start, row, LORA_TILE_ROWS):
+                    tiles.append((r0, min(LORA_TILE_ROWS, row - r0), run_slot))
+            run_start, run_slot = row, slot
+        row += n
+    return torch.tensor(tiles, dtype=torch.int32, device=device).reshape(-1, 3)
+
+
+def lora_shrink(h, x, A, tiles) -> None:
+    """h[row] = x[row] . A[slot]^T into the caller's f32 workspace."""
+    if x.is_cuda:
+        _native().lora_shrink(h, x, A, tiles)
+        return
+    ref.lora_shrink(h, x, A, tiles)
+
+
+def lora_expand(y, h, B, tiles, slice_offsets) -> None:
+    """y[row, n] += h[row, slice(n)] . B[slot][n] in place."""
+    if y.is_cuda:
+        _native().lora_expand(y, h, B, tiles, list(slice_offsets))
+        return
+    ref.lora_expand(y, h, B, tiles, slice_offsets)
+
+
+def lora_apply(y, x, A, B, tiles, slice_offsets, h_ws) -> None:
+    """y[t] += B[a(t)] . (A[a(t)] . x[t]) for the rows covered by `tiles`
+    (shrink into the f32 workspace h_ws [>=T, S*R], then expand into y in
+    place). Allocates and synchronises nothing: safe under graph capture."""
+    if h_ws.shape[0] < x.shape[0]:
+        raise ValueError(
+            f"LoRA workspace holds {h_ws.shape[0]} rows, batch has {x.shape[0]}"
+        )
+    lora_shrink(h_ws, x, A, tiles)
+    lora_expand(y, h_ws, B, tiles, slice_offsets)
+
+
 def moe_topk(router_logits, k: int, renorm: bool):
     """softmax + top-k + optional renorm in one kernel:
     (weights [T,k] f32, ids [T,k] i32). torch.topk tie-breaking (lower

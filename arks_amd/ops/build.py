@@ -31,6 +31,7 @@ SOURCES = [
     os.path.join(CSRC, "sampling.hip"),
     os.path.join(CSRC, "moe.hip"),
     os.path.join(CSRC, "allreduce.hip"),
+    os.path.join(CSRC, "lora.hip"),
 ]
 
 

@@ -104,6 +104,12 @@ void arks_moe_mix(void* out, const void* y, const void* weights,
 void arks_moe_mix_rows(void* out, const void* y, const void* weights,
                        const void* rows, int T, int H, int k,
                        hipStream_t stream);
+void arks_lora_shrink(void* h, const void* x, const void* a, const void* tiles,
+                      int ntiles, int T, int K, int SR, int max_loras,
+                      hipStream_t stream);
+void arks_lora_expand(void* y, const void* h, const void* b, const void* tiles,
+                      int ntiles, int T, int N, int R, int S, int off1,
+                      int off2, int max_loras, hipStream_t stream);
 void arks_mfma_probe(void* d, const void* a, const void* b, hipStream_t stream);
 void arks_mfma_probe32(void* d, const void* a, const void* b, hipStream_t stream);
 void arks_tr16_probe(void* out, int stride_bytes, hipStream_t stream);
@@ -641,6 +647,75 @@ void moe_mix_rows(torch::Tensor out, torch::Tensor y,
                     rows.data_ptr(), T, H, k, current_stream());
 }
 
+// --- multi-LoRA (lora.hip) ---
+void check_lora_tiles(const torch::Tensor& tiles) {
+  TORCH_CHECK(tiles.is_cuda() && tiles.scalar_type() == torch::kInt32 &&
+                  tiles.is_contiguous() && tiles.dim() == 2 &&
+                  tiles.size(1) == 3,
+              "tiles must be a contiguous int32 [ntiles, 3] GPU tensor");
+}
+
+void check_align16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+
+// h[row, :] = x[row, :] . A[slot]^T for the rows the tile table covers.
+void lora_shrink(torch::Tensor h, torch::Tensor x, torch::Tensor a,
+                 torch::Tensor tiles) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(a, "A");
+  check_lora_tiles(tiles);
+  TORCH_CHECK(x.dim() == 2 && a.dim() == 3, "x is [T, K], A is [L, S*R, K]");
+  const int64_t T = x.size(0), K = x.size(1), SR = a.size(1);
+  TORCH_CHECK(a.size(2) == K, "A depth ", a.size(2), " != x width ", K);
+  TORCH_CHECK(K % 32 == 0, "lora_shrink requires K % 32 == 0, got ", K);
+  TORCH_CHECK(SR % 16 == 0 && SR >= 16, "S*R must be a multiple of 16");
+  TORCH_CHECK(h.is_cuda() && h.scalar_type() == torch::kFloat32 &&
+                  h.is_contiguous() && h.dim() == 2 && h.size(1) == SR &&
+                  h.size(0) >= T,
+              "h must be a contiguous f32 [>=T, S*R] workspace");
+  check_align16(x, "x");
+  check_align16(a, "A");
+  arks_lora_shrink(h.data_ptr(), x.data_ptr(), a.data_ptr(), tiles.data_ptr(),
+                   (int)tiles.size(0), (int)T, (int)K, (int)SR,
+                   (int)a.size(0), current_stream());
+}
+
+// y[row, n] += sum_j h[row, s(n) R + j] B[slot][n, j], in place.
+void lora_expand(torch::Tensor y, torch::Tensor h, torch::Tensor b,
+                 torch::Tensor tiles, std::vector<int64_t> slice_offsets) {
+  check_bf16_contig(y, "y");
+  check_bf16_contig(b, "B");
+  check_lora_tiles(tiles);
+  TORCH_CHECK(y.dim() == 2 && b.dim() == 3, "y is [T, N], B is [L, N, R]");
+  const int64_t T = y.size(0), N = y.size(1), R = b.size(2);
+  TORCH_CHECK(b.size(1) == N, "B rows ", b.size(1), " != y width ", N);
+  TORCH_CHECK(N % 16 == 0, "lora_expand requires N % 16 == 0, got ", N);
+  TORCH_CHECK(R == 16 || R == 32 || R == 64, "rank must be 16, 32 or 64");
+  const int64_t S = (int64_t)slice_offsets.size() - 1;
+  TORCH_CHECK(S >= 1 && S <= 3, "1 to 3 slices");
+  TORCH_CHECK(slice_offsets[0] == 0 && slice_offsets[S] == N,
+              "slice_offsets must run from 0 to N");
+  for (int64_t s = 0; s < S; ++s) {
+    TORCH_CHECK(slice_offsets[s] < slice_offsets[s + 1] &&
+                    slice_offsets[s + 1] % 16 == 0,
+                "slice offsets must increase in multiples of 16");
+  }
+  TORCH_CHECK(h.is_cuda() && h.scalar_type() == torch::kFloat32 &&
+                  h.is_contiguous() && h.dim() == 2 && h.size(1) == S * R &&
+                  h.size(0) >= T,
+              "h must be a contiguous f32 [>=T, S*R] workspace");
+  check_align16(y, "y");
+  check_align16(h, "h");
+  check_align16(b, "B");
+  arks_lora_expand(y.data_ptr(), h.data_ptr(), b.data_ptr(), tiles.data_ptr(),
+                   (int)tiles.size(0), (int)T, (int)N, (int)R, (int)S,
+                   S > 1 ? (int)slice_offsets[1] : (int)N,
+                   S > 2 ? (int)slice_offsets[2] : (int)N, (int)b.size(0),
+                   current_stream());
+}
+
 void mfma_probe(torch::Tensor d, torch::Tensor a, torch::Tensor b) {
   check_bf16_contig(a, "a");
   check_bf16_contig(b, "b");
@@ -681,6 +756,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_topk", &moe_topk);
   m.def("moe_mix", &moe_mix);
   m.def("moe_mix_rows", &moe_mix_rows);
+  m.def("lora_shrink", &lora_shrink);
+  m.def("lora_expand", &lora_expand);
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma_probe32", &mfma_probe32);
   m.def("tr16_probe", &tr16_probe);

@@ -296,6 +296,32 @@ def moe_mix_rows(y: torch.Tensor, weights: torch.Tensor,
     return torch.einsum("tkh,tk->th", gathered, weights.float()).to(y.dtype)
 
 
+def lora_shrink(h: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+                tiles: torch.Tensor) -> None:
+    """h[row, :] = x[row, :] . A[slot]^T (fp32) for the rows covered by the
+    (row0, nrows, slot) tile table; slot < 0 tiles are skipped."""
+    for row0, nrows, slot in tiles.tolist():
+        if slot < 0:
+            continue
+        rows = slice(row0, row0 + nrows)
+        h[rows] = x[rows].float() @ A[slot].float().t()
+
+
+def lora_expand(y: torch.Tensor, h: torch.Tensor, B: torch.Tensor,
+                tiles: torch.Tensor, slice_offsets) -> None:
+    """y[row, n] += sum_j h[row, s(n) R + j] B[slot][n, j] in place (fp32
+    accumulate, one rounding to y's dtype); uncovered rows are untouched."""
+    R = B.shape[2]
+    for row0, nrows, slot in tiles.tolist():
+        if slot < 0:
+            continue
+        rows = slice(row0, row0 + nrows)
+        for s in range(len(slice_offsets) - 1):
+            cols = slice(slice_offsets[s], slice_offsets[s + 1])
+            delta = h[rows, s * R:(s + 1) * R].float() @ B[slot, cols].float().t()
+            y[rows, cols] = (y[rows, cols].float() + delta).to(y.dtype)
+
+
 def quant_fp8_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Per-row symmetric quantization to OCP e4m3 (range +-448)."""
     amax = x.float().abs().amax(dim=1).clamp(min=1e-6)

@@ -67,6 +67,31 @@ def _fp8_linear(mod: nn.Module, x: torch.Tensor) -> torch.Tensor:
     return F.linear(xd, mod.weight_qdq, mod.bias)
 
 
+class LoRAState:
+    """Per-layer multi-LoRA slot tensors (arks_amd/loader/lora_loader.py):
+    A [max_loras, S*R, K] and B [max_loras, N, R] bf16 over the layer's LOCAL
+    widths, the fused-slice column offsets, and the runner-wide f32 shrink
+    workspace. Allocated once; adapters are copied into their slot in place,
+    so the pointers captured into decode graphs never change."""
+
+    def __init__(self, A: torch.Tensor, B: torch.Tensor,
+                 slice_offsets: tuple[int, ...], h_ws: torch.Tensor):
+        self.A = A
+        self.B = B
+        self.slice_offsets = slice_offsets
+        # this layer's [rows, S*R] view of the shared flat workspace
+        sr = A.shape[1]
+        rows = h_ws.numel() // sr
+        self.h_ws = h_ws[: rows * sr].view(rows, sr)
+
+    def apply(self, y: torch.Tensor, x: torch.Tensor, tiles: torch.Tensor):
+        from .. import ops
+
+        ops.lora_apply(y, x, self.A, self.B, tiles, self.slice_offsets,
+                       self.h_ws)
+        return y
+
+
 class ColumnParallelLinear(nn.Module):
     """Y = X W^T with W row-sharded over TP ranks (output features split).
     Output stays sharded (gather_output=False semantics)."""
@@ -94,15 +119,19 @@ class ColumnParallelLinear(nn.Module):
         return full[r * self.out_per_rank : (r + 1) * self.out_per_rank]
 
     fp8 = False
+    lora: LoRAState | None = None  # set when the engine runs enable_lora
 
-    def forward(self, x) -> torch.Tensor:
+    def forward(self, x, lora_tiles=None) -> torch.Tensor:
         if isinstance(x, tuple):  # pre-quantized by the producing kernel
             return _fp8_linear_prequant(self, *x)
         if self.fp8:
             return _fp8_linear(self, x)
         from .. import ops
 
-        return ops.linear_bf16(x, self.weight, self.bias)
+        y = ops.linear_bf16(x, self.weight, self.bias)
+        if lora_tiles is not None and self.lora is not None:
+            self.lora.apply(y, x, lora_tiles)
+        return y
 
 
 class QKVParallelLinear(ColumnParallelLinear):
@@ -190,8 +219,9 @@ class RowParallelLinear(nn.Module):
         return full[:, r * self.in_per_rank : (r + 1) * self.in_per_rank]
 
     fp8 = False
+    lora: LoRAState | None = None  # set when the engine runs enable_lora
 
-    def forward(self, x) -> torch.Tensor:
+    def forward(self, x, lora_tiles=None) -> torch.Tensor:
         if isinstance(x, tuple) or self.fp8:
             bias = self.bias
             self.bias = None  # bias must be applied post-reduce, once
@@ -204,6 +234,10 @@ class RowParallelLinear(nn.Module):
             from .. import ops
 
             y = ops.linear_bf16(x, self.weight)
+            if lora_tiles is not None and self.lora is not None:
+                # the delta joins the local partial sum: linear, so the one
+                # all-reduce below covers it
+                self.lora.apply(y, x, lora_tiles)
         y = tp_all_reduce(y)
         if self.bias is not None:
             y = y + self.bias

@@ -45,6 +45,16 @@ def parse_args(argv=None):
     p.add_argument("--num-speculative-tokens", type=int, default=4)
     p.add_argument("--no-prefix-cache", action="store_true",
                    help="disable the content-addressed prefix/radix cache")
+    # multi-LoRA serving (vLLM spellings)
+    p.add_argument("--enable-lora", action="store_true",
+                   help="serve PEFT LoRA adapters of the base model; the "
+                        "request's model field picks the adapter")
+    p.add_argument("--lora-modules", nargs="+", default=None,
+                   metavar="NAME=PATH",
+                   help="adapters loaded at start-up: name=peft_dir ...")
+    p.add_argument("--max-loras", type=int, default=4)
+    p.add_argument("--max-lora-rank", type=int, default=16,
+                   choices=[16, 32, 64])
     # multi-node group flags (LWS leader/worker topology): workers join the
     # leader's torch.distributed rendezvous
     p.add_argument("--leader-address", default=None)
@@ -61,6 +71,18 @@ def build_engine_config(args):
         preset = args.model.split(":", 1)[1]
     else:
         model_path = args.model
+    lora_modules = None
+    if args.lora_modules:
+        lora_modules = {}
+        for item in args.lora_modules:
+            name, sep, path = item.partition("=")
+            if not sep or not name or not path:
+                raise SystemExit(
+                    f"--lora-modules wants name=path, got {item!r}")
+            lora_modules[name] = path
+    if args.enable_lora and args.disaggregation_mode:
+        raise SystemExit(
+            "--enable-lora with --disaggregation-mode is not supported")
     return EngineConfig(
         model_path=model_path,
         preset=preset,
@@ -77,6 +99,10 @@ def build_engine_config(args):
         draft_model=args.draft_model,
         num_speculative_tokens=args.num_speculative_tokens,
         enable_prefix_caching=not args.no_prefix_cache,
+        enable_lora=args.enable_lora,
+        max_loras=args.max_loras,
+        max_lora_rank=args.max_lora_rank,
+        lora_modules=lora_modules,
     )
 
 

@@ -126,9 +126,23 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
         # controller pulls this pod out of the HTTPRoute
         return Response(status_code=503 if engine.failed else 200)
 
+    def _adapters() -> list[str]:
+        """Names of the LoRA adapters loaded next to the base model."""
+        return list(getattr(getattr(engine, "engine", None), "lora_names", ()))
+
+    def _known_model(name: str) -> bool:
+        return name == served_model_name or name in _adapters()
+
+    def _lora_of(name: str) -> str | None:
+        """The request's `model` field picks the adapter (None = base)."""
+        return None if name == served_model_name else name
+
     @app.get("/v1/models")
     async def models():
-        return ModelList(data=[ModelCard(id=served_model_name)]).model_dump()
+        cards = [ModelCard(id=served_model_name)]
+        cards += [ModelCard(id=a, parent=served_model_name,
+                            root=served_model_name) for a in _adapters()]
+        return ModelList(data=cards).model_dump()
 
     @app.get("/metrics")
     async def metrics():
@@ -155,7 +169,8 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
         )
 
 
-    async def _collect_choice(rid, token_ids, sp, stops, prefill_addr):
+    async def _collect_choice(rid, token_ids, sp, stops, prefill_addr,
+                              lora=None):
         """One non-streamed choice: (token_ids, text, finish, n_generated)."""
         tracker = StopStringTracker(stops)
         # incremental detok even in the non-stream path: per-token decode
@@ -167,7 +182,8 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
         finish = None
         try:
             async for out in engine.generate_stream(rid, token_ids, sp,
-                                                    prefill_addr=prefill_addr):
+                                                    prefill_addr=prefill_addr,
+                                                    lora=lora):
                 out_ids.append(out.new_token_id)
                 if stops:
                     emit, stopped = tracker.feed(detok.feed(out.new_token_id))
@@ -189,7 +205,7 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
 
     @app.post("/v1/chat/completions")
     async def chat_completions(req: ChatCompletionRequest, raw: Request):
-        if req.model != served_model_name:
+        if not _known_model(req.model):
             return _error(404, f"model {req.model!r} not found")
         prompt = tokenizer.apply_chat_template([m.model_dump() for m in req.messages])
         token_ids = tokenizer.encode(prompt)
@@ -210,7 +226,7 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
             stops_n = _stop_list(req.stop)
             results = await asyncio.gather(*[
                 _collect_choice(f"{rid}-{i}", token_ids, _choice_sp(sp, i),
-                                stops_n, paddr)
+                                stops_n, paddr, _lora_of(req.model))
                 for i in range(req.n)
             ])
             total_out = sum(r[3] for r in results)
@@ -237,6 +253,7 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
             async for out in engine.generate_stream(
                 rid, token_ids, sp,
                 prefill_addr=raw.headers.get("x-arks-prefill-addr"),
+                lora=_lora_of(req.model),
             ):
                 text_ids.append(out.new_token_id)
                 if out.logprob is not None:
@@ -299,7 +316,8 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
         pending_lp: list[dict] = []  # per-token entries since the last emit
         try:
             async for out in engine.generate_stream(
-            rid, token_ids, sp, prefill_addr=raw.headers.get("x-arks-prefill-addr")
+            rid, token_ids, sp, prefill_addr=raw.headers.get("x-arks-prefill-addr"),
+            lora=_lora_of(req.model),
         ):
                 if await raw.is_disconnected():
                     engine.abort(rid)
@@ -358,7 +376,7 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
 
     @app.post("/v1/completions")
     async def completions(req: CompletionRequest, raw: Request):
-        if req.model != served_model_name:
+        if not _known_model(req.model):
             return _error(404, f"model {req.model!r} not found")
         # normalize prompt to a single token list (n=1, single prompt v0)
         p = req.prompt
@@ -394,7 +412,7 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
             stops_n = _stop_list(req.stop)
             results = await asyncio.gather(*[
                 _collect_choice(f"{rid}-{i}", token_ids, _choice_sp(sp, i),
-                                stops_n, paddr)
+                                stops_n, paddr, _lora_of(req.model))
                 for i in range(req.n)
             ])
             total_out = sum(r[3] for r in results)
@@ -421,6 +439,7 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
             async for out in engine.generate_stream(
                 rid, token_ids, sp,
                 prefill_addr=raw.headers.get("x-arks-prefill-addr"),
+                lora=_lora_of(req.model),
             ):
                 out_ids.append(out.new_token_id)
                 if out.prompt_logprobs is not None:
@@ -488,7 +507,8 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
         detok = IncrementalDetokenizer(tokenizer)
         try:
             async for out in engine.generate_stream(
-            rid, token_ids, sp, prefill_addr=raw.headers.get("x-arks-prefill-addr")
+            rid, token_ids, sp, prefill_addr=raw.headers.get("x-arks-prefill-addr"),
+            lora=_lora_of(req.model),
         ):
                 if await raw.is_disconnected():
                     engine.abort(rid)

@@ -31,6 +31,7 @@ class RequestAdd:
     token_ids: list[int]
     sampling: dict  # SamplingParams fields (picklable for broadcast)
     hold_pages: bool = False  # disaggregated prefill: keep pages for extract
+    lora: str | None = None  # adapter name (TP workers admit identically)
 
 
 def apply_msg(engine: LLMEngine, msg: dict) -> list[str]:
@@ -42,7 +43,7 @@ def apply_msg(engine: LLMEngine, msg: dict) -> list[str]:
         try:
             engine.add_request(
                 add.token_ids, SamplingParams(**add.sampling), add.request_id,
-                hold_pages=add.hold_pages,
+                hold_pages=add.hold_pages, lora=add.lora,
             )
         except ValueError:
             rejected.append(add.request_id)
@@ -124,14 +125,16 @@ class AsyncEngine:
 
     # ---- request API ----
     def submit(self, request_id: str, token_ids: list[int],
-               sampling: SamplingParams, hold_pages: bool = False) -> _Stream:
+               sampling: SamplingParams, hold_pages: bool = False,
+               lora: str | None = None) -> _Stream:
         st = _Stream()
         if self.failed is not None:  # engine loop is gone — end immediately
             st.queue.put_nowait(None)
             return st
         self.streams[request_id] = st
         self.pending_adds.append(
-            RequestAdd(request_id, token_ids, sampling.__dict__.copy(), hold_pages)
+            RequestAdd(request_id, token_ids, sampling.__dict__.copy(),
+                       hold_pages, lora)
         )
         self.metrics.prompt_tokens.inc(len(token_ids))
         if self._wakeup:
@@ -296,7 +299,8 @@ class AsyncEngine:
 
     async def generate_stream(self, request_id: str, token_ids: list[int],
                               sampling: SamplingParams,
-                              prefill_addr: str | None = None):
+                              prefill_addr: str | None = None,
+                              lora: str | None = None):
         """Async iterator of StepOutputs for one request. With a
         prefill_addr (disaggregated decode instance), the prompt is prefilled
         remotely and its KV pages pulled before decoding locally."""
@@ -311,7 +315,7 @@ class AsyncEngine:
                 request_id, token_ids, first, kv, sampling
             )
         else:
-            st = self.submit(request_id, token_ids, sampling)
+            st = self.submit(request_id, token_ids, sampling, lora=lora)
         while True:
             out = await st.queue.get()
             if out is None:

@@ -126,6 +126,9 @@ class ModelCard(BaseModel):
     object: Literal["model"] = "model"
     created: int = Field(default_factory=lambda: int(time.time()))
     owned_by: str = "arks_amd"
+    # LoRA adapters name the base model they were loaded onto
+    parent: str | None = None
+    root: str | None = None
 
 
 class ModelList(BaseModel):
