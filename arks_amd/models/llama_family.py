@@ -37,6 +37,9 @@ class RMSNorm(nn.Module):
         self.eps = eps
 
     def forward(self, x, residual=None):
+        if isinstance(x, ops.SplitKPending) and (self.fp8_out
+                                                 or residual is None):
+            x = x.materialize()  # no fused consumer for these forms
         if self.fp8_out:
             if residual is None:
                 return ops.rmsnorm_fp8(x, self.weight, self.eps)
@@ -79,9 +82,30 @@ class Attention(nn.Module):
             RMSNorm(cfg.head_dim, cfg.rms_norm_eps, dtype) if cfg.qk_norm else None
         )
 
-    def forward(self, x, batch: ForwardBatch, kv_cache) -> torch.Tensor:
+    def forward(self, x, batch: ForwardBatch, kv_cache, defer: bool = False):
+        """defer=True: the caller's next op is a fused add-RMSNorm that can
+        take o_proj's result as an ops.SplitKPending."""
         T = (x[0] if isinstance(x, tuple) else x).shape[0]
-        qkv = self.qkv_proj(x, batch.lora_tiles)
+        # Decode with plain RoPE: let the RoPE+cache kernel reduce the qkv
+        # split-K partials itself (decode attention reads k/v from the cache,
+        # so they are never materialised).
+        qkv = self.qkv_proj(
+            x, batch.lora_tiles,
+            defer=(not batch.is_prefill and self.use_rope
+                   and self.q_norm is None),
+        )
+        if isinstance(qkv, ops.SplitKPending):
+            k_cache, v_cache = kv_cache
+            q = ops.rope_and_cache_splitk(
+                batch.positions, qkv, k_cache, v_cache, batch.slot_mapping,
+                self._cos_sin, self.head_dim, self.nq_local,
+            )
+            out = ops.attention_decode_paged(
+                q.unflatten(-1, (self.nq_local, self.head_dim)), k_cache,
+                v_cache, batch.block_tables, batch.seq_lens, self.scale,
+                window=self.window,
+            )
+            return self.o_proj(out.view(T, -1), batch.lora_tiles, defer=defer)
         # Strided views into the fused QKV buffer — RoPE/cache/attention
         # kernels take row strides, so no .contiguous() copies on the hot path.
         q, k, v = self.qkv_proj.split_qkv(qkv)
@@ -127,7 +151,7 @@ class Attention(nn.Module):
                 q, k_cache, v_cache, batch.block_tables, batch.seq_lens,
                 self.scale, window=self.window,
             )
-        return self.o_proj(out.view(T, -1), batch.lora_tiles)
+        return self.o_proj(out.view(T, -1), batch.lora_tiles, defer=defer)
 
 
 class MLP(nn.Module):
@@ -142,12 +166,15 @@ class MLP(nn.Module):
 
     fp8 = False
 
-    def forward(self, x, batch: ForwardBatch | None = None):
+    def forward(self, x, batch: ForwardBatch | None = None,
+                defer: bool = False):
+        """defer=True: the caller's next op is a fused add-RMSNorm that can
+        take down_proj's result as an ops.SplitKPending."""
         tiles = batch.lora_tiles if batch is not None else None
         gate_up = self.gate_up_proj(x, tiles)
         if self.fp8:
             return self.down_proj(ops.silu_mul_fp8(gate_up))
-        return self.down_proj(ops.silu_mul(gate_up), tiles)
+        return self.down_proj(ops.silu_mul(gate_up), tiles, defer=defer)
 
 
 _ARANGE_CACHE: dict[tuple[int, int, str], torch.Tensor] = {}
@@ -382,9 +409,14 @@ class DecoderLayer(nn.Module):
             x = self.input_layernorm(x)
         else:
             x, residual = self.input_layernorm(x, residual)
-        x = self.self_attn(x, batch, kv_cache)
+        # o_proj and down_proj may come back as ops.SplitKPending: each is
+        # consumed by the very next fused add-RMSNorm (post_attention here;
+        # the next layer's input_layernorm or the model's final norm for
+        # down_proj) before another skinny GEMM reuses the workspace.
+        x = self.self_attn(x, batch, kv_cache, defer=True)
         x, residual = self.post_attention_layernorm(x, residual)
-        x = self.mlp(x, batch) if self._dense_mlp else self.mlp(x)
+        x = (self.mlp(x, batch, defer=True) if self._dense_mlp
+             else self.mlp(x))
         return x, residual
 
 

@@ -57,7 +57,17 @@ def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6) -> torch.T
 
 
 def fused_add_rmsnorm(x, residual, weight, eps: float = 1e-6):
-    """In-place on GPU: residual += x (written to residual), out = norm(residual)."""
+    """In-place on GPU: residual += x (written to residual), out = norm(residual).
+    x may be a SplitKPending handle: the kernel then reduces the producing
+    GEMM's split-K partials itself (bit-identical to materialising first)."""
+    if isinstance(x, SplitKPending):
+        x.check_live()
+        if tuple(residual.shape) != x.shape:
+            raise ValueError(f"residual {tuple(residual.shape)} vs {x.shape}")
+        out = torch.empty_like(residual)
+        _native().splitk_add_rmsnorm(out, x.ws, x.bias, residual, weight, eps,
+                                     x.nsplits, x.mrows)
+        return out, residual
     if x.is_cuda:
         out = torch.empty_like(x)
         _native().fused_add_rmsnorm(out, x, residual, weight, eps)
@@ -100,6 +110,23 @@ def rope_and_cache(positions, q, k, v, k_cache, v_cache, slot_mapping,
         k_cache, v_cache, slot_mapping,
     )
     return q2, k2
+
+
+def rope_and_cache_splitk(positions, qkv, k_cache, v_cache, slot_mapping,
+                          cos_sin, head_dim: int, num_q_heads: int):
+    """rope_and_cache for a qkv projection that is still a SplitKPending
+    handle: reduces the split-K partials, rotates, writes rotated k and v
+    into the paged cache and returns rotated q [T, Hq*D]. k and v are not
+    materialised (the decode attention kernel reads them from the cache)."""
+    qkv.check_live()
+    if qkv.shape[1] != (num_q_heads + 2 * k_cache.shape[1]) * head_dim:
+        raise ValueError(f"qkv width {qkv.shape[1]} does not match the heads")
+    q = torch.empty((qkv.shape[0], num_q_heads * head_dim),
+                    dtype=torch.bfloat16, device=qkv.ws.device)
+    _native().splitk_rope_and_cache(positions, qkv.ws, qkv.bias, q, k_cache,
+                                    v_cache, slot_mapping, cos_sin, head_dim,
+                                    qkv.nsplits, qkv.mrows)
+    return q
 
 
 def reshape_and_cache(k, v, k_cache, v_cache, slot_mapping):
@@ -345,18 +372,62 @@ def _extend_ws(need: int, device):
 
 
 _SKINNY_WS: dict = {}
+# Bumped every time a split-K GEMM overwrites the shared workspace of a
+# device; a SplitKPending remembers the value it was created under.
+_SKINNY_WS_GEN: dict = {}
 
 
-def skinny_gemm(x, weight, bias=None):
+class SplitKPending:
+    """Result of a split-K skinny GEMM that has not been reduced yet: the
+    f32 partials [nsplits, mrows, N] sit in the shared workspace and the
+    consumer kernel (fused_add_rmsnorm / rope_and_cache_splitk) sums them,
+    adds the bias and rounds to bf16 on the fly. materialize() runs the
+    combine kernel for anything that needs the plain [M, N] tensor.
+
+    The workspace is shared by every skinny GEMM of the device, so a handle
+    is only valid until the next one runs; consuming a stale handle raises
+    here, before any kernel is launched."""
+
+    __slots__ = ("ws", "nsplits", "mrows", "shape", "bias", "_key", "_gen")
+
+    def __init__(self, ws, nsplits, mrows, M, N, bias, key):
+        self.ws = ws
+        self.nsplits = nsplits
+        self.mrows = mrows
+        self.shape = (M, N)
+        self.bias = bias
+        self._key = key
+        self._gen = _SKINNY_WS_GEN[key]
+
+    def check_live(self) -> None:
+        if _SKINNY_WS_GEN.get(self._key) != self._gen:
+            raise RuntimeError(
+                "stale split-K handle: another skinny GEMM has overwritten "
+                "the shared workspace since this result was produced"
+            )
+
+    def materialize(self) -> torch.Tensor:
+        self.check_live()
+        out = torch.empty(self.shape, dtype=torch.bfloat16,
+                          device=self.ws.device)
+        _native().skinny_combine(out, self.ws, self.bias, self.nsplits,
+                                 self.mrows)
+        return out
+
+
+def skinny_gemm(x, weight, bias=None, defer: bool = False):
     """C = x @ weight^T for decode-sized M (<=64) via the split-K streaming
     MFMA kernel. Beats hipBLASLt's ~19 us latency floor on the small
     qkv/o_proj shapes and its ~46 us in-graph down-proj algo (bench_skinny /
     bench_down logs, r2); the dispatcher keeps the wide streaming shapes
     (gate_up, lm_head: N >> K) on the tuned library algos. Deterministic
-    split-K (fixed-order combine, no atomics)."""
+    split-K (fixed-order combine, no atomics).
+
+    defer=True returns a SplitKPending instead of the tensor whenever the
+    GEMM splits K (nsplits > 1): the caller hands it to a consumer that
+    reduces the partials itself, saving the combine launch."""
     M, K = x.shape
     N = weight.shape[0]
-    out = torch.empty((M, N), dtype=x.dtype, device=x.device)
     ntiles = N // 64
     if K > N and ntiles < 128 and M > 48:
         # tall-K (down-proj shape): few N tiles, parallelism comes from
@@ -368,6 +439,14 @@ def skinny_gemm(x, weight, bias=None):
         nsplits = min(-(-448 // ntiles), -(-K // 256))
         k_per_split = -(-(-(-K // nsplits)) // 32) * 32
         nsplits = -(-K // k_per_split)
+        if defer and nsplits > 1:
+            part = _skinny_ws(nsplits, N, 64, x.device)
+            _native().skinny_gemm_v_partials(part, x, weight, k_per_split,
+                                             nsplits, _SKINNY_TALLK_VARIANT,
+                                             False)
+            return SplitKPending(part, nsplits, 64, M, N, bias,
+                                 (x.device.index,))
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
         part = (_skinny_ws(nsplits, N, 64, x.device) if nsplits > 1
                 else x.new_empty(0, dtype=torch.float32))
         _native().skinny_gemm_v(out, part, x, weight, bias, k_per_split,
@@ -380,6 +459,12 @@ def skinny_gemm(x, weight, bias=None):
     k_ceil = -(-K // nsplits)
     k_per_split = -(-k_ceil // 32) * 32
     nsplits = -(-K // k_per_split)
+    if defer and nsplits > 1:
+        part = _skinny_ws(nsplits, N, M, x.device)
+        _native().skinny_gemm_partials(part, x, weight, k_per_split, nsplits)
+        return SplitKPending(part, nsplits, ((M + 15) // 16) * 16, M, N, bias,
+                             (x.device.index,))
+    out = torch.empty((M, N), dtype=x.dtype, device=x.device)
     part = _skinny_ws(nsplits, N, M, x.device) if nsplits > 1 else x.new_empty(
         0, dtype=torch.float32
     )
@@ -388,6 +473,8 @@ def skinny_gemm(x, weight, bias=None):
 
 
 def _skinny_ws(nsplits: int, N: int, M: int, device):
+    """The device's shared split-K workspace, grown to fit. Every call is
+    about to overwrite it, so it also retires outstanding handles."""
     mrows = ((M + 15) // 16) * 16
     key = (device.index,)
     need = nsplits * N * mrows
@@ -395,10 +482,15 @@ def _skinny_ws(nsplits: int, N: int, M: int, device):
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, dtype=torch.float32, device=device)
         _SKINNY_WS[key] = ws
+    _SKINNY_WS_GEN[key] = _SKINNY_WS_GEN.get(key, 0) + 1
     return ws
 
 
 _USE_SKINNY = os.environ.get("ARKS_SKINNY_GEMM", "1") == "1"
+# Let the consumers of a split-K skinny GEMM (fused add-RMSNorm, RoPE+cache)
+# reduce its partials instead of launching the combine kernel. 0 = always
+# materialise (the unfused sequence; results are bit-identical either way).
+_SPLITK_FUSE = os.environ.get("ARKS_SPLITK_FUSE", "1") == "1"
 # Weight-elements threshold: the split-K streaming kernel beats hipBLASLt's
 # ~19 us latency floor on the small decode shapes (qkv/o: 1.0-1.6x,
 # bench_skinny v3); the big streaming shapes (gate_up/down/lm_head) stay on
@@ -412,9 +504,11 @@ _SKINNY_TALLK_MAX_ELEMS = 80_000_000
 _SKINNY_TALLK_VARIANT = int(os.environ.get("ARKS_SKINNY_TALLK_V", "7"))
 
 
-def linear_bf16(x, weight, bias=None):
+def linear_bf16(x, weight, bias=None, defer: bool = False):
     """Linear dispatch: the skinny split-K kernel for small decode-shaped
-    GEMMs on GPU, hipBLASLt (F.linear) otherwise."""
+    GEMMs on GPU, hipBLASLt (F.linear) otherwise. defer=True lets the skinny
+    path return a SplitKPending (see skinny_gemm); every other path returns
+    the tensor as usual, so callers must accept both."""
     if (
         _USE_SKINNY
         and x.is_cuda
@@ -430,7 +524,7 @@ def linear_bf16(x, weight, bias=None):
         and weight.is_contiguous()
         and native_available()
     ):
-        return skinny_gemm(x, weight, bias)
+        return skinny_gemm(x, weight, bias, defer=defer and _SPLITK_FUSE)
     import torch.nn.functional as F
 
     return F.linear(x, weight, bias)

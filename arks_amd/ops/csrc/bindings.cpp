@@ -82,11 +82,26 @@ void arks_silu_mul_fp8(void* out, void* inv_scale, const void* gate_up,
 void arks_skinny_gemm(void* part, void* out, const void* a, const void* w,
                       const void* bias, int m_rows, int n_total, int k_total,
                       int k_per_split, int nsplits, int64_t a_stride,
-                      hipStream_t stream);
+                      bool combine, hipStream_t stream);
 void arks_skinny_gemm_v(void* part, void* out, const void* a, const void* w,
                         const void* bias, int m_rows, int n_total, int k_total,
                         int k_per_split, int nsplits, int64_t a_stride,
-                        int variant, bool fuse_silu, hipStream_t stream);
+                        int variant, bool fuse_silu, bool combine,
+                        hipStream_t stream);
+void arks_skinny_combine(void* out, const void* part, const void* bias,
+                         int m_rows, int n_total, int nsplits, int mrows_pad,
+                         hipStream_t stream);
+void arks_splitk_add_rmsnorm(void* out, const void* part, const void* bias,
+                             void* residual, const void* weight, float eps,
+                             int rows, int hidden, int nsplits, int mrows_pad,
+                             hipStream_t stream);
+void arks_splitk_rope_and_cache(const void* positions, const void* part,
+                                const void* bias, void* q_out, void* k_cache,
+                                void* v_cache, const void* slot_mapping,
+                                const void* cos_sin, int num_tokens,
+                                int head_dim, int num_q_heads,
+                                int num_kv_heads, int block_size, int nsplits,
+                                int mrows_pad, int kv_fp8, hipStream_t stream);
 void arks_greedy_sample(void* out, const void* logits, int rows, int vocab,
                         hipStream_t stream);
 void arks_gumbel_sample(void* out, const void* logits, const void* temperatures,
@@ -388,64 +403,190 @@ void attention_extend2_combine(torch::Tensor out, torch::Tensor part_ws,
                             head_dim, current_stream());
 }
 
-void skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
-                 torch::Tensor w, c10::optional<torch::Tensor> bias,
-                 int64_t k_per_split, int64_t nsplits) {
-  check_bf16_contig(out, "out");
+// Shared argument checks of the skinny GEMM entries; returns the bias
+// pointer (or null). out is ignored for a partials-only launch.
+const void* check_skinny_args(const torch::Tensor& out,
+                              const torch::Tensor& part,
+                              const torch::Tensor& a, const torch::Tensor& w,
+                              const c10::optional<torch::Tensor>& bias,
+                              int64_t k, int64_t nsplits, int64_t mrows,
+                              bool partials_only, const char* what) {
   check_bf16_rowstrided(a, "a");
   check_bf16_contig(w, "w");
-  const int m = a.size(0), k = a.size(1), n = w.size(0);
-  TORCH_CHECK(m >= 1 && m <= 64, "skinny_gemm needs 1 <= M <= 64");
+  const int64_t m = a.size(0), n = w.size(0);
+  TORCH_CHECK(m >= 1 && m <= 64, what, " needs 1 <= M <= 64");
   TORCH_CHECK(n % 64 == 0 && k % 32 == 0, "N%64==0 and K%32==0 required");
-  TORCH_CHECK(w.size(1) == k && out.size(0) == m && out.size(1) == n);
+  if (partials_only) {
+    TORCH_CHECK(nsplits > 1, what, ": partials-only needs nsplits > 1");
+  } else {
+    check_bf16_contig(out, "out");
+    TORCH_CHECK(out.size(0) == m && out.size(1) == n);
+  }
   const void* bias_ptr = nullptr;
   if (bias.has_value()) {
     check_bf16_contig(*bias, "bias");
     TORCH_CHECK(bias->numel() == n);
     bias_ptr = bias->data_ptr();
   }
-  const int mrows = ((m + 15) / 16) * 16;
   if (nsplits > 1) {
-    TORCH_CHECK(part.scalar_type() == torch::kFloat32 &&
+    TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
+                part.is_contiguous() &&
                 part.numel() >= (int64_t)nsplits * n * mrows,
-                "skinny_gemm workspace too small");
+                what, " workspace too small");
   }
-  arks_skinny_gemm(nsplits > 1 ? part.data_ptr() : nullptr, out.data_ptr(),
-                   a.data_ptr(), w.data_ptr(), bias_ptr, m, n, k,
-                   (int)k_per_split, (int)nsplits, a.stride(0),
-                   current_stream());
+  return bias_ptr;
+}
+
+void skinny_gemm_impl(torch::Tensor out, torch::Tensor part, torch::Tensor a,
+                      torch::Tensor w, c10::optional<torch::Tensor> bias,
+                      int64_t k_per_split, int64_t nsplits, bool combine) {
+  const int m = a.size(0), k = a.size(1), n = w.size(0);
+  TORCH_CHECK(w.size(1) == k);
+  TORCH_CHECK(k_per_split >= 32 && k_per_split % 32 == 0 &&
+              nsplits * k_per_split >= k, "splits must cover K");
+  const int mrows = ((m + 15) / 16) * 16;
+  const void* bias_ptr = check_skinny_args(out, part, a, w, bias, k, nsplits,
+                                           mrows, !combine, "skinny_gemm");
+  arks_skinny_gemm(nsplits > 1 ? part.data_ptr() : nullptr,
+                   combine ? out.data_ptr() : nullptr, a.data_ptr(),
+                   w.data_ptr(), bias_ptr, m, n, k, (int)k_per_split,
+                   (int)nsplits, a.stride(0), combine, current_stream());
+}
+
+void skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
+                 torch::Tensor w, c10::optional<torch::Tensor> bias,
+                 int64_t k_per_split, int64_t nsplits) {
+  skinny_gemm_impl(out, part, a, w, bias, k_per_split, nsplits, true);
+}
+
+// Partials-only launch (nsplits > 1): leaves the f32 split-K partials
+// [nsplits, ceil16(M), N] in `part` for a consumer that reduces them
+// (splitk_add_rmsnorm / splitk_rope_and_cache / skinny_combine). The bias is
+// applied by that consumer, not here.
+void skinny_gemm_partials(torch::Tensor part, torch::Tensor a, torch::Tensor w,
+                          int64_t k_per_split, int64_t nsplits) {
+  skinny_gemm_impl(torch::Tensor(), part, a, w, c10::nullopt, k_per_split,
+                   nsplits, false);
 }
 
 // Variant/fused entry (MT fixed at 4, i.e. M <= 64). fuse_silu: `a` is the
 // gate_up output [M, >=2K] (gate cols [0,K), up cols [K,2K)).
+void skinny_gemm_v_impl(torch::Tensor out, torch::Tensor part, torch::Tensor a,
+                        torch::Tensor w, c10::optional<torch::Tensor> bias,
+                        int64_t k_per_split, int64_t nsplits, int64_t variant,
+                        bool fuse_silu, bool combine) {
+  const int m = a.size(0), k = w.size(1), n = w.size(0);
+  TORCH_CHECK(a.size(1) >= (fuse_silu ? 2 * k : k), "A too narrow");
+  TORCH_CHECK(0 <= variant && variant <= 8, "variant in 0..8");
+  TORCH_CHECK(k_per_split >= 32 && k_per_split % 32 == 0 &&
+              nsplits * k_per_split >= k, "splits must cover K");
+  const void* bias_ptr = check_skinny_args(out, part, a, w, bias, k, nsplits,
+                                           64, !combine, "skinny_gemm_v");
+  arks_skinny_gemm_v(nsplits > 1 ? part.data_ptr() : nullptr,
+                     combine ? out.data_ptr() : nullptr, a.data_ptr(),
+                     w.data_ptr(), bias_ptr, m, n, k, (int)k_per_split,
+                     (int)nsplits, a.stride(0), (int)variant, fuse_silu,
+                     combine, current_stream());
+}
+
 void skinny_gemm_v(torch::Tensor out, torch::Tensor part, torch::Tensor a,
                    torch::Tensor w, c10::optional<torch::Tensor> bias,
                    int64_t k_per_split, int64_t nsplits, int64_t variant,
                    bool fuse_silu) {
+  skinny_gemm_v_impl(out, part, a, w, bias, k_per_split, nsplits, variant,
+                     fuse_silu, true);
+}
+
+// Partials-only variant launch: partials are [nsplits, 64, N].
+void skinny_gemm_v_partials(torch::Tensor part, torch::Tensor a,
+                            torch::Tensor w, int64_t k_per_split,
+                            int64_t nsplits, int64_t variant, bool fuse_silu) {
+  skinny_gemm_v_impl(torch::Tensor(), part, a, w, c10::nullopt, k_per_split,
+                     nsplits, variant, fuse_silu, false);
+}
+
+// Checks shared by the consumers of split-K partials [nsplits, mrows, n].
+const void* check_partials(const torch::Tensor& part,
+                           const c10::optional<torch::Tensor>& bias,
+                           int64_t nsplits, int64_t mrows, int64_t rows,
+                           int64_t n) {
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
+              part.is_contiguous(), "part must be contiguous f32 on GPU");
+  TORCH_CHECK(nsplits >= 1 && mrows >= rows && rows >= 0 && n % 8 == 0);
+  TORCH_CHECK(part.numel() >= nsplits * mrows * n, "partials too small");
+  if (!bias.has_value()) return nullptr;
+  check_bf16_contig(*bias, "bias");
+  TORCH_CHECK(bias->numel() == n);
+  return bias->data_ptr();
+}
+
+void skinny_combine(torch::Tensor out, torch::Tensor part,
+                    c10::optional<torch::Tensor> bias, int64_t nsplits,
+                    int64_t mrows) {
   check_bf16_contig(out, "out");
-  check_bf16_rowstrided(a, "a");
-  check_bf16_contig(w, "w");
-  const int m = a.size(0), k = w.size(1), n = w.size(0);
-  TORCH_CHECK(m >= 1 && m <= 64, "skinny_gemm_v needs 1 <= M <= 64");
-  TORCH_CHECK(n % 64 == 0 && k % 32 == 0, "N%64==0 and K%32==0 required");
-  TORCH_CHECK(a.size(1) >= (fuse_silu ? 2 * k : k), "A too narrow");
-  TORCH_CHECK(out.size(0) == m && out.size(1) == n);
-  TORCH_CHECK(0 <= variant && variant <= 8, "variant in 0..8");
-  const void* bias_ptr = nullptr;
-  if (bias.has_value()) {
-    check_bf16_contig(*bias, "bias");
-    TORCH_CHECK(bias->numel() == n);
-    bias_ptr = bias->data_ptr();
-  }
-  if (nsplits > 1) {
-    TORCH_CHECK(part.scalar_type() == torch::kFloat32 &&
-                part.numel() >= (int64_t)nsplits * n * 64,
-                "skinny_gemm_v workspace too small");
-  }
-  arks_skinny_gemm_v(nsplits > 1 ? part.data_ptr() : nullptr, out.data_ptr(),
-                     a.data_ptr(), w.data_ptr(), bias_ptr, m, n, k,
-                     (int)k_per_split, (int)nsplits, a.stride(0),
-                     (int)variant, fuse_silu, current_stream());
+  TORCH_CHECK(out.dim() == 2);
+  const int m = out.size(0), n = out.size(1);
+  const void* bias_ptr = check_partials(part, bias, nsplits, mrows, m, n);
+  if (m == 0) return;
+  arks_skinny_combine(out.data_ptr(), part.data_ptr(), bias_ptr, m, n,
+                      (int)nsplits, (int)mrows, current_stream());
+}
+
+// fused_add_rmsnorm whose input is the split-K partials of the producing
+// skinny GEMM instead of its combined bf16 output.
+void splitk_add_rmsnorm(torch::Tensor out, torch::Tensor part,
+                        c10::optional<torch::Tensor> bias,
+                        torch::Tensor residual, torch::Tensor weight,
+                        double eps, int64_t nsplits, int64_t mrows) {
+  check_bf16_contig(out, "out");
+  check_bf16_contig(residual, "residual");
+  check_bf16_contig(weight, "weight");
+  TORCH_CHECK(out.dim() == 2 && residual.dim() == 2);
+  const int rows = out.size(0), hidden = out.size(1);
+  TORCH_CHECK(residual.size(0) == rows && residual.size(1) == hidden &&
+              weight.numel() == hidden);
+  const void* bias_ptr = check_partials(part, bias, nsplits, mrows, rows,
+                                        hidden);
+  if (rows == 0) return;
+  arks_splitk_add_rmsnorm(out.data_ptr(), part.data_ptr(), bias_ptr,
+                          residual.data_ptr(), weight.data_ptr(), (float)eps,
+                          rows, hidden, (int)nsplits, (int)mrows,
+                          current_stream());
+}
+
+// rope_and_cache whose q/k/v input is the split-K partials of the fused qkv
+// skinny GEMM. Writes rotated q to q_out [T, Hq*D]; k/v only to the cache.
+void splitk_rope_and_cache(torch::Tensor positions, torch::Tensor part,
+                           c10::optional<torch::Tensor> bias,
+                           torch::Tensor q_out, torch::Tensor k_cache,
+                           torch::Tensor v_cache, torch::Tensor slot_mapping,
+                           torch::Tensor cos_sin, int64_t head_dim,
+                           int64_t nsplits, int64_t mrows) {
+  TORCH_CHECK(positions.scalar_type() == torch::kInt64 &&
+              positions.is_contiguous());
+  TORCH_CHECK(slot_mapping.scalar_type() == torch::kInt64 &&
+              slot_mapping.is_contiguous());
+  TORCH_CHECK(cos_sin.scalar_type() == torch::kFloat32 &&
+              cos_sin.is_contiguous() && cos_sin.size(-1) == head_dim);
+  check_bf16_contig(q_out, "q_out");
+  const bool kv_fp8 = check_kv_cache(k_cache, "k_cache");
+  TORCH_CHECK(check_kv_cache(v_cache, "v_cache") == kv_fp8);
+  TORCH_CHECK(q_out.dim() == 2 && head_dim % 8 == 0);
+  const int T = q_out.size(0);
+  const int nq = (int)(q_out.size(1) / head_dim);
+  const int nkv = k_cache.size(1);
+  const int block_size = k_cache.size(2);
+  TORCH_CHECK(nq * head_dim == q_out.size(1) && k_cache.size(3) == head_dim &&
+              v_cache.sizes() == k_cache.sizes());
+  TORCH_CHECK(positions.numel() == T && slot_mapping.numel() == T);
+  const void* bias_ptr = check_partials(part, bias, nsplits, mrows, T,
+                                        (int64_t)(nq + 2 * nkv) * head_dim);
+  arks_splitk_rope_and_cache(positions.data_ptr(), part.data_ptr(), bias_ptr,
+                             q_out.data_ptr(), k_cache.data_ptr(),
+                             v_cache.data_ptr(), slot_mapping.data_ptr(),
+                             cos_sin.data_ptr(), T, (int)head_dim, nq, nkv,
+                             block_size, (int)nsplits, (int)mrows,
+                             kv_fp8 ? 1 : 0, current_stream());
 }
 
 void rmsnorm_fp8(torch::Tensor out, torch::Tensor inv_scale,
@@ -744,6 +885,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul_fp8", &silu_mul_fp8);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("skinny_gemm_v", &skinny_gemm_v);
+  m.def("skinny_gemm_partials", &skinny_gemm_partials);
+  m.def("skinny_gemm_v_partials", &skinny_gemm_v_partials);
+  m.def("skinny_combine", &skinny_combine);
+  m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
+  m.def("splitk_rope_and_cache", &splitk_rope_and_cache);
   m.def("greedy_sample", &greedy_sample);
   m.def("gumbel_sample", &gumbel_sample);
   m.def("ipc_alloc", &ipc_alloc);

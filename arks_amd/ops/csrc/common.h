@@ -84,6 +84,50 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* scratch) {
   return total;
 }
 
+// Ordered reduction of split-K partials (skinny_gemm.hip layout
+// [split][m][n], split stride `sstride` floats) for W float4 column groups
+// of one row: s[w] = ((0 + p[0]) + p[1]) + ... — the exact summation order of
+// skinny_combine_kernel, so every consumer rounds the same f32 value.
+// Loads are issued 8*B splits at a time before any add (independent 16 B
+// loads; B = 2 covers the decode shapes' 8-10 splits in one memory round
+// trip, B = 1 halves the registers where 8 is the common case). Slots past
+// the last split clamp their address to it and are not added.
+template <int W, int B>
+__device__ __forceinline__ void splitk_reduce(const float* const (&p)[W],
+                                              const int64_t sstride,
+                                              const int nsplits,
+                                              float4v (&s)[W]) {
+  constexpr int U = 8;
+#pragma unroll
+  for (int w = 0; w < W; ++w) s[w] = float4v{0.f, 0.f, 0.f, 0.f};
+  for (int sp0 = 0; sp0 < nsplits; sp0 += B * U) {
+    float4v v[B][U][W];
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      const bool live = b == 0 || sp0 + b * U < nsplits;  // uniform
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t off =
+            (int64_t)min(sp0 + b * U + u, nsplits - 1) * sstride;
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+          v[b][u][w] = live ? *reinterpret_cast<const float4v*>(p[w] + off)
+                            : float4v{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (sp0 + b * U + u < nsplits) {
+#pragma unroll
+          for (int w = 0; w < W; ++w) s[w] += v[b][u][w];
+        }
+      }
+    }
+  }
+}
+
 __host__ __forceinline__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // OCP e4m3 <-> bf16 bit conversions for the fp8 KV cache (scale 1.0; the

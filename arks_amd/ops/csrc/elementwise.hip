@@ -6,6 +6,15 @@
 
 namespace arks {
 
+// ss + v*v as a rounded multiply followed by a rounded add, never an fma:
+// the form rmsnorm_kernel<true> compiles to. Written out so that the
+// partials-reading variant below accumulates the identical sum of squares
+// (left to the compiler it contracted to fma there and not here).
+__device__ __forceinline__ float add_square(const float ss, const float v) {
+#pragma clang fp contract(off)
+  return ss + v * v;
+}
+
 // ---------------------------------------------------------------------------
 // RMSNorm: one workgroup (256 threads = 4 waves) per row.
 // hidden must be a multiple of 8 (bf16x8 vector loads).
@@ -36,7 +45,7 @@ __global__ void rmsnorm_kernel(bf16* __restrict__ out,
         s[j] = float_to_bf16_bits(v);
         // Accumulate on the bf16-rounded value so pass 2's re-read matches.
         float vb = bf16_bits_to_float(s[j]);
-        ss += vb * vb;
+        ss = add_square(ss, vb);
       }
       *reinterpret_cast<ushort8*>(res_row + i * 8) = s;
     } else {
@@ -56,6 +65,67 @@ __global__ void rmsnorm_kernel(bf16* __restrict__ out,
   const bf16* src_row = FUSED_ADD ? res_row : in_row;
   for (int i = threadIdx.x; i < nvec; i += BLOCK) {
     ushort8 x = *reinterpret_cast<const ushort8*>(src_row + i * 8);
+    ushort8 w = *reinterpret_cast<const ushort8*>(weight + i * 8);
+    ushort8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float v = bf16_bits_to_float(x[j]) * rrms * bf16_bits_to_float(w[j]);
+      o[j] = float_to_bf16_bits(v);
+    }
+    *reinterpret_cast<ushort8*>(out_row + i * 8) = o;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Fused residual-add + RMSNorm whose input is still the split-K partials of
+// the producing skinny GEMM (skinny_gemm.hip, layout [split][m][n]): each
+// element is reduced in split order, biased and rounded to bf16 exactly as
+// skinny_combine_kernel would, then treated as rmsnorm_kernel<true> treats
+// its input. Same 256-thread / 8-columns-per-iteration map and block
+// reduce, so the sum of squares (and rrms) is bit-identical to the unfused
+// pair; what goes away is the combine launch and its bf16 round trip.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void splitk_add_rmsnorm_kernel(
+    bf16* __restrict__ out, const float* __restrict__ part,
+    const bf16* __restrict__ bias,  // [hidden] or null
+    bf16* __restrict__ residual, const bf16* __restrict__ weight,
+    const float eps, const int hidden, const int nsplits,
+    const int64_t split_stride) {
+  constexpr int BLOCK = 256;
+  const int row = blockIdx.x;
+  const float* part_row = part + (int64_t)row * hidden;
+  bf16* res_row = residual + (int64_t)row * hidden;
+  bf16* out_row = out + (int64_t)row * hidden;
+
+  const int nvec = hidden / 8;
+  float ss = 0.f;
+  for (int i = threadIdx.x; i < nvec; i += BLOCK) {
+    const float* const p[2] = {part_row + i * 8, part_row + i * 8 + 4};
+    float4v acc[2];
+    splitk_reduce<2, 2>(p, split_stride, nsplits, acc);
+    ushort8 r = *reinterpret_cast<const ushort8*>(res_row + i * 8);
+    ushort8 s;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float xf = acc[j / 4][j % 4];
+      if (bias != nullptr) xf += bf16_bits_to_float(bias[i * 8 + j]);
+      const uint16_t x = float_to_bf16_bits(xf);  // the combine's rounding
+      float v = bf16_bits_to_float(x) + bf16_bits_to_float(r[j]);
+      s[j] = float_to_bf16_bits(v);
+      float vb = bf16_bits_to_float(s[j]);
+      ss = add_square(ss, vb);
+    }
+    *reinterpret_cast<ushort8*>(res_row + i * 8) = s;
+  }
+
+  __shared__ float red[BLOCK / WAVE_SIZE];
+  float total = block_reduce_sum<BLOCK>(ss, red);
+  const float rrms = rsqrtf(total / (float)hidden + eps);
+
+  // Pass 2: re-read the residual this thread just wrote (L1/L2), as
+  // rmsnorm_kernel<true> does.
+  for (int i = threadIdx.x; i < nvec; i += BLOCK) {
+    ushort8 x = *reinterpret_cast<const ushort8*>(res_row + i * 8);
     ushort8 w = *reinterpret_cast<const ushort8*>(weight + i * 8);
     ushort8 o;
 #pragma unroll
@@ -158,6 +228,17 @@ void arks_fused_add_rmsnorm(void* out, const void* input, void* residual,
   hipLaunchKernelGGL((rmsnorm_kernel<true>), grid, block, 0, stream, (bf16*)out,
                      (const bf16*)input, (bf16*)residual, (const bf16*)weight,
                      eps, hidden);
+}
+
+void arks_splitk_add_rmsnorm(void* out, const void* part, const void* bias,
+                             void* residual, const void* weight, float eps,
+                             int rows, int hidden, int nsplits, int mrows_pad,
+                             hipStream_t stream) {
+  dim3 grid(rows), block(256);
+  hipLaunchKernelGGL(splitk_add_rmsnorm_kernel, grid, block, 0, stream,
+                     (bf16*)out, (const float*)part, (const bf16*)bias,
+                     (bf16*)residual, (const bf16*)weight, eps, hidden,
+                     nsplits, (int64_t)mrows_pad * hidden);
 }
 
 void arks_silu_mul(void* out, const void* gate_up, int64_t rows, int d,

@@ -19,8 +19,15 @@
 //   Swapped operands (A-frag = W rows, B-frag = activations) put the C
 //   fragment at [n, m], n = 4*la+r, col = lane%16 (same trick as the
 //   attention kernels, guide common-mistake #6).
-//   nsplits > 1 (small N) writes f32 partials [split, N, M]; a combine
-//   kernel reduces them in fixed order (deterministic, no atomics).
+//   nsplits > 1 (small N) writes f32 partials [split][m][n]: 16*MT rows
+//   per split, row stride N, one 16 B store per lane per M tile. That is
+//   the orientation of every reader, so the reduction (fixed split order
+//   from 0.f, then bias, then bf16 rounding; deterministic, no atomics)
+//   is a coalesced row read. On the decode path the consumer does it —
+//   splitk_add_rmsnorm_kernel (elementwise.hip) after o_proj/down_proj,
+//   splitk_rope_cache_kernel (kvcache.hip) after qkv — through
+//   splitk_reduce (common.h); skinny_combine_kernel is the fallback that
+//   materialises a bf16 [M, N].
 //
 //   FUSE_SILU: A is the raw gate_up projection output [M, 2K] (gate in
 //   cols [0,K), up in [K,2K), reference vLLM SiluAndMul layout); the LDS
@@ -33,6 +40,7 @@
 // the Python wrapper falls back to hipBLASLt otherwise).
 #include "common.h"
 
+#include <algorithm>
 #include <cfloat>
 
 namespace arks {
@@ -47,6 +55,21 @@ __device__ __forceinline__ f32x4 sk_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
 constexpr int SK_NT = 64;  // N rows per workgroup (16 per wave)
 constexpr int SK_AP = 8;   // a_lds row pad (bf16): rows stay 16B-aligned
 
+// Split-K epilogue: f32 partials [split][m][n] (row stride n_total, 16*MT
+// rows per split). A lane holds four consecutive n for one m per M tile, so
+// each tile is one 16 B store; the four la groups of a row write 64 B
+// contiguous. Rows >= m_rows hold garbage and are never read.
+template <int MT>
+__device__ __forceinline__ void store_partials(float* __restrict__ part,
+                                               const f32x4 (&acc)[MT],
+                                               const int n_total,
+                                               const int n, const int lq) {
+  float* p = part + (int64_t)blockIdx.y * (16 * MT) * n_total + n;
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+    *reinterpret_cast<f32x4*>(p + (int64_t)(t * 16 + lq) * n_total) = acc[t];
+}
+
 // MT = number of 16-row M tiles (M <= 16*MT, MT in 1..4).
 // KC = K elements per staged chunk (ping-pong pair in LDS).
 // PF = W register-prefetch distance in chunks (in-flight W = PF*KC*2 B/row).
@@ -55,7 +78,7 @@ constexpr int SK_AP = 8;   // a_lds row pad (bf16): rows stay 16B-aligned
 // the LLC so KV/activation lines survive across decode steps).
 template <int MT, int KC, int PF, bool FUSE_SILU, int AB = 2, bool NT = false>
 __global__ __launch_bounds__(256) void skinny_gemm_kernel(
-    float* __restrict__ part,   // [nsplits, N, 16*MT] (nsplits > 1)
+    float* __restrict__ part,   // [nsplits, 16*MT, N] (nsplits > 1)
     bf16* __restrict__ out,     // [M, N] (nsplits == 1)
     const bf16* __restrict__ a, // [M, K] (row stride a_stride)
     const bf16* __restrict__ w, // [N, K] row-major
@@ -201,17 +224,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
   }
 
   if (nsplits > 1) {
-    // f32 partials, [split][n][m]: lanes with the same la write 64 B
-    // contiguous (m is the fast axis).
-    float* p = part + ((int64_t)blockIdx.y * n_total + n0) * MROWS;
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = wave * 16 + 4 * la + r;
-        p[n * MROWS + t * 16 + lq] = acc[t][r];
-      }
-    }
+    store_partials<MT>(part, acc, n_total, n0 + wave * 16 + 4 * la, lq);
     return;
   }
 
@@ -344,15 +357,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_wave_kernel(
   }
 
   if (nsplits > 1) {
-    float* p = part + ((int64_t)blockIdx.y * n_total + n0) * MROWS;
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = wave * 16 + 4 * la + r;
-        p[n * MROWS + t * 16 + lq] = acc[t][r];
-      }
-    }
+    store_partials<MT>(part, acc, n_total, n0 + wave * 16 + 4 * la, lq);
     return;
   }
 
@@ -435,15 +440,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_direct_kernel(
   }
 
   if (nsplits > 1) {
-    float* p = part + ((int64_t)blockIdx.y * n_total + n0) * MROWS;
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = wave * 16 + 4 * la + r;
-        p[n * MROWS + t * 16 + lq] = acc[t][r];
-      }
-    }
+    store_partials<MT>(part, acc, n_total, n0 + wave * 16 + 4 * la, lq);
     return;
   }
 
@@ -465,67 +462,64 @@ __global__ __launch_bounds__(256) void skinny_gemm_direct_kernel(
   }
 }
 
-// Reduce the split partials: out[m][n] = sum_s part[s][n][m] (+bias[n]).
-// One workgroup per 16-column N-tile (4x the parallelism of v1, which was
-// 93% latency-parked — gpurun_out/pmc); each thread owns a float4 of m for
-// one n, so the per-split reads are 16 B and independent across splits.
-template <int MT>
+// Reduce the split partials: out[m][n] = bf16(sum_s part[s][m][n] + bias[n]).
+// Partials and output share the [m][n] orientation, so this is elementwise:
+// each thread owns four consecutive n of one row (16 B loads per split, all
+// issued before the adds; 8 B store). The decode path does not launch this —
+// its consumers (rmsnorm / rope) reduce the partials themselves; it remains
+// for callers that need a materialised [M, N].
 __global__ __launch_bounds__(256) void skinny_combine_kernel(
     bf16* __restrict__ out, const float* __restrict__ part,
     const bf16* __restrict__ bias, const int m_rows, const int n_total,
-    const int nsplits) {
-  constexpr int MROWS = 16 * MT;
-  constexpr int NT = 16;  // n per workgroup
-  const int n0 = blockIdx.x * NT;
-  const int tid = threadIdx.x;
-  __shared__ float c_lds[NT][MROWS + 1];
-  // thread -> (n, m4): MROWS/4 quads per n
-  for (int i = tid; i < NT * (MROWS / 4); i += 256) {
-    const int n = i / (MROWS / 4);
-    const int m4 = (i % (MROWS / 4)) * 4;
-    float4v s{0.f, 0.f, 0.f, 0.f};
-    for (int sp = 0; sp < nsplits; ++sp) {
-      const float4v v = *reinterpret_cast<const float4v*>(
-          part + ((int64_t)sp * n_total + n0 + n) * MROWS + m4);
+    const int nsplits, const int64_t split_stride) {
+  const int nq = n_total / 4;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= m_rows * nq) return;
+  const int m = i / nq;
+  const int n = (i % nq) * 4;
+  const float* const p[1] = {part + (int64_t)m * n_total + n};
+  float4v s[1];
+  splitk_reduce<1, 2>(p, split_stride, nsplits, s);
+  ushort4v o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] += v[e];
-    }
-    *reinterpret_cast<float4v*>(&c_lds[n][m4]) = s;
+  for (int e = 0; e < 4; ++e) {
+    float v = s[0][e];
+    if (bias != nullptr) v += bf16_bits_to_float(bias[n + e]);
+    o[e] = float_to_bf16_bits(v);
   }
-  __syncthreads();
-  for (int i = tid; i < m_rows * NT; i += 256) {
-    const int m = i / NT;
-    const int n = i % NT;
-    float v = c_lds[n][m];
-    if (bias != nullptr) v += bf16_bits_to_float(bias[n0 + n]);
-    out[(int64_t)m * n_total + n0 + n] = float_to_bf16_bits(v);
-  }
+  *reinterpret_cast<ushort4v*>(out + (int64_t)m * n_total + n) = o;
 }
 
 }  // namespace arks
 
 using namespace arks;
 
+// Fallback for callers that need a materialised [M, N]: reduce partials
+// written by a partials-only GEMM launch (mrows_pad = rows per split slab).
+extern "C" void arks_skinny_combine(void* out, const void* part,
+                                    const void* bias, int m_rows, int n_total,
+                                    int nsplits, int mrows_pad,
+                                    hipStream_t stream) {
+  dim3 cgrid((m_rows * (n_total / 4) + 255) / 256), cblock(256);
+  hipLaunchKernelGGL(skinny_combine_kernel, cgrid, cblock, 0, stream,
+                     (bf16*)out, (const float*)part, (const bf16*)bias, m_rows,
+                     n_total, nsplits, (int64_t)mrows_pad * n_total);
+}
+
+// combine = false (nsplits > 1 only) stops after the GEMM: the f32 partials
+// stay in `part` for a consumer kernel that reduces them itself.
 extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
                                  const void* w, const void* bias, int m_rows,
                                  int n_total, int k_total, int k_per_split,
-                                 int nsplits, int64_t a_stride,
+                                 int nsplits, int64_t a_stride, bool combine,
                                  hipStream_t stream) {
-  const int mt = (m_rows + 15) / 16;
+  const int mt = std::min((m_rows + 15) / 16, 4);
   dim3 grid(n_total / SK_NT, nsplits), block(256);
-  dim3 cgrid(n_total / 16), cblock(256);
 #define SK_LAUNCH(MT)                                                         \
-  do {                                                                        \
-    hipLaunchKernelGGL((skinny_gemm_kernel<MT, 128, 1, false>), grid, block,  \
-                       0, stream, (float*)part, (bf16*)out, (const bf16*)a,   \
-                       (const bf16*)w, (const bf16*)bias, m_rows, n_total,    \
-                       k_total, k_per_split, nsplits, a_stride);              \
-    if (nsplits > 1) {                                                        \
-      hipLaunchKernelGGL((skinny_combine_kernel<MT>), cgrid, cblock, 0,       \
-                         stream, (bf16*)out, (const float*)part,              \
-                         (const bf16*)bias, m_rows, n_total, nsplits);        \
-    }                                                                         \
-  } while (0)
+  hipLaunchKernelGGL((skinny_gemm_kernel<MT, 128, 1, false>), grid, block, 0, \
+                     stream, (float*)part, (bf16*)out, (const bf16*)a,        \
+                     (const bf16*)w, (const bf16*)bias, m_rows, n_total,      \
+                     k_total, k_per_split, nsplits, a_stride)
   switch (mt) {
     case 1: SK_LAUNCH(1); break;
     case 2: SK_LAUNCH(2); break;
@@ -533,6 +527,9 @@ extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
     default: SK_LAUNCH(4); break;
   }
 #undef SK_LAUNCH
+  if (nsplits > 1 && combine)
+    arks_skinny_combine(out, part, bias, m_rows, n_total, nsplits, 16 * mt,
+                        stream);
 }
 
 // Variant entry for the big streaming decode shapes (down-proj), MT=4 only:
@@ -543,9 +540,9 @@ extern "C" void arks_skinny_gemm_v(void* part, void* out, const void* a,
                                    int m_rows, int n_total, int k_total,
                                    int k_per_split, int nsplits,
                                    int64_t a_stride, int variant,
-                                   bool fuse_silu, hipStream_t stream) {
+                                   bool fuse_silu, bool combine,
+                                   hipStream_t stream) {
   dim3 grid(n_total / SK_NT, nsplits), block(256);
-  dim3 cgrid(n_total / 16), cblock(256);
 #define SK_LAUNCH_V(KC, PF, FS)                                               \
   hipLaunchKernelGGL((skinny_gemm_kernel<4, KC, PF, FS>), grid, block, 0,     \
                      stream, (float*)part, (bf16*)out, (const bf16*)a,        \
@@ -592,9 +589,6 @@ extern "C" void arks_skinny_gemm_v(void* part, void* out, const void* a,
   }
 #undef SK_SWITCH
 #undef SK_LAUNCH_V
-  if (nsplits > 1) {
-    hipLaunchKernelGGL((skinny_combine_kernel<4>), cgrid, cblock, 0, stream,
-                       (bf16*)out, (const float*)part, (const bf16*)bias,
-                       m_rows, n_total, nsplits);
-  }
+  if (nsplits > 1 && combine)
+    arks_skinny_combine(out, part, bias, m_rows, n_total, nsplits, 64, stream);
 }

@@ -121,15 +121,20 @@ class ColumnParallelLinear(nn.Module):
     fp8 = False
     lora: LoRAState | None = None  # set when the engine runs enable_lora
 
-    def forward(self, x, lora_tiles=None) -> torch.Tensor:
+    def forward(self, x, lora_tiles=None, defer: bool = False):
+        """defer=True: the caller can consume an ops.SplitKPending in place
+        of the tensor (see ops.skinny_gemm). Granted only where the fused
+        consumers are valid: bf16 GEMM, TP world size 1, no LoRA delta."""
         if isinstance(x, tuple):  # pre-quantized by the producing kernel
             return _fp8_linear_prequant(self, *x)
         if self.fp8:
             return _fp8_linear(self, x)
         from .. import ops
 
-        y = ops.linear_bf16(x, self.weight, self.bias)
-        if lora_tiles is not None and self.lora is not None:
+        use_lora = lora_tiles is not None and self.lora is not None
+        defer = defer and not use_lora and get_tp_world_size() == 1
+        y = ops.linear_bf16(x, self.weight, self.bias, defer=defer)
+        if use_lora:
             self.lora.apply(y, x, lora_tiles)
         return y
 
@@ -221,7 +226,10 @@ class RowParallelLinear(nn.Module):
     fp8 = False
     lora: LoRAState | None = None  # set when the engine runs enable_lora
 
-    def forward(self, x, lora_tiles=None) -> torch.Tensor:
+    def forward(self, x, lora_tiles=None, defer: bool = False):
+        """defer=True: the caller can consume an ops.SplitKPending in place
+        of the tensor. Granted only with TP world size 1, no bias and no LoRA
+        delta; the all-reduce and bias paths below are otherwise unchanged."""
         if isinstance(x, tuple) or self.fp8:
             bias = self.bias
             self.bias = None  # bias must be applied post-reduce, once
@@ -233,8 +241,13 @@ class RowParallelLinear(nn.Module):
         else:
             from .. import ops
 
-            y = ops.linear_bf16(x, self.weight)
-            if lora_tiles is not None and self.lora is not None:
+            use_lora = lora_tiles is not None and self.lora is not None
+            defer = (defer and not use_lora and self.bias is None
+                     and get_tp_world_size() == 1)
+            y = ops.linear_bf16(x, self.weight, defer=defer)
+            if isinstance(y, ops.SplitKPending):
+                return y  # single rank, no bias: nothing left to apply
+            if use_lora:
                 # the delta joins the local partial sum: linear, so the one
                 # all-reduce below covers it
                 self.lora.apply(y, x, lora_tiles)
