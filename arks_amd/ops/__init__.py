@@ -428,54 +428,46 @@ def skinny_gemm(x, weight, bias=None, defer: bool = False):
     reduces the partials itself, saving the combine launch."""
     M, K = x.shape
     N = weight.shape[0]
-    ntiles = N // 64
-    if K > N and ntiles < 128 and M > 48:
-        # tall-K (down-proj shape): few N tiles, parallelism comes from
-        # K-splits; the deeper-staged AB=3 variant at nsplits ~= 448/ntiles
-        # measured fastest (34.6 us vs hipBLASLt's 46.4 in-graph, r2).
-        # M-gated: the variant kernel is fixed at MT=4 (full 64-row cost)
-        # while hipBLASLt switches to a faster algo below M~48 — routing
-        # small-M down-proj here regressed b16x8k decode by 4% (r2)
-        nsplits = min(-(-448 // ntiles), -(-K // 256))
-        k_per_split = -(-(-(-K // nsplits)) // 32) * 32
-        nsplits = -(-K // k_per_split)
-        if defer and nsplits > 1:
-            part = _skinny_ws(nsplits, N, 64, x.device)
-            _native().skinny_gemm_v_partials(part, x, weight, k_per_split,
-                                             nsplits, _SKINNY_TALLK_VARIANT,
-                                             False)
-            return SplitKPending(part, nsplits, 64, M, N, bias,
-                                 (x.device.index,))
-        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-        part = (_skinny_ws(nsplits, N, 64, x.device) if nsplits > 1
-                else x.new_empty(0, dtype=torch.float32))
-        _native().skinny_gemm_v(out, part, x, weight, bias, k_per_split,
-                                nsplits, _SKINNY_TALLK_VARIANT, False)
-        return out
-    if ntiles >= 384:
-        nsplits = 1
-    else:
-        nsplits = min(-(-512 // ntiles), -(-K // 256))
-    k_ceil = -(-K // nsplits)
-    k_per_split = -(-k_ceil // 32) * 32
-    nsplits = -(-K // k_per_split)
+    config, nsplits, k_per_split, mrows = _skinny_plan(M, N, K)
+    part = (_skinny_ws(nsplits, N, mrows, x.device) if nsplits > 1
+            else x.new_empty(0, dtype=torch.float32))
     if defer and nsplits > 1:
-        part = _skinny_ws(nsplits, N, M, x.device)
-        _native().skinny_gemm_partials(part, x, weight, k_per_split, nsplits)
-        return SplitKPending(part, nsplits, ((M + 15) // 16) * 16, M, N, bias,
+        _native().skinny_gemm_partials(part, x, weight, k_per_split, nsplits,
+                                       config)
+        return SplitKPending(part, nsplits, mrows, M, N, bias,
                              (x.device.index,))
     out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    part = _skinny_ws(nsplits, N, M, x.device) if nsplits > 1 else x.new_empty(
-        0, dtype=torch.float32
-    )
-    _native().skinny_gemm(out, part, x, weight, bias, k_per_split, nsplits)
+    _native().skinny_gemm(out, part, x, weight, bias, k_per_split, nsplits,
+                          config)
     return out
 
 
-def _skinny_ws(nsplits: int, N: int, M: int, device):
+def _skinny_plan(M: int, N: int, K: int):
+    """Routing rule of the skinny GEMM: (config, nsplits, k_per_split, mrows).
+    config is the kernel the extension launches (0 = default ring with MT
+    from M, 1 = tall-K, 2 = tall-K with non-temporal W loads); mrows is the
+    slab height of its split-K partials, 16 * MT."""
+    ntiles = N // 64
+    if K > N and ntiles < 128 and M > 48:
+        # tall-K (down-proj shape): few N tiles, parallelism comes from
+        # K-splits; the deeper-staged AB=3 kernel at nsplits ~= 448/ntiles
+        # measured fastest (34.6 us vs hipBLASLt's 46.4 in-graph, r2).
+        # M-gated: that kernel is fixed at MT=4 (full 64-row cost) while
+        # hipBLASLt switches to a faster algo below M~48 — routing small-M
+        # down-proj here regressed b16x8k decode by 4% (r2)
+        config, mt = _SKINNY_TALLK_CONFIG, 4
+        nsplits = min(-(-448 // ntiles), -(-K // 256))
+    else:
+        config, mt = 0, min(-(-M // 16), 4)
+        nsplits = 1 if ntiles >= 384 else min(-(-512 // ntiles), -(-K // 256))
+    k_per_split = -(-(-(-K // nsplits)) // 32) * 32
+    nsplits = -(-K // k_per_split)
+    return config, nsplits, k_per_split, 16 * mt
+
+
+def _skinny_ws(nsplits: int, N: int, mrows: int, device):
     """The device's shared split-K workspace, grown to fit. Every call is
     about to overwrite it, so it also retires outstanding handles."""
-    mrows = ((M + 15) // 16) * 16
     key = (device.index,)
     need = nsplits * N * mrows
     ws = _SKINNY_WS.get(key)
@@ -500,8 +492,16 @@ _SKINNY_MAX_ELEMS = 34_000_000
 # split-K kernel and beat the library's in-graph algo (r2); wide-N shapes
 # (gate_up/lm_head) stay on hipBLASLt which reaches ~6 TB/s there.
 _SKINNY_TALLK_MAX_ELEMS = 80_000_000
-# 7 = AB=3 deep-staged; 8 = same + non-temporal W loads
-_SKINNY_TALLK_VARIANT = int(os.environ.get("ARKS_SKINNY_TALLK_V", "7"))
+# ARKS_SKINNY_TALLK_V picks the tall-K kernel: 7 = AB=3 deep-staged (launch
+# config 1), 8 = same + non-temporal W loads (config 2). The numbers are the
+# variant ids of the r2 experiments; only these two kernels are built.
+_TALLK_V = os.environ.get("ARKS_SKINNY_TALLK_V", "7").strip()
+if _TALLK_V not in ("7", "8"):
+    raise ValueError(
+        f"ARKS_SKINNY_TALLK_V={_TALLK_V!r}: accepted values are 7 (tall-K "
+        "kernel) and 8 (tall-K kernel with non-temporal W loads)"
+    )
+_SKINNY_TALLK_CONFIG = {"7": 1, "8": 2}[_TALLK_V]
 
 
 def linear_bf16(x, weight, bias=None, defer: bool = False):

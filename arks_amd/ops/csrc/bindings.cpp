@@ -27,13 +27,8 @@ void arks_rope_inplace(const void* positions, void* q, void* k,
 void arks_reshape_and_cache(const void* k, const void* v, void* k_cache,
                             void* v_cache, const void* slot_mapping,
                             int num_tokens, int num_kv_heads, int head_dim,
-                            int block_size, int64_t kv_stride,
+                            int block_size, int64_t kv_stride, int kv_fp8,
                             hipStream_t stream);
-void arks_reshape_and_cache_fp8(const void* k, const void* v, void* k_cache,
-                                void* v_cache, const void* slot_mapping,
-                                int num_tokens, int num_kv_heads, int head_dim,
-                                int block_size, int64_t kv_stride,
-                                hipStream_t stream);
 void arks_rope_and_cache(const void* positions, void* q, void* k,
                          const void* v, void* k_cache, void* v_cache,
                          const void* slot_mapping, const void* cos_sin,
@@ -82,12 +77,8 @@ void arks_silu_mul_fp8(void* out, void* inv_scale, const void* gate_up,
 void arks_skinny_gemm(void* part, void* out, const void* a, const void* w,
                       const void* bias, int m_rows, int n_total, int k_total,
                       int k_per_split, int nsplits, int64_t a_stride,
-                      bool combine, hipStream_t stream);
-void arks_skinny_gemm_v(void* part, void* out, const void* a, const void* w,
-                        const void* bias, int m_rows, int n_total, int k_total,
-                        int k_per_split, int nsplits, int64_t a_stride,
-                        int variant, bool fuse_silu, bool combine,
-                        hipStream_t stream);
+                      int config, bool combine, hipStream_t stream);
+int arks_skinny_slab_rows(int m_rows, int config);
 void arks_skinny_combine(void* out, const void* part, const void* bias,
                          int m_rows, int n_total, int nsplits, int mrows_pad,
                          hipStream_t stream);
@@ -218,7 +209,7 @@ void reshape_and_cache(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
                        torch::Tensor v_cache, torch::Tensor slot_mapping) {
   check_bf16_rowstrided(k, "k");
   check_bf16_rowstrided(v, "v");
-  const bool fp8 = check_kv_cache(k_cache, "k_cache");
+  const bool kv_fp8 = check_kv_cache(k_cache, "k_cache");
   check_kv_cache(v_cache, "v_cache");
   TORCH_CHECK(slot_mapping.scalar_type() == torch::kInt64);
   TORCH_CHECK(k.stride(0) == v.stride(0), "k/v must share row stride");
@@ -227,11 +218,10 @@ void reshape_and_cache(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
   const int block_size = k_cache.size(2);
   const int head_dim = k_cache.size(3);
   TORCH_CHECK(head_dim % 8 == 0);
-  auto fn = fp8 ? arks_reshape_and_cache_fp8 : arks_reshape_and_cache;
-  fn(k.data_ptr(), v.data_ptr(), k_cache.data_ptr(),
-     v_cache.data_ptr(), slot_mapping.data_ptr(),
-     num_tokens, num_kv_heads, head_dim, block_size,
-     k.stride(0), current_stream());
+  arks_reshape_and_cache(k.data_ptr(), v.data_ptr(), k_cache.data_ptr(),
+                         v_cache.data_ptr(), slot_mapping.data_ptr(),
+                         num_tokens, num_kv_heads, head_dim, block_size,
+                         k.stride(0), kv_fp8 ? 1 : 0, current_stream());
 }
 
 void rope_and_cache(torch::Tensor positions, torch::Tensor q,
@@ -437,72 +427,43 @@ const void* check_skinny_args(const torch::Tensor& out,
   return bias_ptr;
 }
 
+// config selects the kernel (skinny_gemm.hip): 0 = default ring with MT from
+// M, 1 = tall-K, 2 = tall-K with non-temporal W loads.
 void skinny_gemm_impl(torch::Tensor out, torch::Tensor part, torch::Tensor a,
                       torch::Tensor w, c10::optional<torch::Tensor> bias,
-                      int64_t k_per_split, int64_t nsplits, bool combine) {
+                      int64_t k_per_split, int64_t nsplits, int64_t config,
+                      bool combine) {
   const int m = a.size(0), k = a.size(1), n = w.size(0);
   TORCH_CHECK(w.size(1) == k);
+  TORCH_CHECK(0 <= config && config <= 2, "config in 0..2");
   TORCH_CHECK(k_per_split >= 32 && k_per_split % 32 == 0 &&
               nsplits * k_per_split >= k, "splits must cover K");
-  const int mrows = ((m + 15) / 16) * 16;
+  const int mrows = arks_skinny_slab_rows(m, (int)config);
   const void* bias_ptr = check_skinny_args(out, part, a, w, bias, k, nsplits,
                                            mrows, !combine, "skinny_gemm");
   arks_skinny_gemm(nsplits > 1 ? part.data_ptr() : nullptr,
                    combine ? out.data_ptr() : nullptr, a.data_ptr(),
                    w.data_ptr(), bias_ptr, m, n, k, (int)k_per_split,
-                   (int)nsplits, a.stride(0), combine, current_stream());
+                   (int)nsplits, a.stride(0), (int)config, combine,
+                   current_stream());
 }
 
 void skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
                  torch::Tensor w, c10::optional<torch::Tensor> bias,
-                 int64_t k_per_split, int64_t nsplits) {
-  skinny_gemm_impl(out, part, a, w, bias, k_per_split, nsplits, true);
+                 int64_t k_per_split, int64_t nsplits, int64_t config) {
+  skinny_gemm_impl(out, part, a, w, bias, k_per_split, nsplits, config, true);
 }
 
 // Partials-only launch (nsplits > 1): leaves the f32 split-K partials
-// [nsplits, ceil16(M), N] in `part` for a consumer that reduces them
-// (splitk_add_rmsnorm / splitk_rope_and_cache / skinny_combine). The bias is
-// applied by that consumer, not here.
+// [nsplits, slab rows, N] in `part` (slab rows = 16 * MT of the kernel that
+// config launches) for a consumer that reduces them (splitk_add_rmsnorm /
+// splitk_rope_and_cache / skinny_combine). The bias is applied by that
+// consumer, not here.
 void skinny_gemm_partials(torch::Tensor part, torch::Tensor a, torch::Tensor w,
-                          int64_t k_per_split, int64_t nsplits) {
+                          int64_t k_per_split, int64_t nsplits,
+                          int64_t config) {
   skinny_gemm_impl(torch::Tensor(), part, a, w, c10::nullopt, k_per_split,
-                   nsplits, false);
-}
-
-// Variant/fused entry (MT fixed at 4, i.e. M <= 64). fuse_silu: `a` is the
-// gate_up output [M, >=2K] (gate cols [0,K), up cols [K,2K)).
-void skinny_gemm_v_impl(torch::Tensor out, torch::Tensor part, torch::Tensor a,
-                        torch::Tensor w, c10::optional<torch::Tensor> bias,
-                        int64_t k_per_split, int64_t nsplits, int64_t variant,
-                        bool fuse_silu, bool combine) {
-  const int m = a.size(0), k = w.size(1), n = w.size(0);
-  TORCH_CHECK(a.size(1) >= (fuse_silu ? 2 * k : k), "A too narrow");
-  TORCH_CHECK(0 <= variant && variant <= 8, "variant in 0..8");
-  TORCH_CHECK(k_per_split >= 32 && k_per_split % 32 == 0 &&
-              nsplits * k_per_split >= k, "splits must cover K");
-  const void* bias_ptr = check_skinny_args(out, part, a, w, bias, k, nsplits,
-                                           64, !combine, "skinny_gemm_v");
-  arks_skinny_gemm_v(nsplits > 1 ? part.data_ptr() : nullptr,
-                     combine ? out.data_ptr() : nullptr, a.data_ptr(),
-                     w.data_ptr(), bias_ptr, m, n, k, (int)k_per_split,
-                     (int)nsplits, a.stride(0), (int)variant, fuse_silu,
-                     combine, current_stream());
-}
-
-void skinny_gemm_v(torch::Tensor out, torch::Tensor part, torch::Tensor a,
-                   torch::Tensor w, c10::optional<torch::Tensor> bias,
-                   int64_t k_per_split, int64_t nsplits, int64_t variant,
-                   bool fuse_silu) {
-  skinny_gemm_v_impl(out, part, a, w, bias, k_per_split, nsplits, variant,
-                     fuse_silu, true);
-}
-
-// Partials-only variant launch: partials are [nsplits, 64, N].
-void skinny_gemm_v_partials(torch::Tensor part, torch::Tensor a,
-                            torch::Tensor w, int64_t k_per_split,
-                            int64_t nsplits, int64_t variant, bool fuse_silu) {
-  skinny_gemm_v_impl(torch::Tensor(), part, a, w, c10::nullopt, k_per_split,
-                     nsplits, variant, fuse_silu, false);
+                   nsplits, config, false);
 }
 
 // Checks shared by the consumers of split-K partials [nsplits, mrows, n].
@@ -883,10 +844,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quant_fp8_rows", &quant_fp8_rows);
   m.def("rmsnorm_fp8", &rmsnorm_fp8);
   m.def("silu_mul_fp8", &silu_mul_fp8);
-  m.def("skinny_gemm", &skinny_gemm);
-  m.def("skinny_gemm_v", &skinny_gemm_v);
-  m.def("skinny_gemm_partials", &skinny_gemm_partials);
-  m.def("skinny_gemm_v_partials", &skinny_gemm_v_partials);
+  m.def("skinny_gemm", &skinny_gemm, py::arg("out"), py::arg("part"),
+        py::arg("a"), py::arg("w"), py::arg("bias"), py::arg("k_per_split"),
+        py::arg("nsplits"), py::arg("config") = 0);
+  m.def("skinny_gemm_partials", &skinny_gemm_partials, py::arg("part"),
+        py::arg("a"), py::arg("w"), py::arg("k_per_split"),
+        py::arg("nsplits"), py::arg("config") = 0);
   m.def("skinny_combine", &skinny_combine);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache);

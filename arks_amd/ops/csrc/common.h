@@ -128,6 +128,20 @@ __device__ __forceinline__ void splitk_reduce(const float* const (&p)[W],
   }
 }
 
+// One rotary pair (a, b) by (c, s), rounded to bf16, with the contraction
+// written out: o1 = fma(a, c, -(b*s)), o2 = fma(b, c, a*s). Every RoPE kernel
+// (rope_kernel, rope_cache_kernel, splitk_rope_cache_kernel) rotates through
+// this one function, so they agree to the last bit by construction. Left to
+// the compiler, `a*c - b*s` / `b*c + a*s` were contracted per instantiation
+// and one kernel came out the other way round for o2, differing from the
+// others in the last bf16 bit about once in 1e5 elements.
+__device__ __forceinline__ void rope_rotate(const float a, const float b,
+                                            const float c, const float s,
+                                            uint16_t& o1, uint16_t& o2) {
+  o1 = float_to_bf16_bits(__builtin_fmaf(a, c, -(b * s)));
+  o2 = float_to_bf16_bits(__builtin_fmaf(b, c, a * s));
+}
+
 __host__ __forceinline__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // OCP e4m3 <-> bf16 bit conversions for the fp8 KV cache (scale 1.0; the

@@ -15,55 +15,40 @@ __device__ __forceinline__ float add_square(const float ss, const float v) {
   return ss + v * v;
 }
 
-// ---------------------------------------------------------------------------
-// RMSNorm: one workgroup (256 threads = 4 waves) per row.
-// hidden must be a multiple of 8 (bf16x8 vector loads).
-// ---------------------------------------------------------------------------
-template <bool FUSED_ADD>
-__global__ void rmsnorm_kernel(bf16* __restrict__ out,
-                               const bf16* __restrict__ input,
-                               bf16* __restrict__ residual,  // null unless FUSED_ADD
-                               const bf16* __restrict__ weight,
-                               const float eps, const int hidden) {
-  constexpr int BLOCK = 256;
-  const int row = blockIdx.x;
-  const bf16* in_row = input + (int64_t)row * hidden;
-  bf16* res_row = FUSED_ADD ? residual + (int64_t)row * hidden : nullptr;
-  bf16* out_row = out + (int64_t)row * hidden;
+// The norm kernels below run one workgroup of NORM_BLOCK threads (4 waves)
+// per row, 8 columns per thread per iteration; that map and
+// block_reduce_sum<NORM_BLOCK> fix the summation order of the sum of squares.
+constexpr int NORM_BLOCK = 256;
 
-  const int nvec = hidden / 8;
-  float ss = 0.f;
-  // Pass 1: (optionally add residual and store it), accumulate sum of squares.
-  for (int i = threadIdx.x; i < nvec; i += BLOCK) {
-    ushort8 x = *reinterpret_cast<const ushort8*>(in_row + i * 8);
-    if constexpr (FUSED_ADD) {
-      ushort8 r = *reinterpret_cast<const ushort8*>(res_row + i * 8);
-      ushort8 s;
+// Pass-1 step of the fused-add norms for eight columns: residual += x,
+// rounded to bf16 and stored back; returns ss plus the squares of the
+// ROUNDED sums, so that pass 2's re-read sees what was accumulated.
+__device__ __forceinline__ float add_residual8(const ushort8 x,
+                                               bf16* __restrict__ res,
+                                               float ss) {
+  ushort8 r = *reinterpret_cast<const ushort8*>(res);
+  ushort8 s;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float v = bf16_bits_to_float(x[j]) + bf16_bits_to_float(r[j]);
-        s[j] = float_to_bf16_bits(v);
-        // Accumulate on the bf16-rounded value so pass 2's re-read matches.
-        float vb = bf16_bits_to_float(s[j]);
-        ss = add_square(ss, vb);
-      }
-      *reinterpret_cast<ushort8*>(res_row + i * 8) = s;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float v = bf16_bits_to_float(x[j]);
-        ss += v * v;
-      }
-    }
+  for (int j = 0; j < 8; ++j) {
+    float v = bf16_bits_to_float(x[j]) + bf16_bits_to_float(r[j]);
+    s[j] = float_to_bf16_bits(v);
+    ss = add_square(ss, bf16_bits_to_float(s[j]));
   }
+  *reinterpret_cast<ushort8*>(res) = s;
+  return ss;
+}
 
-  __shared__ float red[BLOCK / WAVE_SIZE];
-  float total = block_reduce_sum<BLOCK>(ss, red);
+// Passes 1.5 and 2 of every norm: block-reduce the sum of squares, then
+// normalize src_row (re-read from L1/L2), scale by weight, round.
+__device__ __forceinline__ void rmsnorm_finish(bf16* __restrict__ out_row,
+                                               const bf16* __restrict__ src_row,
+                                               const bf16* __restrict__ weight,
+                                               const float ss, const float eps,
+                                               const int hidden) {
+  __shared__ float red[NORM_BLOCK / WAVE_SIZE];
+  float total = block_reduce_sum<NORM_BLOCK>(ss, red);
   const float rrms = rsqrtf(total / (float)hidden + eps);
-
-  // Pass 2: normalize (re-read from L1/L2) and scale by weight.
-  const bf16* src_row = FUSED_ADD ? res_row : in_row;
-  for (int i = threadIdx.x; i < nvec; i += BLOCK) {
+  for (int i = threadIdx.x; i < hidden / 8; i += NORM_BLOCK) {
     ushort8 x = *reinterpret_cast<const ushort8*>(src_row + i * 8);
     ushort8 w = *reinterpret_cast<const ushort8*>(weight + i * 8);
     ushort8 o;
@@ -77,13 +62,46 @@ __global__ void rmsnorm_kernel(bf16* __restrict__ out,
 }
 
 // ---------------------------------------------------------------------------
+// RMSNorm, optionally with the residual add fused in.
+// hidden must be a multiple of 8 (bf16x8 vector loads).
+// ---------------------------------------------------------------------------
+template <bool FUSED_ADD>
+__global__ void rmsnorm_kernel(bf16* __restrict__ out,
+                               const bf16* __restrict__ input,
+                               bf16* __restrict__ residual,  // null unless FUSED_ADD
+                               const bf16* __restrict__ weight,
+                               const float eps, const int hidden) {
+  const int row = blockIdx.x;
+  const bf16* in_row = input + (int64_t)row * hidden;
+  bf16* res_row = FUSED_ADD ? residual + (int64_t)row * hidden : nullptr;
+
+  const int nvec = hidden / 8;
+  float ss = 0.f;
+  // Pass 1: (optionally add residual and store it), accumulate sum of squares.
+  for (int i = threadIdx.x; i < nvec; i += NORM_BLOCK) {
+    ushort8 x = *reinterpret_cast<const ushort8*>(in_row + i * 8);
+    if constexpr (FUSED_ADD) {
+      ss = add_residual8(x, res_row + i * 8, ss);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v = bf16_bits_to_float(x[j]);
+        ss += v * v;
+      }
+    }
+  }
+  rmsnorm_finish(out + (int64_t)row * hidden, FUSED_ADD ? res_row : in_row,
+                 weight, ss, eps, hidden);
+}
+
+// ---------------------------------------------------------------------------
 // Fused residual-add + RMSNorm whose input is still the split-K partials of
 // the producing skinny GEMM (skinny_gemm.hip, layout [split][m][n]): each
 // element is reduced in split order, biased and rounded to bf16 exactly as
-// skinny_combine_kernel would, then treated as rmsnorm_kernel<true> treats
-// its input. Same 256-thread / 8-columns-per-iteration map and block
-// reduce, so the sum of squares (and rrms) is bit-identical to the unfused
-// pair; what goes away is the combine launch and its bf16 round trip.
+// skinny_combine_kernel would, then goes through the very helpers
+// rmsnorm_kernel<true> uses, so the residual, the sum of squares and the
+// output are bit-identical to the unfused pair; what goes away is the
+// combine launch and its bf16 round trip.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void splitk_add_rmsnorm_kernel(
     bf16* __restrict__ out, const float* __restrict__ part,
@@ -91,50 +109,27 @@ __global__ __launch_bounds__(256) void splitk_add_rmsnorm_kernel(
     bf16* __restrict__ residual, const bf16* __restrict__ weight,
     const float eps, const int hidden, const int nsplits,
     const int64_t split_stride) {
-  constexpr int BLOCK = 256;
   const int row = blockIdx.x;
   const float* part_row = part + (int64_t)row * hidden;
   bf16* res_row = residual + (int64_t)row * hidden;
-  bf16* out_row = out + (int64_t)row * hidden;
 
   const int nvec = hidden / 8;
   float ss = 0.f;
-  for (int i = threadIdx.x; i < nvec; i += BLOCK) {
+  for (int i = threadIdx.x; i < nvec; i += NORM_BLOCK) {
     const float* const p[2] = {part_row + i * 8, part_row + i * 8 + 4};
     float4v acc[2];
     splitk_reduce<2, 2>(p, split_stride, nsplits, acc);
-    ushort8 r = *reinterpret_cast<const ushort8*>(res_row + i * 8);
-    ushort8 s;
+    ushort8 x;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float xf = acc[j / 4][j % 4];
       if (bias != nullptr) xf += bf16_bits_to_float(bias[i * 8 + j]);
-      const uint16_t x = float_to_bf16_bits(xf);  // the combine's rounding
-      float v = bf16_bits_to_float(x) + bf16_bits_to_float(r[j]);
-      s[j] = float_to_bf16_bits(v);
-      float vb = bf16_bits_to_float(s[j]);
-      ss = add_square(ss, vb);
+      x[j] = float_to_bf16_bits(xf);  // the combine's rounding
     }
-    *reinterpret_cast<ushort8*>(res_row + i * 8) = s;
+    ss = add_residual8(x, res_row + i * 8, ss);
   }
-
-  __shared__ float red[BLOCK / WAVE_SIZE];
-  float total = block_reduce_sum<BLOCK>(ss, red);
-  const float rrms = rsqrtf(total / (float)hidden + eps);
-
-  // Pass 2: re-read the residual this thread just wrote (L1/L2), as
-  // rmsnorm_kernel<true> does.
-  for (int i = threadIdx.x; i < nvec; i += BLOCK) {
-    ushort8 x = *reinterpret_cast<const ushort8*>(res_row + i * 8);
-    ushort8 w = *reinterpret_cast<const ushort8*>(weight + i * 8);
-    ushort8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float v = bf16_bits_to_float(x[j]) * rrms * bf16_bits_to_float(w[j]);
-      o[j] = float_to_bf16_bits(v);
-    }
-    *reinterpret_cast<ushort8*>(out_row + i * 8) = o;
-  }
+  rmsnorm_finish(out + (int64_t)row * hidden, res_row, weight, ss, eps,
+                 hidden);
 }
 
 // ---------------------------------------------------------------------------
@@ -194,12 +189,11 @@ __global__ void rope_kernel(const int64_t* __restrict__ positions,
     ushort2v o1, o2;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const float c = cs[p2 + j];
-      const float s = cs[half + p2 + j];
-      const float a = bf16_bits_to_float(x1[j]);
-      const float b = bf16_bits_to_float(x2[j]);
-      o1[j] = float_to_bf16_bits(a * c - b * s);
-      o2[j] = float_to_bf16_bits(b * c + a * s);
+      uint16_t r1, r2;
+      rope_rotate(bf16_bits_to_float(x1[j]), bf16_bits_to_float(x2[j]),
+                  cs[p2 + j], cs[half + p2 + j], r1, r2);
+      o1[j] = r1;
+      o2[j] = r2;
     }
     *reinterpret_cast<ushort2v*>(base + p2) = o1;
     *reinterpret_cast<ushort2v*>(base + half + p2) = o2;

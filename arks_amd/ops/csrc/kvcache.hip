@@ -1,108 +1,39 @@
-// Paged KV-cache scatter: write the new tokens' K/V into their assigned slots.
-// Cache layout: [num_blocks, num_kv_heads, block_size, head_dim] bf16
-// slot = block_id * block_size + offset  (flat, per token)
-#include "common.h"
+// Paged KV-cache writers: scatter the new tokens' K/V into their assigned
+// slots, alone or fused with RoPE (and with the split-K reduction of the qkv
+// GEMM). Cache layout, slot addressing and the bf16 / e4m3 stores are in
+// kv_store.h; the rotation is rope_rotate (common.h).
+#include "kv_store.h"
 
-#include <hip/hip_fp8.h>
+#include <type_traits>
 
 namespace arks {
 
+template <bool FP8>
 __global__ void reshape_and_cache_kernel(
     const bf16* __restrict__ k,  // [T, Hkv, D], token rows strided
     const bf16* __restrict__ v,
-    bf16* __restrict__ k_cache,  // [B, Hkv, block_size, D]
-    bf16* __restrict__ v_cache,
+    void* __restrict__ k_cache,  // [B, Hkv, block_size, D] bf16 or e4m3
+    void* __restrict__ v_cache,
     const int64_t* __restrict__ slot_mapping,  // [T]
     const int num_kv_heads, const int head_dim, const int block_size,
     const int64_t kv_stride) {
   const int token = blockIdx.x;
-  const int64_t slot = slot_mapping[token];
-  if (slot < 0) return;  // padding slot
-  const int64_t block_id = slot / block_size;
-  const int offset = (int)(slot % block_size);
+  const CachePage pg =
+      cache_page(slot_mapping[token], num_kv_heads, block_size, head_dim);
+  if (!pg.valid) return;  // padding slot
   const int nvec = num_kv_heads * head_dim / 8;
   const bf16* k_src = k + (int64_t)token * kv_stride;
   const bf16* v_src = v + (int64_t)token * kv_stride;
   for (int i = threadIdx.x; i < nvec; i += blockDim.x) {
     const int h = (i * 8) / head_dim;
     const int d = (i * 8) % head_dim;
-    const int64_t dst = ((block_id * num_kv_heads + h) * block_size + offset) *
-                            head_dim + d;
-    *reinterpret_cast<ushort8*>(k_cache + dst) =
-        *reinterpret_cast<const ushort8*>(k_src + i * 8);
-    *reinterpret_cast<ushort8*>(v_cache + dst) =
-        *reinterpret_cast<const ushort8*>(v_src + i * 8);
+    const int64_t dst = pg.base + (int64_t)h * pg.hstride + d;
+    cache_store<FP8>(k_cache, dst,
+                     *reinterpret_cast<const ushort8*>(k_src + i * 8));
+    cache_store<FP8>(v_cache, dst,
+                     *reinterpret_cast<const ushort8*>(v_src + i * 8));
   }
 }
-
-__global__ void reshape_and_cache_fp8_kernel(
-    const bf16* __restrict__ k,  // [T, Hkv, D], token rows strided
-    const bf16* __restrict__ v,
-    uint8_t* __restrict__ k_cache,  // [B, Hkv, block_size, D] e4m3
-    uint8_t* __restrict__ v_cache,
-    const int64_t* __restrict__ slot_mapping,  // [T]
-    const int num_kv_heads, const int head_dim, const int block_size,
-    const int64_t kv_stride) {
-  const int token = blockIdx.x;
-  const int64_t slot = slot_mapping[token];
-  if (slot < 0) return;  // padding slot
-  const int64_t block_id = slot / block_size;
-  const int offset = (int)(slot % block_size);
-  const int nvec = num_kv_heads * head_dim / 8;
-  const bf16* k_src = k + (int64_t)token * kv_stride;
-  const bf16* v_src = v + (int64_t)token * kv_stride;
-  for (int i = threadIdx.x; i < nvec; i += blockDim.x) {
-    const int h = (i * 8) / head_dim;
-    const int d = (i * 8) % head_dim;
-    const int64_t dst = ((block_id * num_kv_heads + h) * block_size + offset) *
-                            head_dim + d;
-    ushort8 kv8 = *reinterpret_cast<const ushort8*>(k_src + i * 8);
-    ushort8 vv8 = *reinterpret_cast<const ushort8*>(v_src + i * 8);
-    uchar8 ko, vo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      __hip_fp8_e4m3 kq(bf16_bits_to_float(kv8[e]));
-      __hip_fp8_e4m3 vq(bf16_bits_to_float(vv8[e]));
-      ko[e] = kq.__x;
-      vo[e] = vq.__x;
-    }
-    *reinterpret_cast<uchar8*>(k_cache + dst) = ko;
-    *reinterpret_cast<uchar8*>(v_cache + dst) = vo;
-  }
-}
-
-}  // namespace arks
-
-using namespace arks;
-
-extern "C" void arks_reshape_and_cache_fp8(
-    const void* k, const void* v, void* k_cache, void* v_cache,
-    const void* slot_mapping, int num_tokens, int num_kv_heads, int head_dim,
-    int block_size, int64_t kv_stride, hipStream_t stream) {
-  if (num_tokens == 0) return;
-  int threads = std::min(256, num_kv_heads * head_dim / 8);
-  hipLaunchKernelGGL(reshape_and_cache_fp8_kernel, dim3(num_tokens),
-                     dim3(threads), 0, stream, (const bf16*)k, (const bf16*)v,
-                     (uint8_t*)k_cache, (uint8_t*)v_cache,
-                     (const int64_t*)slot_mapping, num_kv_heads, head_dim,
-                     block_size, kv_stride);
-}
-
-extern "C" void arks_reshape_and_cache(const void* k, const void* v,
-                                       void* k_cache, void* v_cache,
-                                       const void* slot_mapping, int num_tokens,
-                                       int num_kv_heads, int head_dim,
-                                       int block_size, int64_t kv_stride,
-                                       hipStream_t stream) {
-  if (num_tokens == 0) return;
-  int threads = std::min(256, num_kv_heads * head_dim / 8);
-  hipLaunchKernelGGL(reshape_and_cache_kernel, dim3(num_tokens), dim3(threads),
-                     0, stream, (const bf16*)k, (const bf16*)v, (bf16*)k_cache,
-                     (bf16*)v_cache, (const int64_t*)slot_mapping, num_kv_heads,
-                     head_dim, block_size, kv_stride);
-}
-
-namespace arks {
 
 // ---------------------------------------------------------------------------
 // Fused RoPE + cache write: rotate q/k in place AND scatter the rotated k
@@ -129,14 +60,8 @@ __global__ void rope_cache_kernel(
   const int half = head_dim / 2;
   const int64_t pos = positions[token];
   const float* cs = cos_sin + pos * head_dim;
-  const int64_t slot = slot_mapping[token];
-  const bool cache = slot >= 0;
-  const int64_t block_id = cache ? slot / block_size : 0;
-  const int offset = cache ? (int)(slot % block_size) : 0;
-  const int64_t cbase =
-      (block_id * num_kv_heads) * (int64_t)block_size * head_dim +
-      (int64_t)offset * head_dim;
-  const int64_t hstride = (int64_t)block_size * head_dim;
+  const CachePage pg =
+      cache_page(slot_mapping[token], num_kv_heads, block_size, head_dim);
 
   const int total_heads = num_q_heads + num_kv_heads;
   const int pairs2 = half / 2;
@@ -153,70 +78,30 @@ __global__ void rope_cache_kernel(
     ushort2v o1, o2;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const float c = cs[p2 + j];
-      const float s = cs[half + p2 + j];
-      const float a = bf16_bits_to_float(x1[j]);
-      const float b = bf16_bits_to_float(x2[j]);
-      o1[j] = float_to_bf16_bits(a * c - b * s);
-      o2[j] = float_to_bf16_bits(b * c + a * s);
+      uint16_t r1, r2;
+      rope_rotate(bf16_bits_to_float(x1[j]), bf16_bits_to_float(x2[j]),
+                  cs[p2 + j], cs[half + p2 + j], r1, r2);
+      o1[j] = r1;
+      o2[j] = r2;
     }
     *reinterpret_cast<ushort2v*>(base + p2) = o1;
     *reinterpret_cast<ushort2v*>(base + half + p2) = o2;
-    if (!is_q && cache) {
-      const int64_t dst = cbase + (int64_t)(h - num_q_heads) * hstride;
-      if constexpr (FP8) {
-        uint8_t* kc = reinterpret_cast<uint8_t*>(k_cache);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          // convert from the bf16-ROUNDED values so the cache is
-          // bit-identical to the separate rope + reshape_and_cache path
-          __hip_fp8_e4m3 a(bf16_bits_to_float(o1[j]));
-          __hip_fp8_e4m3 b(bf16_bits_to_float(o2[j]));
-          kc[dst + p2 + j] = a.__x;
-          kc[dst + half + p2 + j] = b.__x;
-        }
-      } else {
-        bf16* kc = reinterpret_cast<bf16*>(k_cache);
-        *reinterpret_cast<ushort2v*>(kc + dst + p2) = o1;
-        *reinterpret_cast<ushort2v*>(kc + dst + half + p2) = o2;
-      }
+    if (!is_q && pg.valid) {
+      const int64_t dst = pg.base + (int64_t)(h - num_q_heads) * pg.hstride;
+      cache_store<FP8>(k_cache, dst + p2, o1);
+      cache_store<FP8>(k_cache, dst + half + p2, o2);
     }
   }
-  if (!cache) return;
+  if (!pg.valid) return;
   // v: plain copy into the page (vectorized 8)
   const bf16* v_src = v + (int64_t)token * k_stride;
   const int nvec = num_kv_heads * head_dim / 8;
   for (int i = threadIdx.x; i < nvec; i += blockDim.x) {
     const int h = (i * 8) / head_dim;
     const int d = (i * 8) % head_dim;
-    const int64_t dst = cbase + (int64_t)h * hstride + d;
-    ushort8 vv8 = *reinterpret_cast<const ushort8*>(v_src + i * 8);
-    if constexpr (FP8) {
-      uchar8 vo;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        __hip_fp8_e4m3 vq(bf16_bits_to_float(vv8[e]));
-        vo[e] = vq.__x;
-      }
-      *reinterpret_cast<uchar8*>(reinterpret_cast<uint8_t*>(v_cache) + dst) = vo;
-    } else {
-      *reinterpret_cast<ushort8*>(reinterpret_cast<bf16*>(v_cache) + dst) = vv8;
-    }
+    cache_store<FP8>(v_cache, pg.base + (int64_t)h * pg.hstride + d,
+                     *reinterpret_cast<const ushort8*>(v_src + i * 8));
   }
-}
-
-// One rotary pair (a, b) by (c, s), rounded to bf16, with the contraction
-// written out: o1 = fma(a, c, -(b*s)), o2 = fma(b, c, a*s). That is the form
-// the compiler gives rope_cache_kernel's `a*c - b*s` / `b*c + a*s` (read off
-// its ISA); the same expressions inside the partials-reading kernel below
-// were contracted the other way round for o2 and then differed from
-// rope_cache_kernel in the last bf16 bit about once in 1e5 elements. The
-// bit-equality tests at the full decode shapes guard the pairing.
-__device__ __forceinline__ void rope_rotate(const float a, const float b,
-                                            const float c, const float s,
-                                            uint16_t& o1, uint16_t& o2) {
-  o1 = float_to_bf16_bits(__builtin_fmaf(a, c, -(b * s)));
-  o2 = float_to_bf16_bits(__builtin_fmaf(b, c, a * s));
 }
 
 // ---------------------------------------------------------------------------
@@ -251,14 +136,8 @@ __global__ __launch_bounds__(1024) void splitk_rope_cache_kernel(
   const int n_total = (num_q_heads + 2 * num_kv_heads) * head_dim;
   const int64_t pos = positions[token];
   const float* cs = cos_sin + pos * head_dim;
-  const int64_t slot = slot_mapping[token];
-  const bool cache = slot >= 0;
-  const int64_t block_id = cache ? slot / block_size : 0;
-  const int offset = cache ? (int)(slot % block_size) : 0;
-  const int64_t cbase =
-      (block_id * num_kv_heads) * (int64_t)block_size * head_dim +
-      (int64_t)offset * head_dim;
-  const int64_t hstride = (int64_t)block_size * head_dim;
+  const CachePage pg =
+      cache_page(slot_mapping[token], num_kv_heads, block_size, head_dim);
   const float* part_row = part + (int64_t)token * n_total;
 
   // q and k heads are consecutive column blocks of the fused row, so head h
@@ -266,8 +145,8 @@ __global__ __launch_bounds__(1024) void splitk_rope_cache_kernel(
   const int quads = half / 4;  // pair-quads per head
   const int nrot_q = num_q_heads * quads;
   // without a cache slot neither k nor v is needed by anyone
-  const int nrot = cache ? nrot_q + num_kv_heads * quads : nrot_q;
-  const int nvec = cache ? num_kv_heads * head_dim / 8 : 0;
+  const int nrot = pg.valid ? nrot_q + num_kv_heads * quads : nrot_q;
+  const int nvec = pg.valid ? num_kv_heads * head_dim / 8 : 0;
   const int v_col0 = (num_q_heads + num_kv_heads) * head_dim;
   for (int idx = threadIdx.x; idx < nrot + nvec; idx += blockDim.x) {
     if (idx < nrot) {
@@ -299,28 +178,15 @@ __global__ __launch_bounds__(1024) void splitk_rope_cache_kernel(
         *reinterpret_cast<ushort4v*>(base + p4) = o1;
         *reinterpret_cast<ushort4v*>(base + half + p4) = o2;
       } else {
-        const int64_t dst = cbase + (int64_t)(h - num_q_heads) * hstride;
-        if constexpr (FP8) {
-          uint8_t* kc = reinterpret_cast<uint8_t*>(k_cache);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            __hip_fp8_e4m3 a(bf16_bits_to_float(o1[j]));
-            __hip_fp8_e4m3 b(bf16_bits_to_float(o2[j]));
-            kc[dst + p4 + j] = a.__x;
-            kc[dst + half + p4 + j] = b.__x;
-          }
-        } else {
-          bf16* kc = reinterpret_cast<bf16*>(k_cache);
-          *reinterpret_cast<ushort4v*>(kc + dst + p4) = o1;
-          *reinterpret_cast<ushort4v*>(kc + dst + half + p4) = o2;
-        }
+        const int64_t dst = pg.base + (int64_t)(h - num_q_heads) * pg.hstride;
+        cache_store<FP8>(k_cache, dst + p4, o1);
+        cache_store<FP8>(k_cache, dst + half + p4, o2);
       }
     } else {
       // v: reduce + round, straight into the page (vectorized 8)
       const int i = idx - nrot;
       const int h = (i * 8) / head_dim;
       const int d = (i * 8) % head_dim;
-      const int64_t dst = cbase + (int64_t)h * hstride + d;
       const int col = v_col0 + i * 8;
       const float* const p[2] = {part_row + col, part_row + col + 4};
       float4v acc[2];
@@ -332,24 +198,41 @@ __global__ __launch_bounds__(1024) void splitk_rope_cache_kernel(
         if (bias != nullptr) vf += bf16_bits_to_float(bias[col + e]);
         vv8[e] = float_to_bf16_bits(vf);
       }
-      if constexpr (FP8) {
-        uchar8 vo;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          __hip_fp8_e4m3 vq(bf16_bits_to_float(vv8[e]));
-          vo[e] = vq.__x;
-        }
-        *reinterpret_cast<uchar8*>(reinterpret_cast<uint8_t*>(v_cache) + dst) =
-            vo;
-      } else {
-        *reinterpret_cast<ushort8*>(reinterpret_cast<bf16*>(v_cache) + dst) =
-            vv8;
-      }
+      cache_store<FP8>(v_cache, pg.base + (int64_t)h * pg.hstride + d, vv8);
     }
   }
 }
 
 }  // namespace arks
+
+using namespace arks;
+
+// Calls f(std::true_type) for an e4m3 cache, f(std::false_type) for bf16, so
+// a launcher names its kernel template once.
+template <typename F>
+static void dispatch_kv_fp8(int kv_fp8, F&& f) {
+  if (kv_fp8)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
+extern "C" void arks_reshape_and_cache(const void* k, const void* v,
+                                       void* k_cache, void* v_cache,
+                                       const void* slot_mapping, int num_tokens,
+                                       int num_kv_heads, int head_dim,
+                                       int block_size, int64_t kv_stride,
+                                       int kv_fp8, hipStream_t stream) {
+  if (num_tokens == 0) return;
+  int threads = std::min(256, num_kv_heads * head_dim / 8);
+  dispatch_kv_fp8(kv_fp8, [&](auto fp8) {
+    hipLaunchKernelGGL((reshape_and_cache_kernel<decltype(fp8)::value>),
+                       dim3(num_tokens), dim3(threads), 0, stream,
+                       (const bf16*)k, (const bf16*)v, k_cache, v_cache,
+                       (const int64_t*)slot_mapping, num_kv_heads, head_dim,
+                       block_size, kv_stride);
+  });
+}
 
 extern "C" void arks_splitk_rope_and_cache(
     const void* positions, const void* part, const void* bias, void* q_out,
@@ -364,21 +247,14 @@ extern "C" void arks_splitk_rope_and_cache(
   dim3 grid(num_tokens), block(std::min(1024, (items + 63) / 64 * 64));
   const int64_t split_stride =
       (int64_t)mrows_pad * (num_q_heads + 2 * num_kv_heads) * head_dim;
-  if (kv_fp8) {
-    hipLaunchKernelGGL((splitk_rope_cache_kernel<true>), grid, block, 0, stream,
-                       (const int64_t*)positions, (const float*)part,
-                       (const bf16*)bias, (bf16*)q_out, k_cache, v_cache,
-                       (const int64_t*)slot_mapping, (const float*)cos_sin,
-                       head_dim, num_q_heads, num_kv_heads, block_size,
-                       nsplits, split_stride);
-  } else {
-    hipLaunchKernelGGL((splitk_rope_cache_kernel<false>), grid, block, 0,
-                       stream, (const int64_t*)positions, (const float*)part,
-                       (const bf16*)bias, (bf16*)q_out, k_cache, v_cache,
-                       (const int64_t*)slot_mapping, (const float*)cos_sin,
-                       head_dim, num_q_heads, num_kv_heads, block_size,
-                       nsplits, split_stride);
-  }
+  dispatch_kv_fp8(kv_fp8, [&](auto fp8) {
+    hipLaunchKernelGGL((splitk_rope_cache_kernel<decltype(fp8)::value>), grid,
+                       block, 0, stream, (const int64_t*)positions,
+                       (const float*)part, (const bf16*)bias, (bf16*)q_out,
+                       k_cache, v_cache, (const int64_t*)slot_mapping,
+                       (const float*)cos_sin, head_dim, num_q_heads,
+                       num_kv_heads, block_size, nsplits, split_stride);
+  });
 }
 
 extern "C" void arks_rope_and_cache(
@@ -389,19 +265,12 @@ extern "C" void arks_rope_and_cache(
     hipStream_t stream) {
   if (num_tokens == 0) return;
   dim3 grid(num_tokens), block(256);
-  if (kv_fp8) {
-    hipLaunchKernelGGL((rope_cache_kernel<true>), grid, block, 0, stream,
-                       (const int64_t*)positions, (bf16*)q, (bf16*)k,
-                       (const bf16*)v, k_cache, v_cache,
+  dispatch_kv_fp8(kv_fp8, [&](auto fp8) {
+    hipLaunchKernelGGL((rope_cache_kernel<decltype(fp8)::value>), grid, block,
+                       0, stream, (const int64_t*)positions, (bf16*)q,
+                       (bf16*)k, (const bf16*)v, k_cache, v_cache,
                        (const int64_t*)slot_mapping, (const float*)cos_sin,
                        head_dim, num_q_heads, num_kv_heads, block_size,
                        q_stride, k_stride);
-  } else {
-    hipLaunchKernelGGL((rope_cache_kernel<false>), grid, block, 0, stream,
-                       (const int64_t*)positions, (bf16*)q, (bf16*)k,
-                       (const bf16*)v, k_cache, v_cache,
-                       (const int64_t*)slot_mapping, (const float*)cos_sin,
-                       head_dim, num_q_heads, num_kv_heads, block_size,
-                       q_stride, k_stride);
-  }
+  });
 }

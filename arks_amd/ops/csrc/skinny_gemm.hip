@@ -29,12 +29,14 @@
 //   splitk_reduce (common.h); skinny_combine_kernel is the fallback that
 //   materialises a bf16 [M, N].
 //
-//   FUSE_SILU: A is the raw gate_up projection output [M, 2K] (gate in
-//   cols [0,K), up in [K,2K), reference vLLM SiluAndMul layout); the LDS
-//   staging step computes silu(gate)*up on the fly, bf16-rounded with the
-//   same formula as silu_mul_kernel (elementwise.hip:89) so the fused
-//   down-proj is bit-identical to silu_mul + skinny_gemm. This removes the
-//   silu_mul kernel and its intermediate tensor from every decode layer.
+// The file builds seven kernels: skinny_gemm_kernel<MT, 128, 1> for MT 1..4
+// (AB=2 ring; launch config 0, MT from M), the tall-K kernel
+// <4, 128, 2, AB=3> for the down-proj shape (config 1), the same with
+// non-temporal W loads (config 2), and skinny_combine_kernel. The
+// experiments that lost to these — global-direct A reads, wave-private
+// barrier-free staging, silu_mul fused into the A staging, other (KC, PF)
+// pairs — are recorded with their numbers in profiles/r02_final.md; the MLP
+// runs silu_mul_kernel (elementwise.hip) ahead of the down-proj.
 //
 // N must be a multiple of 64 and K of 32 (true for every Qwen/Llama shape;
 // the Python wrapper falls back to hipBLASLt otherwise).
@@ -73,10 +75,10 @@ __device__ __forceinline__ void store_partials(float* __restrict__ part,
 // MT = number of 16-row M tiles (M <= 16*MT, MT in 1..4).
 // KC = K elements per staged chunk (ping-pong pair in LDS).
 // PF = W register-prefetch distance in chunks (in-flight W = PF*KC*2 B/row).
-// FUSE_SILU: see header comment.
+// AB = depth of the A ring in LDS (chunks staged AB-1 ahead).
 // NT: non-temporal W loads (W is streamed exactly once; keeps it out of
 // the LLC so KV/activation lines survive across decode steps).
-template <int MT, int KC, int PF, bool FUSE_SILU, int AB = 2, bool NT = false>
+template <int MT, int KC, int PF, int AB = 2, bool NT = false>
 __global__ __launch_bounds__(256) void skinny_gemm_kernel(
     float* __restrict__ part,   // [nsplits, 16*MT, N] (nsplits > 1)
     bf16* __restrict__ out,     // [M, N] (nsplits == 1)
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
   auto stage_a = [&](int kc, int buf) {
     constexpr int CPT = KC / 8;  // 16 B column-groups per row
     constexpr int NIT = MROWS * CPT / 256;
-    ushort8 gv[NIT], uv[NIT];
+    ushort8 gv[NIT];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int i = tid + it * 256;
@@ -134,8 +136,6 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
       const int kcol = min(kc + (i % CPT) * 8, k_total - 8);
       const bf16* base = a + (int64_t)row * a_stride + kcol;
       gv[it] = *reinterpret_cast<const ushort8*>(base);
-      if constexpr (FUSE_SILU)
-        uv[it] = *reinterpret_cast<const ushort8*>(base + k_total);
     }
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -143,14 +143,6 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
       const int row = i / CPT;
       const int col8 = (i % CPT) * 8;
       ushort8 v = gv[it];
-      if constexpr (FUSE_SILU) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float x = bf16_bits_to_float(gv[it][j]);
-          float silu = x / (1.f + __expf(-x));
-          v[j] = float_to_bf16_bits(silu * bf16_bits_to_float(uv[it][j]));
-        }
-      }
       *reinterpret_cast<ushort8*>(&lds.a_buf[buf][row][col8]) = v;
     }
   };
@@ -248,220 +240,6 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
   }
 }
 
-// Wave-private variant — MEASURED LOSER, kept for the record (bench_down
-// r2: 1.1 TB/s): each wave stages its OWN copy of the A chunk into its own
-// LDS slice so there are no cross-wave barriers, but the 4x A reads and 4x
-// staging instructions per W byte cost far more than the barriers did.
-template <int MT, bool FUSE_SILU>
-__global__ __launch_bounds__(256) void skinny_gemm_wave_kernel(
-    float* __restrict__ part, bf16* __restrict__ out,
-    const bf16* __restrict__ a, const bf16* __restrict__ w,
-    const bf16* __restrict__ bias, const int m_rows, const int n_total,
-    const int k_total, const int k_per_split, const int nsplits,
-    const int64_t a_stride) {
-  constexpr int MROWS = 16 * MT;
-  constexpr int KC2 = 64;
-  constexpr int KS2 = KC2 / 32;  // k32 steps per chunk
-  const int n0 = blockIdx.x * SK_NT;
-  const int kb = blockIdx.y * k_per_split;
-  const int ke = min(k_total, kb + k_per_split);
-
-  const int tid = threadIdx.x;
-  const int wave = tid / WAVE_SIZE;
-  const int lane = tid % WAVE_SIZE;
-  const int lq = lane % 16;
-  const int la = lane / 16;
-
-  __shared__ __attribute__((aligned(16))) union {
-    bf16 a_buf[4][2][64][KC2 + SK_AP];
-    float c_buf[SK_NT][64 + 1];
-  } lds;
-
-  f32x4 acc[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
-
-  const bf16* wrow = w + (int64_t)(n0 + wave * 16 + lq) * k_total + 8 * la;
-
-  // Per-wave A staging: 64 lanes cover 64 rows x KC2/8 col-groups.
-  auto stage_a = [&](int kc, int buf) {
-    const int kw = min(KC2, ke - kc);
-    constexpr int CPT = KC2 / 8;
-#pragma unroll
-    for (int it = 0; it < MROWS * CPT / WAVE_SIZE; ++it) {
-      const int i = lane + it * WAVE_SIZE;
-      const int row = i / CPT;
-      const int col8 = (i % CPT) * 8;
-      if (col8 >= kw) continue;
-      ushort8 v{};
-      if (row < m_rows) {
-        const bf16* base = a + (int64_t)row * a_stride + kc + col8;
-        if constexpr (FUSE_SILU) {
-          ushort8 gv = *reinterpret_cast<const ushort8*>(base);
-          ushort8 uv = *reinterpret_cast<const ushort8*>(base + k_total);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float x = bf16_bits_to_float(gv[j]);
-            float silu = x / (1.f + __expf(-x));
-            v[j] = float_to_bf16_bits(silu * bf16_bits_to_float(uv[j]));
-          }
-        } else {
-          v = *reinterpret_cast<const ushort8*>(base);
-        }
-      }
-      *reinterpret_cast<ushort8*>(&lds.a_buf[wave][buf][row][col8]) = v;
-    }
-  };
-
-  ushort8 wreg[2][KS2];
-  auto load_w = [&](int kc, ushort8 (&dst)[KS2]) {
-#pragma unroll
-    for (int s = 0; s < KS2; ++s)
-      dst[s] = (kc + s * 32 < ke)
-                   ? *reinterpret_cast<const ushort8*>(wrow + kc + s * 32)
-                   : ushort8{};
-  };
-
-  stage_a(kb, 0);
-  load_w(kb, wreg[0]);
-  if (kb + KC2 < ke) load_w(kb + KC2, wreg[1]);
-
-  int buf = 0;
-  for (int kc = kb; kc < ke; kc += KC2, buf ^= 1) {
-    const int kw = min(KC2, ke - kc);
-    const int kn = kc + KC2;
-    if (kn < ke) stage_a(kn, buf ^ 1);
-    ushort8 wnext[KS2];
-    if (kn + KC2 < ke) load_w(kn + KC2, wnext);
-    else {
-#pragma unroll
-      for (int s = 0; s < KS2; ++s) wnext[s] = ushort8{};
-    }
-#pragma unroll
-    for (int s = 0; s < KS2; ++s) {
-      if (s * 32 >= kw) break;
-      bf16x8 wfrag = *reinterpret_cast<bf16x8*>(&wreg[0][s]);
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        ushort8 af = *reinterpret_cast<const ushort8*>(
-            &lds.a_buf[wave][buf][t * 16 + lq][s * 32 + 8 * la]);
-        acc[t] = sk_mfma(wfrag, *reinterpret_cast<bf16x8*>(&af), acc[t]);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < KS2; ++s) wreg[0][s] = wreg[1][s];
-#pragma unroll
-    for (int s = 0; s < KS2; ++s) wreg[1][s] = wnext[s];
-    // no barrier: a_buf slice is wave-private; the wave's own lgkmcnt/vmcnt
-    // ordering is sufficient
-  }
-
-  if (nsplits > 1) {
-    store_partials<MT>(part, acc, n_total, n0 + wave * 16 + 4 * la, lq);
-    return;
-  }
-
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      lds.c_buf[wave * 16 + 4 * la + r][t * 16 + lq] = acc[t][r];
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < m_rows * SK_NT; i += 256) {
-    const int m = i / SK_NT;
-    const int n = i % SK_NT;
-    float v = lds.c_buf[n][m];
-    if (bias != nullptr) v += bf16_bits_to_float(bias[n0 + n]);
-    out[(int64_t)m * n_total + n0 + n] = float_to_bf16_bits(v);
-  }
-}
-
-// Direct (barrier-free) variant — MEASURED LOSER, kept for the record
-// (bench_down r2: 1.5 TB/s vs 3.9 staged): both W and A stream straight
-// from global. The dependent A loads share the vmcnt counter with W and
-// quadruple the per-wave load count, swamping the issue stream; the
-// raw-read probe (scripts/bench_membw.hip) only shows 6.7 TB/s for the
-// W pattern when it is the ONLY load stream.
-// Rows >= m_rows are clamped to the last valid row (duplicate finite reads;
-// their C columns are discarded by the epilogue/partial consumer).
-template <int MT, bool FUSE_SILU>
-__global__ __launch_bounds__(256) void skinny_gemm_direct_kernel(
-    float* __restrict__ part, bf16* __restrict__ out,
-    const bf16* __restrict__ a, const bf16* __restrict__ w,
-    const bf16* __restrict__ bias, const int m_rows, const int n_total,
-    const int k_total, const int k_per_split, const int nsplits,
-    const int64_t a_stride) {
-  constexpr int MROWS = 16 * MT;
-  const int n0 = blockIdx.x * SK_NT;
-  const int kb = blockIdx.y * k_per_split;
-  const int ke = min(k_total, kb + k_per_split);
-
-  const int tid = threadIdx.x;
-  const int wave = tid / WAVE_SIZE;
-  const int lane = tid % WAVE_SIZE;
-  const int lq = lane % 16;
-  const int la = lane / 16;
-
-  f32x4 acc[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
-
-  const bf16* wrow = w + (int64_t)(n0 + wave * 16 + lq) * k_total + 8 * la;
-  const bf16* arow[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-    arow[t] = a + (int64_t)min(t * 16 + lq, m_rows - 1) * a_stride + 8 * la;
-
-#pragma unroll 4
-  for (int k = kb; k < ke; k += 32) {
-    bf16x8 wfrag = *reinterpret_cast<const bf16x8*>(wrow + k);
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      bf16x8 af;
-      if constexpr (FUSE_SILU) {
-        ushort8 gv = *reinterpret_cast<const ushort8*>(arow[t] + k);
-        ushort8 uv = *reinterpret_cast<const ushort8*>(arow[t] + k_total + k);
-        ushort8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float x = bf16_bits_to_float(gv[j]);
-          float silu = x / (1.f + __expf(-x));
-          v[j] = float_to_bf16_bits(silu * bf16_bits_to_float(uv[j]));
-        }
-        af = *reinterpret_cast<bf16x8*>(&v);
-      } else {
-        af = *reinterpret_cast<const bf16x8*>(arow[t] + k);
-      }
-      acc[t] = sk_mfma(wfrag, af, acc[t]);
-    }
-  }
-
-  if (nsplits > 1) {
-    store_partials<MT>(part, acc, n_total, n0 + wave * 16 + 4 * la, lq);
-    return;
-  }
-
-  __shared__ float c_lds[SK_NT][64 + 1];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      c_lds[wave * 16 + 4 * la + r][t * 16 + lq] = acc[t][r];
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < m_rows * SK_NT; i += 256) {
-    const int m = i / SK_NT;
-    const int n = i % SK_NT;
-    float v = c_lds[n][m];
-    if (bias != nullptr) v += bf16_bits_to_float(bias[n0 + n]);
-    out[(int64_t)m * n_total + n0 + n] = float_to_bf16_bits(v);
-  }
-}
-
 // Reduce the split partials: out[m][n] = bf16(sum_s part[s][m][n] + bias[n]).
 // Partials and output share the [m][n] orientation, so this is elementwise:
 // each thread owns four consecutive n of one row (16 B loads per split, all
@@ -506,89 +284,47 @@ extern "C" void arks_skinny_combine(void* out, const void* part,
                      n_total, nsplits, (int64_t)mrows_pad * n_total);
 }
 
+// M tiles of the kernel that `config` launches for m_rows rows: the default
+// ring (config 0) takes MT from M, the tall-K kernels (1, 2) are built for
+// MT = 4 only.
+static int skinny_mt(int m_rows, int config) {
+  return config == 0 ? std::min((m_rows + 15) / 16, 4) : 4;
+}
+
+// Rows per split slab of the partials that arks_skinny_gemm writes.
+extern "C" int arks_skinny_slab_rows(int m_rows, int config) {
+  return 16 * skinny_mt(m_rows, config);
+}
+
+// config 0: default AB=2 ring, MT from M; 1: tall-K (PF=2, AB=3, MT=4);
+// 2: tall-K with non-temporal W loads.
 // combine = false (nsplits > 1 only) stops after the GEMM: the f32 partials
 // stay in `part` for a consumer kernel that reduces them itself.
 extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
                                  const void* w, const void* bias, int m_rows,
                                  int n_total, int k_total, int k_per_split,
-                                 int nsplits, int64_t a_stride, bool combine,
-                                 hipStream_t stream) {
-  const int mt = std::min((m_rows + 15) / 16, 4);
+                                 int nsplits, int64_t a_stride, int config,
+                                 bool combine, hipStream_t stream) {
   dim3 grid(n_total / SK_NT, nsplits), block(256);
-#define SK_LAUNCH(MT)                                                         \
-  hipLaunchKernelGGL((skinny_gemm_kernel<MT, 128, 1, false>), grid, block, 0, \
-                     stream, (float*)part, (bf16*)out, (const bf16*)a,        \
-                     (const bf16*)w, (const bf16*)bias, m_rows, n_total,      \
-                     k_total, k_per_split, nsplits, a_stride)
-  switch (mt) {
-    case 1: SK_LAUNCH(1); break;
-    case 2: SK_LAUNCH(2); break;
-    case 3: SK_LAUNCH(3); break;
-    default: SK_LAUNCH(4); break;
-  }
-#undef SK_LAUNCH
-  if (nsplits > 1 && combine)
-    arks_skinny_combine(out, part, bias, m_rows, n_total, nsplits, 16 * mt,
-                        stream);
-}
-
-// Variant entry for the big streaming decode shapes (down-proj), MT=4 only:
-// variant selects (KC, PF); fuse_silu selects the fused SwiGLU staging (A is
-// then the [M, 2K] gate_up output; a_stride is its row stride).
-extern "C" void arks_skinny_gemm_v(void* part, void* out, const void* a,
-                                   const void* w, const void* bias,
-                                   int m_rows, int n_total, int k_total,
-                                   int k_per_split, int nsplits,
-                                   int64_t a_stride, int variant,
-                                   bool fuse_silu, bool combine,
-                                   hipStream_t stream) {
-  dim3 grid(n_total / SK_NT, nsplits), block(256);
-#define SK_LAUNCH_V(KC, PF, FS)                                               \
-  hipLaunchKernelGGL((skinny_gemm_kernel<4, KC, PF, FS>), grid, block, 0,     \
-                     stream, (float*)part, (bf16*)out, (const bf16*)a,        \
-                     (const bf16*)w, (const bf16*)bias, m_rows, n_total,      \
-                     k_total, k_per_split, nsplits, a_stride)
-#define SK_SWITCH(FS)                                                         \
-  switch (variant) {                                                          \
-    case 1: SK_LAUNCH_V(128, 2, FS); break;                                   \
-    case 2: SK_LAUNCH_V(128, 3, FS); break;                                   \
-    case 3: SK_LAUNCH_V(256, 1, FS); break;                                   \
-    case 4: SK_LAUNCH_V(256, 2, FS); break;                                   \
-    case 5:                                                                   \
-      hipLaunchKernelGGL((skinny_gemm_direct_kernel<4, FS>), grid, block, 0,  \
-                         stream, (float*)part, (bf16*)out, (const bf16*)a,    \
-                         (const bf16*)w, (const bf16*)bias, m_rows, n_total,  \
-                         k_total, k_per_split, nsplits, a_stride);            \
-      break;                                                                  \
-    case 6:                                                                   \
-      hipLaunchKernelGGL((skinny_gemm_wave_kernel<4, FS>), grid, block, 0,    \
-                         stream, (float*)part, (bf16*)out, (const bf16*)a,    \
-                         (const bf16*)w, (const bf16*)bias, m_rows, n_total,  \
-                         k_total, k_per_split, nsplits, a_stride);            \
-      break;                                                                  \
-    case 8:                                                                   \
-      hipLaunchKernelGGL((skinny_gemm_kernel<4, 128, 2, FS, 3, true>), grid,  \
-                         block, 0, stream, (float*)part, (bf16*)out,          \
-                         (const bf16*)a, (const bf16*)w, (const bf16*)bias,   \
-                         m_rows, n_total, k_total, k_per_split, nsplits,      \
-                         a_stride);                                           \
-      break;                                                                  \
-    case 7:                                                                   \
-      hipLaunchKernelGGL((skinny_gemm_kernel<4, 128, 2, FS, 3>), grid,        \
-                         block, 0, stream, (float*)part, (bf16*)out,          \
-                         (const bf16*)a, (const bf16*)w, (const bf16*)bias,   \
-                         m_rows, n_total, k_total, k_per_split, nsplits,      \
-                         a_stride);                                           \
-      break;                                                                  \
-    default: SK_LAUNCH_V(128, 1, FS); break;                                  \
-  }
-  if (fuse_silu) {
-    SK_SWITCH(true)
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, (float*)part,
+                       (bf16*)out, (const bf16*)a, (const bf16*)w,
+                       (const bf16*)bias, m_rows, n_total, k_total,
+                       k_per_split, nsplits, a_stride);
+  };
+  if (config == 2) {
+    launch(skinny_gemm_kernel<4, 128, 2, 3, true>);
+  } else if (config == 1) {
+    launch(skinny_gemm_kernel<4, 128, 2, 3>);
   } else {
-    SK_SWITCH(false)
+    switch (skinny_mt(m_rows, config)) {
+      case 1: launch(skinny_gemm_kernel<1, 128, 1>); break;
+      case 2: launch(skinny_gemm_kernel<2, 128, 1>); break;
+      case 3: launch(skinny_gemm_kernel<3, 128, 1>); break;
+      default: launch(skinny_gemm_kernel<4, 128, 1>); break;
+    }
   }
-#undef SK_SWITCH
-#undef SK_LAUNCH_V
   if (nsplits > 1 && combine)
-    arks_skinny_combine(out, part, bias, m_rows, n_total, nsplits, 64, stream);
+    arks_skinny_combine(out, part, bias, m_rows, n_total, nsplits,
+                        arks_skinny_slab_rows(m_rows, config), stream);
 }

@@ -48,53 +48,24 @@ def main():
     # force the skinny kernel regardless of the dispatch threshold
     import arks_amd.ops as O
     native = O._native()
-    vnames = {0: "kc128/pf1", 1: "kc128/pf2", 2: "kc128/pf3",
-              3: "kc256/pf1", 4: "kc256/pf2", 5: "direct   ", 6: "wavepriv ", 7: "kc128/ab3"}
-    for variant in (0, 6, 7):
+    # launch configs of skinny_gemm.hip (at M=64 all three write 64-row slabs)
+    cnames = {0: "kc128/pf1/ab2", 1: "kc128/pf2/ab3", 2: "  same + nt  "}
+    for config in (0, 1, 2):
         for nsplits in (8, 16, 24, 32):
             k_per_split = -(-(-(-K // nsplits)) // 32) * 32
             nsp = -(-K // k_per_split)
             out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-            part = (O._skinny_ws(nsp, N, M, x.device) if nsp > 1
+            part = (O._skinny_ws(nsp, N, 64, x.device) if nsp > 1
                     else x.new_empty(0, dtype=torch.float32))
 
             def run():
-                native.skinny_gemm_v(out, part, x, w, None, k_per_split,
-                                     nsp, variant, False)
+                native.skinny_gemm(out, part, x, w, None, k_per_split, nsp,
+                                   config)
 
             run()
             err = (out.float() - ref.float()).abs().max().item()
             us = timeit(run)
-            print(f"skinny {vnames[variant]} ns={nsp:3d}: {us:7.1f} us  "
-                  f"{nbytes / us / 1e6:5.2f} TB/s  maxerr={err:.3e}")
-
-    # fused silu_mul + down-proj vs the two-kernel sequence
-    gu = torch.randn(M, 2 * K, dtype=torch.bfloat16, device=dev)
-    act = torch.empty(M, K, dtype=torch.bfloat16, device=dev)
-    native.silu_mul(act, gu)
-    fref = F.linear(act, w)
-
-    def two_kernel():
-        native.silu_mul(act, gu)
-        return F.linear(act, w)
-
-    us = timeit(two_kernel)
-    print(f"silu_mul + hipBLASLt : {us:7.1f} us  (sequence)")
-    for variant in (0, 6, 7):
-        for nsplits in (8, 16, 24, 32):
-            k_per_split = -(-(-(-K // nsplits)) // 32) * 32
-            nsp = -(-K // k_per_split)
-            out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-            part = O._skinny_ws(nsp, N, M, x.device)
-
-            def runf():
-                native.skinny_gemm_v(out, part, gu, w, None, k_per_split,
-                                     nsp, variant, True)
-
-            runf()
-            err = (out.float() - fref.float()).abs().max().item()
-            us = timeit(runf)
-            print(f"fused  {vnames[variant]} ns={nsp:3d}: {us:7.1f} us  "
+            print(f"skinny {cnames[config]} ns={nsp:3d}: {us:7.1f} us  "
                   f"{nbytes / us / 1e6:5.2f} TB/s  maxerr={err:.3e}")
 
 

@@ -17,12 +17,12 @@ for name, K, N in (("qkv", 3584, 4608), ("o", 3584, 3584)):
     us0 = timeit(lambda: O.skinny_gemm(x, w))
     nb = w.numel() * 2
     print(f"{name}: dispatch {us0:6.1f} us {nb/us0/1e6:.2f} TB/s")
-    for variant in (0, 7):
+    for config in (0, 1):  # default ring, tall-K kernel
         for ns in (8, 12, 16):
             kps = -(-(-(-K // ns)) // 32) * 32
             nsp = -(-K // kps)
             out = torch.empty(64, N, dtype=torch.bfloat16, device="cuda")
             part = O._skinny_ws(nsp, N, 64, x.device)
-            f = lambda: native.skinny_gemm_v(out, part, x, w, None, kps, nsp, variant, False)
+            f = lambda: native.skinny_gemm(out, part, x, w, None, kps, nsp, config)
             us = timeit(f)
-            print(f"{name}: v{variant} ns={nsp:2d} {us:6.1f} us {nb/us/1e6:.2f} TB/s")
+            print(f"{name}: config {config} ns={nsp:2d} {us:6.1f} us {nb/us/1e6:.2f} TB/s")

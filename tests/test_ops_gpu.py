@@ -88,6 +88,33 @@ def test_reshape_and_cache():
     torch.testing.assert_close(kc.cpu(), kc_ref)
     torch.testing.assert_close(vc.cpu(), vc_ref)
 
+    # a padding row (slot -1 writes nothing anywhere), bf16 and fp8 caches
+    T, hkv, hd, nb = 5, 2, 64, 4
+    k = torch.randn(T, hkv, hd, dtype=torch.bfloat16, device=DEV)
+    v = torch.randn(T, hkv, hd, dtype=torch.bfloat16, device=DEV)
+    slots = torch.tensor([17, 3, -1, 63, 32], dtype=torch.int64, device=DEV)
+    keep = (slots >= 0).cpu()
+    kc_ref = torch.zeros(nb, hkv, bs, hd, dtype=torch.float32)
+    vc_ref = torch.zeros_like(kc_ref)
+    ref.reshape_and_cache(k.float().cpu()[keep], v.float().cpu()[keep],
+                          kc_ref, vc_ref, slots.cpu()[keep])
+    assert kc_ref.count_nonzero() >= 4 * hkv * hd - 8
+    for dt in (torch.bfloat16, torch.float8_e4m3fn):
+        kc = torch.zeros(nb, hkv, bs, hd, dtype=dt, device=DEV)
+        vc = torch.zeros_like(kc)
+        ops.reshape_and_cache(k, v, kc, vc, slots)
+        for got, want in ((kc, kc_ref), (vc, vc_ref)):
+            err = (got.float().cpu() - want).abs()
+            if dt == torch.bfloat16:
+                assert err.max() == 0  # a copy
+            else:
+                # correctly rounded to e4m3 whichever way ties go: within
+                # half an ulp, 2^(e-3) for |x| in [2^e, 2^(e+1)), e >= -6
+                # (subnormals below); untouched bytes (want == 0) stay 0
+                e = torch.frexp(want)[1] - 1
+                half_ulp = 0.5 * torch.exp2((e.clamp(min=-6) - 3).float())
+                assert (err <= half_ulp * (want != 0)).all()
+
 
 def test_mfma_probe():
     """Verify the MFMA fragment-layout hypothesis vs torch.matmul.
@@ -640,32 +667,68 @@ def test_one_shot_allreduce_single_device():
 @pytest.mark.parametrize("fp8", [False, True])
 def test_rope_and_cache_fused_matches_two_step(fp8):
     """Fused RoPE+cache kernel vs the separate rope + reshape_and_cache
-    pair, including padded rows (slot -1: rotate but skip the cache)."""
+    pair, including padded rows (slot -1: rotate but skip the cache). Both
+    rotate through rope_rotate and store through cache_store, so the results
+    are the same bits. The last case is the Qwen2.5-7B batch-64 decode shape:
+    a differently contracted fma shows about once in 1e5 elements, and this
+    one rotates 262k."""
     assert_native()
     torch.manual_seed(21)
-    T, hq, hkv, hd, bs = 9, 8, 2, 128, 16
-    nblocks = 8
+    bs = 16
     dt = torch.float8_e4m3fn if fp8 else torch.bfloat16
-    qkv = torch.randn(T, (hq + 2 * hkv) * hd, dtype=torch.bfloat16, device=DEV)
-    q = qkv[:, : hq * hd]
-    k = qkv[:, hq * hd: (hq + hkv) * hd]
-    v = qkv[:, (hq + hkv) * hd:]
-    q2, k2, v2 = q.clone().contiguous(), k.clone().contiguous(), v.clone().contiguous()
-    cos_sin = ref.rope_cos_sin_cache(hd, 64, 10000.0).cuda()
-    pos = torch.randint(0, 64, (T,), dtype=torch.int64, device=DEV)
-    slots = torch.tensor([i * 3 if i != 4 else -1 for i in range(T)],
-                         dtype=torch.int64, device=DEV)
-    kc_a = torch.zeros(nblocks, hkv, bs, hd, dtype=dt, device=DEV)
-    vc_a = torch.zeros_like(kc_a)
-    kc_b = torch.zeros_like(kc_a)
-    vc_b = torch.zeros_like(kc_a)
-    # fused
-    ops.rope_and_cache(pos, q, k, v, kc_a, vc_a, slots, cos_sin, hd)
-    # two-step
-    ops.rope_apply_inplace(pos, q2, k2, cos_sin, hd)
-    ops.reshape_and_cache(k2.view(T, hkv, hd), v2.view(T, hkv, hd),
-                          kc_b, vc_b, slots)
-    torch.testing.assert_close(q, q2, atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(k, k2, atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(kc_a.float(), kc_b.float(), atol=3e-2, rtol=3e-2)
-    torch.testing.assert_close(vc_a.float(), vc_b.float(), atol=3e-2, rtol=3e-2)
+    for T, hq, hkv, hd, max_pos, base in [
+        (9, 8, 2, 128, 64, 10000.0),
+        (9, 2, 1, 64, 64, 10000.0),
+        (64, 28, 4, 128, 2048, 1000000.0),
+    ]:
+        nblocks = (3 * T + bs - 1) // bs  # slots are i * 3
+        qkv = torch.randn(T, (hq + 2 * hkv) * hd, dtype=torch.bfloat16,
+                          device=DEV)
+        q = qkv[:, : hq * hd]
+        k = qkv[:, hq * hd: (hq + hkv) * hd]
+        v = qkv[:, (hq + hkv) * hd:]
+        q2, k2, v2 = (t.clone().contiguous() for t in (q, k, v))
+        cos_sin = ref.rope_cos_sin_cache(hd, max_pos, base).cuda()
+        pos = torch.randint(0, max_pos, (T,), dtype=torch.int64, device=DEV)
+        slots = torch.tensor([i * 3 if i != 4 else -1 for i in range(T)],
+                             dtype=torch.int64, device=DEV)
+        kc_a = torch.zeros(nblocks, hkv, bs, hd, dtype=dt, device=DEV)
+        vc_a = torch.zeros_like(kc_a)
+        kc_b = torch.zeros_like(kc_a)
+        vc_b = torch.zeros_like(kc_a)
+        # fused
+        ops.rope_and_cache(pos, q, k, v, kc_a, vc_a, slots, cos_sin, hd)
+        # two-step
+        ops.rope_apply_inplace(pos, q2, k2, cos_sin, hd)
+        ops.reshape_and_cache(k2.view(T, hkv, hd), v2.view(T, hkv, hd),
+                              kc_b, vc_b, slots)
+        assert torch.equal(q, q2)
+        assert torch.equal(k, k2)
+        assert torch.equal(kc_a.view(torch.uint8), kc_b.view(torch.uint8))
+        assert torch.equal(vc_a.view(torch.uint8), vc_b.view(torch.uint8))
+        assert kc_a.view(torch.uint8).any()
+        # slot 12 would have been row 4's: nothing was cached for it
+        assert not kc_a.view(torch.uint8)[0, :, 12].any()
+
+
+@pytest.mark.parametrize("with_bias", [False, True])
+def test_skinny_gemm_tall_k_configs_agree(monkeypatch, with_bias):
+    """The tall-K kernel and its non-temporal-load twin (launch configs 1 and
+    2, ARKS_SKINNY_TALLK_V=7 / 8): the load hint changes no arithmetic, so
+    the two results are the same bits."""
+    assert_native()
+    torch.manual_seed(29)
+    m, n, k = 64, 256, 1024
+    a = torch.randn(m, k, dtype=torch.bfloat16, device=DEV) * 0.5
+    w = torch.randn(n, k, dtype=torch.bfloat16, device=DEV) * 0.05
+    bias = (torch.randn(n, dtype=torch.bfloat16, device=DEV)
+            if with_bias else None)
+    outs = []
+    for config in (1, 2):
+        monkeypatch.setattr(ops, "_SKINNY_TALLK_CONFIG", config)
+        assert ops._skinny_plan(m, n, k) == (config, 4, 256, 64)
+        outs.append(ops.skinny_gemm(a, w, bias))
+    expect = torch.nn.functional.linear(a, w, bias).float()
+    for out in outs:
+        torch.testing.assert_close(out.float(), expect, atol=5e-2, rtol=5e-2)
+    assert torch.equal(outs[0], outs[1])
