@@ -49,6 +49,9 @@ class ModelConfig:
     eos_token_id: int = 151645
     bos_token_id: int = 151643
     torch_dtype: str = "bfloat16"
+    # "awq" when the checkpoint's quantization_config declares 4-bit AWQ
+    # (the only on-disk quantization read); None for plain checkpoints
+    quant_method: str | None = None
 
     def __post_init__(self):
         # Sliding-window attention is implemented end to end: the
@@ -87,6 +90,27 @@ class ModelConfig:
         full-attention layer keeps the whole history live."""
         ws = [self.layer_window(i) for i in range(self.num_hidden_layers)]
         return ws[0] if ws and all(w == ws[0] and w > 0 for w in ws) else 0
+
+    @staticmethod
+    def _check_quantization_config(qc: dict | None) -> str | None:
+        """Accepts exactly AutoAWQ 4-bit, group 128, zero-point, "GEMM"
+        layout; anything else raises naming the offending field."""
+        if not qc:
+            return None
+        want = {"quant_method": "awq", "bits": 4, "group_size": 128,
+                "zero_point": True, "version": "gemm"}
+        for field, ok in want.items():
+            got = qc.get(field)
+            if isinstance(got, str):
+                got = got.lower()
+            if got != ok or (field == "zero_point" and got is not True):
+                raise ValueError(
+                    f"unsupported quantization_config: {field}="
+                    f"{qc.get(field)!r} (only {field}={ok!r} is supported; "
+                    "the engine reads 4-bit AWQ, group size 128, with "
+                    "zero-points, GEMM layout)"
+                )
+        return "awq"
 
     @classmethod
     def from_hf_config(cls, cfg: dict) -> "ModelConfig":
@@ -133,6 +157,8 @@ class ModelConfig:
             eos_token_id=eos,
             bos_token_id=cfg.get("bos_token_id", 1),
             torch_dtype=cfg.get("torch_dtype", "bfloat16"),
+            quant_method=cls._check_quantization_config(
+                cfg.get("quantization_config")),
         )
 
     @classmethod
@@ -450,6 +476,10 @@ class EngineConfig:
     enable_mixed_batching: bool = True
     # None | "fp8": W8A8 OCP-e4m3 for qkv/gate_up/down/lm_head GEMMs
     # (dynamic per-token activation scales; o_proj and KV stay bf16)
+    # "int4": W4A16, round-to-nearest at load, group size 128, for the dense
+    # qkv/o/gate_up/down GEMMs (lm_head, embeddings, MoE experts stay bf16)
+    # "awq": a 4-bit AWQ checkpoint (auto-detected from its config.json;
+    # giving it for any other checkpoint is an error)
     quantization: str | None = None
     # "auto" (bf16) | "fp8": e4m3 KV pages (halves the decode KV stream;
     # scale 1.0, opt-in like vLLM's --kv-cache-dtype fp8)
@@ -476,6 +506,11 @@ class EngineConfig:
     lora_modules: dict[str, str] | None = None
 
     def __post_init__(self):
+        if self.quantization not in (None, "fp8", "int4", "awq"):
+            raise ValueError(
+                f"unknown quantization {self.quantization!r}: expected "
+                "None, 'fp8', 'int4' or 'awq'"
+            )
         if not self.enable_lora:
             if self.lora_modules:
                 raise ValueError("lora_modules given without enable_lora")
@@ -506,6 +541,25 @@ class EngineConfig:
             raise ValueError(
                 f"{len(mods)} lora_modules exceed max_loras={self.max_loras}"
             )
+
+    def resolve_quantization(self, model_cfg: ModelConfig) -> str | None:
+        """The mode the engine runs: an AWQ checkpoint selects "awq" on its
+        own and excludes every other mode; "awq" needs such a checkpoint."""
+        if model_cfg.quant_method == "awq":
+            if self.quantization not in (None, "awq"):
+                raise ValueError(
+                    f"quantization={self.quantization!r} cannot be applied "
+                    "to an AWQ checkpoint: its weights are already 4-bit "
+                    "(leave quantization unset or give 'awq')"
+                )
+            return "awq"
+        if self.quantization == "awq":
+            raise ValueError(
+                "quantization='awq' needs an AWQ checkpoint, but the model's "
+                "config.json has no AWQ quantization_config (use 'int4' to "
+                "quantize a bf16 checkpoint at load)"
+            )
+        return self.quantization
 
     def model_config(self) -> ModelConfig:
         if self.model_path:

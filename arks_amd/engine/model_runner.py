@@ -36,6 +36,7 @@ class ModelRunner:
     def __init__(self, engine_cfg: EngineConfig, model_cfg: ModelConfig | None = None):
         self.cfg = engine_cfg
         self.model_cfg = model_cfg or engine_cfg.model_config()
+        self.quantization = engine_cfg.resolve_quantization(self.model_cfg)
         self.device = torch.device(
             engine_cfg.device if torch.cuda.is_available() or engine_cfg.device == "cpu"
             else "cpu"
@@ -86,6 +87,10 @@ class ModelRunner:
 
     # ---------------- initialization ----------------
     def load_weights(self) -> None:
+        if self.quantization == "awq":
+            # W4 storage first: the bf16 weights of the quantized layers are
+            # never allocated on the device
+            self.model.prepare_awq()
         if self.cfg.model_path:
             from ..loader.safetensors_loader import load_model_weights
 
@@ -95,10 +100,14 @@ class ModelRunner:
             self.model.to(self.device)
             self.model.random_init(self.cfg.seed)
         self.model.to(self.device)
-        if self.cfg.quantization == "fp8":
+        if self.quantization == "fp8":
             self.model.quantize_fp8()
-        elif self.cfg.quantization is not None:
-            raise ValueError(f"unknown quantization {self.cfg.quantization!r}")
+        elif self.quantization == "int4":
+            self.model.quantize_int4()
+        elif self.quantization == "awq":
+            self.model.finalize_w4()
+        elif self.quantization is not None:
+            raise ValueError(f"unknown quantization {self.quantization!r}")
         # serving past max_position_embeddings: the rope table must cover
         # every reachable position (OOB table reads fault on GPU)
         if hasattr(self.model, "extend_rope_table"):

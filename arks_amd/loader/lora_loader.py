@@ -49,15 +49,20 @@ def _fused_layers(layer) -> dict[str, tuple]:
     return out
 
 
+def _local_shape(mod) -> tuple[int, int]:
+    """(N, K) of a linear layer's local weight, W4-quantized or not."""
+    return mod.w4_shape if getattr(mod, "w4", False) else tuple(mod.weight.shape)
+
+
 def _slice_offsets(name: str, mod) -> tuple[int, ...]:
     if name == "qkv_proj":
         q = mod.nq_local * mod.head_dim
         kv = mod.nkv_local * mod.head_dim
         return (0, q, q + kv, q + 2 * kv)
     if name == "gate_up_proj":
-        n = mod.weight.shape[0]
+        n = _local_shape(mod)[0]
         return (0, n // 2, n)
-    return (0, mod.weight.shape[0])
+    return (0, _local_shape(mod)[0])
 
 
 def allocate_lora_slots(model, max_loras: int, max_rank: int, device,
@@ -72,7 +77,7 @@ def allocate_lora_slots(model, max_loras: int, max_rank: int, device,
     total = h_ws.numel() * 4
     for li, layer in enumerate(model.layers):
         for name, (mod, targets) in _fused_layers(layer).items():
-            N, K = mod.weight.shape
+            N, K = _local_shape(mod)
             offs = _slice_offsets(name, mod)
             if K % 32 != 0 or N % 16 != 0 or any(o % 16 for o in offs):
                 raise ValueError(

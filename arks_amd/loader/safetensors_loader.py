@@ -180,7 +180,8 @@ def _dangling_names(chunk) -> set:
     """Names whose fused-weight partner group is incomplete in `chunk`
     (q/k/v and gate/up must be applied together — a group split across a
     file or staging-buffer boundary must carry over, or its weights would
-    silently never load)."""
+    silently never load). Partners share the tensor's own suffix, so an AWQ
+    checkpoint's .qweight / .qzeros / .scales groups carry over alike."""
     names = set(chunk)
     out = set()
     for n in names:
@@ -192,7 +193,8 @@ def _dangling_names(chunk) -> set:
                 out.add(n)
         if "gate_proj" in n or "up_proj" in n:
             stem = n.rsplit(".", 2)[0]
-            if any(f"{stem}.{p}.weight" not in names
+            kind = n.rsplit(".", 1)[1]
+            if any(f"{stem}.{p}.{kind}" not in names
                    for p in ("gate_proj", "up_proj")):
                 out.add(n)
     return out
@@ -211,8 +213,9 @@ def _chunk_complete(chunk: dict[str, torch.Tensor]) -> bool:
                     return False
         if "gate_proj" in n or "up_proj" in n:
             stem = n.rsplit(".", 2)[0]
+            kind = n.rsplit(".", 1)[1]
             for p in ("gate_proj", "up_proj"):
-                if f"{stem}.{p}.weight" not in names:
+                if f"{stem}.{p}.{kind}" not in names:
                     return False
     return True
 
@@ -220,15 +223,70 @@ def _chunk_complete(chunk: dict[str, torch.Tensor]) -> bool:
 def save_random_checkpoint(cfg, out_dir: str, seed: int = 0) -> None:
     """Write a random-init HF-layout checkpoint (config.json + safetensors)
     for tests of the loading path (no network for real checkpoints)."""
-    from safetensors.torch import save_file
+    _write_checkpoint(cfg, out_dir, _random_hf_tensors(cfg, seed))
 
+
+_AWQ_CONFIG = {"quant_method": "awq", "bits": 4, "group_size": 128,
+               "zero_point": True, "version": "gemm"}
+
+
+def save_awq_checkpoint(cfg, out_dir: str, seed: int = 0,
+                        dequantized_dir: str | None = None,
+                        split_files: bool = False) -> None:
+    """Write a random-init checkpoint in the AutoAWQ "GEMM" layout: every
+    dense q/k/v/o/gate/up/down projection is quantized (ops.ref.w4_quantize)
+    and stored as .qweight/.qzeros/.scales (ops.ref.awq_pack); norms, biases,
+    embeddings and lm_head are f16 as AutoAWQ writes them. config.json
+    carries the quantization_config.
+    dequantized_dir: also write a plain bf16 checkpoint holding the
+    dequantized weights (the model an AWQ engine must reproduce).
+    split_files: two safetensors files, with gate_proj and up_proj tensors
+    in different files (exercises the loader's carry-over)."""
+    from ..ops import ref
+
+    if cfg.num_local_experts > 0:
+        raise ValueError("save_awq_checkpoint covers dense models only")
+    projs = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj",
+             "down_proj")
+    awq: dict[str, torch.Tensor] = {}
+    plain: dict[str, torch.Tensor] = {}
+    for name, t in _random_hf_tensors(cfg, seed).items():
+        stem, _, param = name.rpartition(".")
+        if param == "weight" and stem.rsplit(".", 1)[-1] in projs:
+            qzs = ref.w4_quantize(t)
+            qweight, qzeros, scales = ref.awq_pack(*qzs)
+            awq[f"{stem}.qweight"] = qweight
+            awq[f"{stem}.qzeros"] = qzeros
+            awq[f"{stem}.scales"] = scales
+            plain[name] = ref.w4_dequant(*qzs).to(torch.bfloat16)
+        else:
+            # bf16 -> f16 -> bf16 must round-trip for the two checkpoints to
+            # hold the same model: keep what f16 represents
+            t16 = t.to(torch.float16)
+            awq[name] = t16
+            plain[name] = t16.to(torch.bfloat16)
+    files = None
+    if split_files:
+        first = {n: t for n, t in awq.items() if ".up_proj." not in n}
+        second = {n: t for n, t in awq.items() if ".up_proj." in n}
+        files = {"model-00001-of-00002.safetensors": first,
+                 "model-00002-of-00002.safetensors": second}
+    _write_checkpoint(cfg, out_dir, awq, files=files,
+                      extra_config={"quantization_config": dict(_AWQ_CONFIG),
+                                    "torch_dtype": "float16"})
+    if dequantized_dir is not None:
+        _write_checkpoint(cfg, dequantized_dir, plain)
+
+
+def _random_hf_tensors(cfg, seed: int) -> dict[str, torch.Tensor]:
+    """HF-layout tensors of a random-init model (fused weights split back
+    apart)."""
     from ..models import create_model
     from ..parallel.comm import get_tp_world_size
 
     assert get_tp_world_size() == 1, "save from a TP=1 process"
     model = create_model(cfg)
     model.random_init(seed)
-    os.makedirs(out_dir, exist_ok=True)
     # Emit HF-layout names (split fused weights back apart).
     out: dict[str, torch.Tensor] = {
         "model.embed_tokens.weight": model.embed_tokens.weight.data,
@@ -298,8 +356,18 @@ def save_random_checkpoint(cfg, out_dir: str, seed: int = 0) -> None:
         out[f"{pre}.post_attention_layernorm.weight"] = (
             layer.post_attention_layernorm.weight.data
         )
-    save_file({k: v.contiguous() for k, v in out.items()},
-              os.path.join(out_dir, "model.safetensors"))
+    return out
+
+
+def _write_checkpoint(cfg, out_dir: str, tensors: dict[str, torch.Tensor],
+                      files: dict | None = None,
+                      extra_config: dict | None = None) -> None:
+    from safetensors.torch import save_file
+
+    os.makedirs(out_dir, exist_ok=True)
+    for fname, part in (files or {"model.safetensors": tensors}).items():
+        save_file({k: v.contiguous() for k, v in part.items()},
+                  os.path.join(out_dir, fname))
     hf_cfg = {
         "architectures": [cfg.architecture],
         "vocab_size": cfg.vocab_size,
@@ -318,5 +386,6 @@ def save_random_checkpoint(cfg, out_dir: str, seed: int = 0) -> None:
         "bos_token_id": cfg.bos_token_id,
         "torch_dtype": "bfloat16",
     }
+    hf_cfg.update(extra_config or {})
     with open(os.path.join(out_dir, "config.json"), "w") as f:
         json.dump(hf_cfg, f, indent=1)

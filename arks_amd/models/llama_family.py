@@ -28,6 +28,10 @@ from ..parallel.layers import (
 )
 
 
+# tensor suffixes of an AutoAWQ "GEMM" projection
+_AWQ_KINDS = ("qweight", "qzeros", "scales")
+
+
 class RMSNorm(nn.Module):
     fp8_out = False  # emit (fp8, scales) for a W8A8 consumer GEMM
 
@@ -462,6 +466,74 @@ class LlamaFamilyForCausalLM(nn.Module):
         quantize_module_fp8(self.lm_head)
         self.norm.fp8_out = True
 
+    def _w4_targets(self):
+        """(name, module) of the layers int4 / AWQ quantize: the dense
+        qkv/o/gate_up/down projections. lm_head and the embeddings stay bf16
+        (as in AWQ checkpoints), and so do MoE blocks."""
+        for i, layer in enumerate(self.layers):
+            yield f"layers.{i}.self_attn.qkv_proj", layer.self_attn.qkv_proj
+            yield f"layers.{i}.self_attn.o_proj", layer.self_attn.o_proj
+            if isinstance(layer.mlp, MoEMLP):
+                continue
+            yield f"layers.{i}.mlp.gate_up_proj", layer.mlp.gate_up_proj
+            yield f"layers.{i}.mlp.down_proj", layer.mlp.down_proj
+
+    def quantize_int4(self) -> None:
+        """W4A16 round-to-nearest (group 128) over a loaded bf16 model; the
+        activations stay bf16, so the norms and SwiGLU are unchanged."""
+        from ..parallel.layers import quantize_module_w4
+
+        for name, mod in self._w4_targets():
+            quantize_module_w4(mod, name)
+
+    def prepare_awq(self) -> None:
+        """Switch the quantized layers to (empty) W4 storage BEFORE an AWQ
+        checkpoint streams in, so their bf16 weights are never allocated on
+        the device; finalize_w4() completes the switch after loading."""
+        from ..parallel.layers import init_module_w4
+
+        if self.cfg.num_local_experts > 0:
+            raise ValueError(
+                f"AWQ checkpoints of MoE architectures are not supported "
+                f"({self.cfg.architecture}): int4 covers dense layers only"
+            )
+        for name, mod in self._w4_targets():
+            init_module_w4(mod, name)
+
+    def finalize_w4(self) -> None:
+        from ..parallel.layers import finalize_module_w4
+
+        for _, mod in self._w4_targets():
+            finalize_module_w4(mod)
+
+    def _load_awq(self, mod, name: str, kind: str, fulls, shard_parts) -> None:
+        """One AWQ tensor kind (qweight / qzeros / scales) of a projection,
+        or of the fused partners `fulls`: unpack on the host to row form
+        [N, K] or [N, K/128], shard with `shard_parts`, fuse along N and
+        store in the module's packed buffers. The three kinds are
+        independent, so they may arrive in different chunks."""
+        from ..ops import ref
+
+        if not getattr(mod, "w4", False):
+            raise ValueError(
+                f"{name}: AWQ tensor in the checkpoint but the model was not "
+                "prepared for AWQ (config.json lacks quantization_config?)"
+            )
+        rows = []
+        for t in fulls:
+            t = t.cpu()
+            if kind == "scales":
+                rows.append(t.t())
+            else:
+                rows.append(ref._unpack_nibbles(t).t())
+        fused = torch.cat([p for p in shard_parts(*rows)], dim=0).contiguous()
+        if kind == "qweight":
+            mod.w4_qweight.copy_(ref._pack_nibbles(fused))
+        elif kind == "qzeros":
+            mod.w4_zeros.copy_(fused.t().contiguous())
+        else:
+            mod.w4_scales.copy_(fused.t().contiguous().to(torch.float16))
+
     def _build_cos_sin(self, min_len: int | None = None):
         from ..ops import ref
 
@@ -555,6 +627,13 @@ class LlamaFamilyForCausalLM(nn.Module):
                     proj, param = sub.split(".")[1], sub.split(".")[2]
                     pending_qkv.setdefault(li, {})[f"{proj}.{param}"] = w
                     d = pending_qkv[li]
+                    keys_a = [f"{p}.{param}"
+                              for p in ("q_proj", "k_proj", "v_proj")]
+                    if param in _AWQ_KINDS and all(k in d for k in keys_a):
+                        qkv = layer.self_attn.qkv_proj
+                        self._load_awq(
+                            qkv, f"layers.{li}.self_attn.qkv_proj", param,
+                            [d.pop(k) for k in keys_a], qkv.shard_qkv_parts)
                     keys_w = {"q_proj.weight", "k_proj.weight", "v_proj.weight"}
                     keys_b = {"q_proj.bias", "k_proj.bias", "v_proj.bias"}
                     if keys_w <= d.keys():
@@ -576,6 +655,27 @@ class LlamaFamilyForCausalLM(nn.Module):
                         f"layers.{li}.self_attn.o_proj.weight",
                         layer.self_attn.o_proj.shard(w),
                     )
+                elif (sub.startswith(("self_attn.o_proj.", "mlp.down_proj."))
+                      and sub.split(".")[2] in _AWQ_KINDS):
+                    mod = (layer.self_attn.o_proj if "o_proj" in sub
+                           else layer.mlp.down_proj)
+                    kind = sub.split(".")[2]
+                    per = mod.in_per_rank // (1 if kind == "qweight" else 128)
+                    r = get_tp_rank()
+                    self._load_awq(
+                        mod, f"layers.{li}.{sub.rsplit('.', 1)[0]}", kind, [w],
+                        lambda full: [full[:, r * per:(r + 1) * per]])
+                elif (sub.startswith(("mlp.gate_proj.", "mlp.up_proj."))
+                      and sub.split(".")[2] in _AWQ_KINDS):
+                    kind = sub.split(".")[2]
+                    d = pending_mlp.setdefault((li, kind), {})
+                    d[sub] = w
+                    keys_a = [f"mlp.{p}.{kind}" for p in ("gate_proj", "up_proj")]
+                    if all(k in d for k in keys_a):
+                        gu = layer.mlp.gate_up_proj
+                        self._load_awq(
+                            gu, f"layers.{li}.mlp.gate_up_proj", kind,
+                            [d.pop(k) for k in keys_a], gu.shard_merged_parts)
                 elif sub in ("mlp.gate_proj.weight", "mlp.up_proj.weight"):
                     pending_mlp.setdefault(li, {})[sub] = w
                     d = pending_mlp[li]

@@ -530,6 +530,166 @@ def linear_bf16(x, weight, bias=None, defer: bool = False):
     return F.linear(x, weight, bias)
 
 
+# ---------------------------------------------------------------------------
+# W4A16 (4-bit AWQ-style weights, group 128; format in ops/ref.py)
+# ---------------------------------------------------------------------------
+W4_SKINNY_MAX_M = 64
+# bf16 [N*K] scratch per device for the M > 64 path (dequantize, then the
+# library GEMM). Reserved when a layer is quantized and never grown inside
+# w4_linear, so the pointer captured into decode graphs stays valid.
+_W4_DEQUANT_WS: dict = {}
+
+
+def w4_reserve_workspace(numel: int, device) -> None:
+    """Make the device's W4 dequant workspace hold at least `numel` bf16
+    elements (the largest quantized layer). Call before capturing graphs."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return
+    key = (device.index if device.index is not None
+           else torch.cuda.current_device(),)
+    ws = _W4_DEQUANT_WS.get(key)
+    if ws is None or ws.numel() < numel:
+        _W4_DEQUANT_WS[key] = torch.empty(numel, dtype=torch.bfloat16,
+                                          device=device)
+
+
+def _w4_plan(M: int, N: int, K: int):
+    """Routing rule of the W4 skinny GEMM: (nw, nsplits, k_per_split, mrows).
+    nw = 64-row N sub-tiles per workgroup, mrows = 16 * MT the slab height of
+    the split-K partials, k_per_split a multiple of the 128 group.
+
+    MEASURED on an MI355X (in-graph, weights cycled past the LLC; sweep over
+    nw x nsplits at M = 1/16/32/64 on the Qwen2.5-7B shapes, tables in
+    profiles/w4_gemm.md):
+    - nw = 2 pays only above M = 32, where the activation re-read per tile
+      outweighs the halved workgroup count (down-proj M=64: 27.8 us vs 30.6;
+      M=16: 19.5 vs 17.5; qkv/o/gate_up within 0.6 us of each other at 32).
+    - K-splits: fastest around 800 workgroups at nw = 1 and 450 at nw = 2,
+      with at least 4 chunks (512 k) per split: qkv/o 7 splits (M=64 16 us vs
+      32-38 unsplit), down-proj 14-15 (28 us vs 150-180 unsplit).
+    - once the N tiles alone reach 256 workgroups a split's partials cost
+      more than they hide (gate_up at nw=1, M=16: 26.4 us unsplit, 32.4 with
+      2 splits, 28.8 with 3; at M=64/nw=2 3 splits would gain 7%)."""
+    nw = 2 if (M > 32 and N % 128 == 0) else 1
+    ntiles = N // (64 * nw)
+    chunks = K // 128
+    if ntiles >= 256:
+        nsplits = 1
+    else:
+        target = 800 if nw == 1 else 448
+        nsplits = max(1, min(-(-target // ntiles), chunks // 4))
+    k_per_split = -(-chunks // nsplits) * 128
+    nsplits = -(-K // k_per_split)
+    return nw, nsplits, k_per_split, 16 * min(-(-M // 16), 4)
+
+
+def w4_dequant(packed, out=None):
+    """bf16 [N, K] from a packed W4 weight, via w4_dequant_kernel on GPU."""
+    qweight, scales, zeros = packed
+    N, K = qweight.shape[0], qweight.shape[1] * 8
+    if not qweight.is_cuda:
+        return ref.w4_dequant(*ref.w4_unpack(packed)).to(torch.bfloat16)
+    if out is None:
+        out = torch.empty(N * K, dtype=torch.bfloat16, device=qweight.device)
+    _native().w4_dequant(out, qweight, scales, zeros)
+    return out[: N * K].view(N, K)
+
+
+# 64 < M <= this: the skinny kernel once per 64-row slab; above it the
+# weight is dequantized into the workspace for the library GEMM. Crossover
+# and numbers in w4_linear's docstring.
+W4_SLAB_MAX_M = 128
+
+
+def _w4_skinny(x, packed, bias, defer: bool, plan, out=None):
+    """One launch of the W4 skinny kernel for M <= 64 rows (plus the combine
+    when it splits K and the result is not deferred)."""
+    qweight, scales, zeros = packed
+    M, K = x.shape
+    N = qweight.shape[0]
+    if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    nw, nsplits, k_per_split, mrows = plan or _w4_plan(M, N, K)
+    part = (_skinny_ws(nsplits, N, mrows, x.device) if nsplits > 1
+            else x.new_empty(0, dtype=torch.float32))
+    if defer and nsplits > 1 and _SPLITK_FUSE:
+        _native().w4_skinny_gemm_partials(part, x, qweight, scales, zeros,
+                                          k_per_split, nsplits, nw)
+        return SplitKPending(part, nsplits, mrows, M, N, bias,
+                             (x.device.index,))
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    _native().w4_skinny_gemm(out, part, x, qweight, scales, zeros, bias,
+                             k_per_split, nsplits, nw)
+    return out
+
+
+def _w4_slabs(x, packed, bias):
+    """M > 64 through the skinny kernel, 64 rows at a time, each slab
+    written straight into its rows of the output."""
+    M = x.shape[0]
+    out = torch.empty((M, packed[0].shape[0]), dtype=x.dtype, device=x.device)
+    for r in range(0, M, W4_SKINNY_MAX_M):
+        _w4_skinny(x[r:r + W4_SKINNY_MAX_M], packed, bias, False, None,
+                   out=out[r:r + W4_SKINNY_MAX_M])
+    return out
+
+
+def _w4_dequant_linear(x, packed, bias):
+    """M > 64 through the library GEMM on the weight expanded to bf16 in the
+    device's reserved workspace."""
+    N, K = packed[0].shape[0], packed[0].shape[1] * 8
+    ws = _W4_DEQUANT_WS.get((x.device.index,))
+    if ws is None or ws.numel() < N * K:
+        raise RuntimeError(
+            f"W4 dequant workspace missing or smaller than {N}x{K}: "
+            "call ops.w4_reserve_workspace when the layer is quantized"
+        )
+    import torch.nn.functional as F
+
+    return F.linear(x, w4_dequant(packed, ws), bias)
+
+
+def w4_linear(x, packed, bias=None, defer: bool = False, plan=None):
+    """y = x @ dequant(packed)^T + bias for a packed W4 weight
+    (qweight, scales, zeros). On GPU: the W4 streaming kernel for M <= 64
+    (defer=True returns a SplitKPending when it splits K, as skinny_gemm
+    does); M up to W4_SLAB_MAX_M runs that kernel per 64-row slab; above it
+    the weight is expanded to bf16 in the preallocated workspace and the
+    library GEMM runs on it. No eager fallback: a shape the kernels cannot
+    take raises. On CPU: the reference emulation.
+    plan overrides _w4_plan for M <= 64 (tests force a split count with it).
+
+    M > 64 crossover, MEASURED with scripts/bench_w4.py on an MI355X
+    (in-graph us, slabs vs dequant+library; profiles/w4_gemm.md):
+    M=128: qkv 31.0 vs 37.0, o 28.2 vs 34.2, gate_up 100 vs 151, down 55 vs
+    109 — slabs win everywhere. M=256: qkv 61.6 vs 47.9, o 55.4 vs 30.5,
+    gate_up 197 vs 157 — the library GEMM wins (down alone still favours
+    slabs, 108 vs 138). 192 was not measured; the threshold sits at the last
+    size where slabs were seen to win. Above M = 64 bf16 weights are faster
+    than either route on qkv/o/gate_up (23 / 23 / 70 us at 128): int4 trades
+    large-batch and prefill speed for decode speed and memory."""
+    qweight, scales, zeros = packed
+    if not x.is_cuda:
+        return ref.w4_linear(x, packed, bias)
+    if x.dim() != 2 or x.dtype != torch.bfloat16:
+        raise ValueError(f"w4_linear needs a 2-D bf16 input, got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    M, K = x.shape
+    N = qweight.shape[0]
+    if qweight.shape[1] * 8 != K:
+        raise ValueError(f"w4_linear: x has K={K}, weight K="
+                         f"{qweight.shape[1] * 8}")
+    if M == 0:
+        return x.new_empty((0, N))
+    if M <= W4_SKINNY_MAX_M:
+        return _w4_skinny(x, packed, bias, defer, plan)
+    if M <= W4_SLAB_MAX_M:
+        return _w4_slabs(x, packed, bias)
+    return _w4_dequant_linear(x, packed, bias)
+
+
 def rmsnorm_fp8(x, weight, eps: float = 1e-6):
     """Fused RMSNorm -> per-token fp8 e4m3: (out8, inv_scale). GPU-only
     fast path (hidden <= 8192); otherwise compose the unfused ops."""

@@ -116,6 +116,16 @@ void arks_lora_shrink(void* h, const void* x, const void* a, const void* tiles,
 void arks_lora_expand(void* y, const void* h, const void* b, const void* tiles,
                       int ntiles, int T, int N, int R, int S, int off1,
                       int off2, int max_loras, hipStream_t stream);
+void arks_w4_skinny_gemm(void* part, void* out, const void* a, const void* qw,
+                         const void* scales, const void* zeros,
+                         const void* bias, int m_rows, int n_total,
+                         int k_total, int k_per_split, int nsplits,
+                         int64_t a_stride, int nw, bool combine,
+                         hipStream_t stream);
+int arks_w4_slab_rows(int m_rows);
+void arks_w4_dequant(void* out, const void* qw, const void* scales,
+                     const void* zeros, int n_total, int k_total,
+                     hipStream_t stream);
 void arks_mfma_probe(void* d, const void* a, const void* b, hipStream_t stream);
 void arks_mfma_probe32(void* d, const void* a, const void* b, hipStream_t stream);
 void arks_tr16_probe(void* out, int stride_bytes, hipStream_t stream);
@@ -464,6 +474,108 @@ void skinny_gemm_partials(torch::Tensor part, torch::Tensor a, torch::Tensor w,
                           int64_t config) {
   skinny_gemm_impl(torch::Tensor(), part, a, w, c10::nullopt, k_per_split,
                    nsplits, config, false);
+}
+
+// Packed W4 weight (w4_gemm.hip): qweight i32 [N, K/8], scales f16 [K/128, N],
+// zeros u8 [K/128, N]. Returns (n, k).
+std::pair<int64_t, int64_t> check_w4_packed(const torch::Tensor& qw,
+                                            const torch::Tensor& scales,
+                                            const torch::Tensor& zeros) {
+  TORCH_CHECK(qw.is_cuda() && qw.scalar_type() == torch::kInt32 &&
+              qw.dim() == 2 && qw.is_contiguous(),
+              "qweight must be contiguous int32 [N, K/8] on GPU");
+  const int64_t n = qw.size(0), k = qw.size(1) * 8;
+  TORCH_CHECK(k >= 128 && k % 128 == 0, "W4 needs K % 128 == 0, got K=", k);
+  TORCH_CHECK(n % 64 == 0, "W4 needs N % 64 == 0, got N=", n);
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kFloat16 &&
+              scales.is_contiguous() && scales.dim() == 2 &&
+              scales.size(0) == k / 128 && scales.size(1) == n,
+              "scales must be contiguous f16 [K/128, N] on GPU");
+  TORCH_CHECK(zeros.is_cuda() && zeros.scalar_type() == torch::kUInt8 &&
+              zeros.is_contiguous() && zeros.dim() == 2 &&
+              zeros.size(0) == k / 128 && zeros.size(1) == n,
+              "zeros must be contiguous uint8 [K/128, N] on GPU");
+  TORCH_CHECK(scales.device() == qw.device() && zeros.device() == qw.device());
+  return {n, k};
+}
+
+// nw = 64-row N sub-tiles per workgroup (1 or 2); combine = false leaves the
+// split-K partials in `part` (bias is then applied by the consumer).
+void w4_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
+                         torch::Tensor a, torch::Tensor qw,
+                         torch::Tensor scales, torch::Tensor zeros,
+                         c10::optional<torch::Tensor> bias,
+                         int64_t k_per_split, int64_t nsplits, int64_t nw,
+                         bool combine) {
+  const auto [n, k] = check_w4_packed(qw, scales, zeros);
+  check_bf16_rowstrided(a, "a");
+  TORCH_CHECK(a.dim() == 2 && a.size(1) == k, "a must be [M, K]");
+  TORCH_CHECK(a.device() == qw.device());
+  const int64_t m = a.size(0);
+  TORCH_CHECK(m >= 1 && m <= 64, "w4_skinny_gemm needs 1 <= M <= 64");
+  TORCH_CHECK(a.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "a rows must be 16-byte aligned");
+  TORCH_CHECK((nw == 1 || nw == 2) && n % (64 * nw) == 0,
+              "nw in {1, 2} with N % (64 * nw) == 0");
+  TORCH_CHECK(nsplits >= 1 && k_per_split >= 128 && k_per_split % 128 == 0 &&
+              nsplits * k_per_split >= k && (nsplits - 1) * k_per_split < k,
+              "splits of a multiple of 128 must cover K exactly");
+  const int mrows = arks_w4_slab_rows((int)m);
+  const void* bias_ptr = nullptr;
+  if (combine) {
+    check_bf16_contig(out, "out");
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == m && out.size(1) == n);
+    if (bias.has_value()) {
+      check_bf16_contig(*bias, "bias");
+      TORCH_CHECK(bias->numel() == n);
+      bias_ptr = bias->data_ptr();
+    }
+  } else {
+    TORCH_CHECK(nsplits > 1, "partials-only needs nsplits > 1");
+  }
+  if (nsplits > 1) {
+    TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
+                part.is_contiguous() &&
+                part.numel() >= nsplits * n * mrows &&
+                reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
+                "w4_skinny_gemm workspace too small");
+  }
+  arks_w4_skinny_gemm(nsplits > 1 ? part.data_ptr() : nullptr,
+                      combine ? out.data_ptr() : nullptr, a.data_ptr(),
+                      qw.data_ptr(), scales.data_ptr(), zeros.data_ptr(),
+                      bias_ptr, (int)m, (int)n, (int)k, (int)k_per_split,
+                      (int)nsplits, a.stride(0), (int)nw, combine,
+                      current_stream());
+}
+
+void w4_skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
+                    torch::Tensor qw, torch::Tensor scales,
+                    torch::Tensor zeros, c10::optional<torch::Tensor> bias,
+                    int64_t k_per_split, int64_t nsplits, int64_t nw) {
+  w4_skinny_gemm_impl(out, part, a, qw, scales, zeros, bias, k_per_split,
+                      nsplits, nw, true);
+}
+
+void w4_skinny_gemm_partials(torch::Tensor part, torch::Tensor a,
+                             torch::Tensor qw, torch::Tensor scales,
+                             torch::Tensor zeros, int64_t k_per_split,
+                             int64_t nsplits, int64_t nw) {
+  w4_skinny_gemm_impl(torch::Tensor(), part, a, qw, scales, zeros,
+                      c10::nullopt, k_per_split, nsplits, nw, false);
+}
+
+// out bf16 [>= N*K elements] receives the dequantized [N, K] weight.
+void w4_dequant(torch::Tensor out, torch::Tensor qw, torch::Tensor scales,
+                torch::Tensor zeros) {
+  const auto [n, k] = check_w4_packed(qw, scales, zeros);
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(out.numel() >= n * k && out.device() == qw.device() &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "w4_dequant output too small");
+  TORCH_CHECK(n * (k / 8) < (int64_t)1 << 39);
+  arks_w4_dequant(out.data_ptr(), qw.data_ptr(), scales.data_ptr(),
+                  zeros.data_ptr(), (int)n, (int)k, current_stream());
 }
 
 // Checks shared by the consumers of split-K partials [nsplits, mrows, n].
@@ -851,6 +963,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("a"), py::arg("w"), py::arg("k_per_split"),
         py::arg("nsplits"), py::arg("config") = 0);
   m.def("skinny_combine", &skinny_combine);
+  m.def("w4_skinny_gemm", &w4_skinny_gemm);
+  m.def("w4_skinny_gemm_partials", &w4_skinny_gemm_partials);
+  m.def("w4_dequant", &w4_dequant);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache);
   m.def("greedy_sample", &greedy_sample);

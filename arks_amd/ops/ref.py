@@ -351,3 +351,121 @@ def gumbel_sample(
 
 def softmax_scale(head_dim: int) -> float:
     return 1.0 / math.sqrt(head_dim)
+
+
+# ---------------------------------------------------------------------------
+# W4A16: 4-bit unsigned asymmetric weights, group size 128 along K.
+#   w[n, k] = (q[n, k] - z[n, k // 128]) * s[n, k // 128]
+# q, z are uint8 in 0..15; s is f32 holding f16-representable values (the
+# stored precision). The packed form the GPU kernels read (w4_gemm.hip):
+#   qweight int32 [N, K/8]  nibble i of word c of row n = q[n, 8c + order[i]]
+#   scales  f16   [K/128, N]
+#   zeros   uint8 [K/128, N]
+# order = [0,2,4,6,1,3,5,7] puts elements 2p and 2p+1 in nibbles p and p+4,
+# i.e. 16 bits apart, so one shift+mask yields a bf16 pair in the kernel.
+# ---------------------------------------------------------------------------
+W4_GROUP = 128
+_W4_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+
+
+def _pack_nibbles(x: torch.Tensor) -> torch.Tensor:
+    """[..., L] values 0..15 -> int32 [..., L/8]; nibble i of word c holds
+    x[..., 8c + order[i]]."""
+    assert x.shape[-1] % 8 == 0, x.shape
+    v = x.reshape(*x.shape[:-1], -1, 8).to(torch.int64)
+    v = v[..., list(_W4_ORDER)]
+    shifts = torch.arange(0, 32, 4, dtype=torch.int64, device=x.device)
+    return (v << shifts).sum(dim=-1).to(torch.int32)  # wraps to two's compl.
+
+
+def _unpack_nibbles(p: torch.Tensor) -> torch.Tensor:
+    """Inverse of _pack_nibbles: int32 [..., C] -> uint8 [..., 8C]."""
+    shifts = torch.arange(0, 32, 4, dtype=torch.int32, device=p.device)
+    nib = ((p.unsqueeze(-1) >> shifts) & 0xF).to(torch.uint8)
+    out = torch.empty_like(nib)
+    out[..., list(_W4_ORDER)] = nib
+    return out.reshape(*p.shape[:-1], -1)
+
+
+def w4_check_k(K: int, what: str = "weight") -> None:
+    if K % W4_GROUP != 0:
+        raise ValueError(
+            f"{what}: int4 needs the input width to be a multiple of the "
+            f"group size {W4_GROUP}, got K={K}"
+        )
+
+
+def w4_quantize(w: torch.Tensor):
+    """Round-to-nearest per (row, 128-group) over the group's min/max range
+    (widened to include 0 so the zero-point fits 0..15): (q, z, s) with
+    q uint8 [N, K], z uint8 [N, K/128], s f32 [N, K/128]. s is rounded UP to
+    f16 so the stored scale still spans the range; a constant group gets the
+    smallest scale instead of dividing by zero."""
+    N, K = w.shape
+    w4_check_k(K)
+    G = K // W4_GROUP
+    wf = w.float().reshape(N, G, W4_GROUP)
+    lo = wf.amin(dim=-1).clamp(max=0.0)
+    hi = wf.amax(dim=-1).clamp(min=0.0)
+    s = ((hi - lo) / 15.0).clamp(min=2.0 ** -14)
+    s16 = s.to(torch.float16)
+    # next f16 up (positive values: the bit pattern plus one)
+    s16 = torch.where(s16.float() < s,
+                      (s16.view(torch.int16) + 1).view(torch.float16), s16)
+    s = s16.float()
+    z = torch.round(-lo / s).clamp(0, 15)
+    q = (torch.round(wf / s[..., None]) + z[..., None]).clamp(0, 15)
+    return (q.reshape(N, K).to(torch.uint8), z.to(torch.uint8), s)
+
+
+def w4_dequant(q: torch.Tensor, z: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """f32 [N, K] = (q - z) * s."""
+    N, K = q.shape
+    G = K // W4_GROUP
+    d = q.float().reshape(N, G, W4_GROUP) - z.float()[..., None]
+    return (d * s.float()[..., None]).reshape(N, K)
+
+
+def w4_pack(q: torch.Tensor, z: torch.Tensor, s: torch.Tensor):
+    """(q, z, s) -> the packed triple (qweight, scales, zeros) above."""
+    w4_check_k(q.shape[1])
+    return (_pack_nibbles(q), s.t().contiguous().to(torch.float16),
+            z.t().contiguous().to(torch.uint8))
+
+
+def w4_unpack(packed):
+    """Inverse of w4_pack: (q, z, s)."""
+    qweight, scales, zeros = packed
+    return (_unpack_nibbles(qweight), zeros.t().contiguous(),
+            scales.t().float().contiguous())
+
+
+def w4_linear(x: torch.Tensor, packed, bias=None) -> torch.Tensor:
+    """The CPU emulation of a W4 layer: a bf16 GEMM on the bf16-rounded
+    dequantized weight."""
+    w = w4_dequant(*w4_unpack(packed)).to(torch.bfloat16)
+    return torch.nn.functional.linear(x, w, bias)
+
+
+def awq_unpack(qweight: torch.Tensor, qzeros: torch.Tensor,
+               scales: torch.Tensor):
+    """AutoAWQ "GEMM" on-disk layout -> (q [N, K], z [N, K/128], s [N, K/128]).
+    qweight int32 [K, N/8], qzeros int32 [K/128, N/8], scales f16 [K/128, N];
+    nibble i of packed column c holds logical column 8c + order[i]."""
+    K = qweight.shape[0]
+    w4_check_k(K, "AWQ qweight")
+    if qzeros.shape[0] * W4_GROUP != K or scales.shape[0] * W4_GROUP != K:
+        raise ValueError(
+            f"AWQ tensors disagree on group size {W4_GROUP}: qweight K={K}, "
+            f"qzeros {tuple(qzeros.shape)}, scales {tuple(scales.shape)}"
+        )
+    q = _unpack_nibbles(qweight).t().contiguous()
+    z = _unpack_nibbles(qzeros).t().contiguous()
+    return q, z, scales.t().float().contiguous()
+
+
+def awq_pack(q: torch.Tensor, z: torch.Tensor, s: torch.Tensor):
+    """Inverse of awq_unpack: (qweight, qzeros, scales)."""
+    return (_pack_nibbles(q.t().contiguous()),
+            _pack_nibbles(z.t().contiguous()),
+            s.t().contiguous().to(torch.float16))

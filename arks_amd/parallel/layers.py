@@ -67,6 +67,99 @@ def _fp8_linear(mod: nn.Module, x: torch.Tensor) -> torch.Tensor:
     return F.linear(xd, mod.weight_qdq, mod.bias)
 
 
+def _w4_check_shape(mod: nn.Module, name: str) -> tuple[int, int]:
+    from ..ops import ref
+
+    N, K = mod.weight.shape
+    if K % ref.W4_GROUP != 0:
+        raise ValueError(
+            f"{name}: int4 needs the per-rank input width to be a multiple "
+            f"of the group size {ref.W4_GROUP}, got K={K} at TP="
+            f"{get_tp_world_size()}"
+        )
+    if N % 8 != 0:
+        raise ValueError(f"{name}: int4 needs N % 8 == 0, got N={N}")
+    return N, K
+
+
+def _w4_set_storage(mod: nn.Module, name: str) -> tuple[int, int]:
+    """Replace mod.weight [N, K] by (empty) packed W4 buffers; returns (N, K).
+    The bf16 parameter is dropped, so a model switched before its weights
+    stream in never holds them."""
+    from .. import ops
+    from ..ops import ref
+
+    N, K = _w4_check_shape(mod, name)
+    dev = mod.weight.device
+    G = K // ref.W4_GROUP
+    del mod._parameters["weight"]
+    mod.weight = None
+    mod.register_buffer(
+        "w4_qweight", torch.zeros(N, K // 8, dtype=torch.int32, device=dev),
+        persistent=False)
+    mod.register_buffer(
+        "w4_scales", torch.zeros(G, N, dtype=torch.float16, device=dev),
+        persistent=False)
+    mod.register_buffer(
+        "w4_zeros", torch.zeros(G, N, dtype=torch.uint8, device=dev),
+        persistent=False)
+    mod.w4 = True
+    mod.w4_shape = (N, K)
+    ops.w4_reserve_workspace(N * K, dev)
+    return N, K
+
+
+def init_module_w4(mod: nn.Module, name: str = "linear") -> None:
+    """Switch a linear layer to W4 storage with nothing in it yet (an AWQ
+    checkpoint is about to stream into the packed buffers)."""
+    _w4_set_storage(mod, name)
+
+
+def finalize_module_w4(mod: nn.Module) -> None:
+    """After the packed buffers are filled: reserve the device's dequant
+    workspace (the module may have moved since it was switched) and, on CPU,
+    keep the bf16 dequantized weight that emulates the GPU numerics."""
+    from .. import ops
+    from ..ops import ref
+
+    dev = mod.w4_qweight.device
+    if dev.type == "cuda":
+        ops.w4_reserve_workspace(mod.w4_shape[0] * mod.w4_shape[1], dev)
+        return
+    packed = (mod.w4_qweight, mod.w4_scales, mod.w4_zeros)
+    mod.register_buffer(
+        "weight_qdq",
+        ref.w4_dequant(*ref.w4_unpack(packed)).to(torch.bfloat16),
+        persistent=False,
+    )
+
+
+def quantize_module_w4(mod: nn.Module, name: str = "linear") -> None:
+    """Switch a linear layer to W4A16: round-to-nearest 4-bit asymmetric
+    weights, group size 128 along K (ops.ref.w4_quantize), packed for
+    ops.w4_linear. The bf16 parameter is dropped; on CPU a bf16 dequantized
+    copy emulates the GPU numerics for tests."""
+    from ..ops import ref
+
+    _w4_check_shape(mod, name)
+    w = mod.weight.data
+    packed = ref.w4_pack(*ref.w4_quantize(w))
+    _w4_set_storage(mod, name)
+    mod.w4_qweight.copy_(packed[0])
+    mod.w4_scales.copy_(packed[1])
+    mod.w4_zeros.copy_(packed[2])
+    finalize_module_w4(mod)
+
+
+def _w4_linear(mod: nn.Module, x, bias, defer: bool):
+    if not x.is_cuda:
+        return F.linear(x, mod.weight_qdq, bias)
+    from .. import ops
+
+    return ops.w4_linear(x, (mod.w4_qweight, mod.w4_scales, mod.w4_zeros),
+                         bias, defer=defer)
+
+
 class LoRAState:
     """Per-layer multi-LoRA slot tensors (arks_amd/loader/lora_loader.py):
     A [max_loras, S*R, K] and B [max_loras, N, R] bf16 over the layer's LOCAL
@@ -119,12 +212,14 @@ class ColumnParallelLinear(nn.Module):
         return full[r * self.out_per_rank : (r + 1) * self.out_per_rank]
 
     fp8 = False
+    w4 = False
     lora: LoRAState | None = None  # set when the engine runs enable_lora
 
     def forward(self, x, lora_tiles=None, defer: bool = False):
         """defer=True: the caller can consume an ops.SplitKPending in place
         of the tensor (see ops.skinny_gemm). Granted only where the fused
-        consumers are valid: bf16 GEMM, TP world size 1, no LoRA delta."""
+        consumers are valid: bf16 or W4 GEMM, TP world size 1, no LoRA
+        delta."""
         if isinstance(x, tuple):  # pre-quantized by the producing kernel
             return _fp8_linear_prequant(self, *x)
         if self.fp8:
@@ -133,7 +228,10 @@ class ColumnParallelLinear(nn.Module):
 
         use_lora = lora_tiles is not None and self.lora is not None
         defer = defer and not use_lora and get_tp_world_size() == 1
-        y = ops.linear_bf16(x, self.weight, self.bias, defer=defer)
+        if self.w4:
+            y = _w4_linear(self, x, self.bias, defer)
+        else:
+            y = ops.linear_bf16(x, self.weight, self.bias, defer=defer)
         if use_lora:
             self.lora.apply(y, x, lora_tiles)
         return y
@@ -224,6 +322,7 @@ class RowParallelLinear(nn.Module):
         return full[:, r * self.in_per_rank : (r + 1) * self.in_per_rank]
 
     fp8 = False
+    w4 = False
     lora: LoRAState | None = None  # set when the engine runs enable_lora
 
     def forward(self, x, lora_tiles=None, defer: bool = False):
@@ -244,7 +343,10 @@ class RowParallelLinear(nn.Module):
             use_lora = lora_tiles is not None and self.lora is not None
             defer = (defer and not use_lora and self.bias is None
                      and get_tp_world_size() == 1)
-            y = ops.linear_bf16(x, self.weight, defer=defer)
+            if self.w4:
+                y = _w4_linear(self, x, None, defer)
+            else:
+                y = ops.linear_bf16(x, self.weight, defer=defer)
             if isinstance(y, ops.SplitKPending):
                 return y  # single rank, no bias: nothing left to apply
             if use_lora:

@@ -34,7 +34,10 @@ def parse_args(argv=None):
     p.add_argument("--enforce-eager", action="store_true")
     p.add_argument("--disaggregation-mode", choices=["prefill", "decode"],
                    default=None)
-    p.add_argument("--quantization", choices=["fp8"], default=None)
+    p.add_argument("--quantization", choices=["fp8", "int4", "awq"],
+                   default=None,
+                   help="fp8: W8A8; int4: 4-bit round-to-nearest at load; "
+                        "awq: a 4-bit AWQ checkpoint (also auto-detected)")
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--speculative", choices=["ngram", "draft"], default=None,
                    help="speculative decoding: ngram (prompt lookup) or "
