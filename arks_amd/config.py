@@ -504,6 +504,10 @@ class EngineConfig:
     max_loras: int = 4
     max_lora_rank: int = 16
     lora_modules: dict[str, str] | None = None
+    # structured outputs (arks_amd.structured): cap on a grammar's DFA
+    # states, and rows of the device-resident mask pool ([slots, V/32])
+    structured_max_states: int = 20000
+    structured_mask_slots: int = 512
 
     def __post_init__(self):
         if self.quantization not in (None, "fp8", "int4", "awq"):

@@ -6,6 +6,7 @@ an asyncio loop (arks_amd.server); bench.py drives it directly.
 
 from __future__ import annotations
 
+import threading
 import time
 
 from ..config import EngineConfig
@@ -15,8 +16,13 @@ from .sequence import SamplingParams, Sequence, SeqStatus, StepOutput
 
 
 class LLMEngine:
-    def __init__(self, cfg: EngineConfig):
+    def __init__(self, cfg: EngineConfig, tokenizer=None):
         self.cfg = cfg
+        # structured outputs: the tokenizer whose vocabulary grammars are
+        # indexed against (set_tokenizer), and the LRU of compiled grammars
+        self._tokenizer = tokenizer
+        self._grammars = None
+        self._grammar_lock = threading.Lock()
         self.model_cfg = cfg.model_config()
         # Sliding-window attention: each layer masks keys outside its
         # window (per-layer Qwen2 mixing honored via
@@ -73,6 +79,7 @@ class LLMEngine:
         lora: str | None = None,
     ) -> Sequence:
         seq = Sequence(prompt_token_ids, sampling, request_id, arrival_time)
+        self._attach_matcher(seq)
         seq.hold_pages = hold_pages
         if lora is not None:
             if lora not in self.runner.lora_slots:
@@ -82,6 +89,51 @@ class LLMEngine:
         self.scheduler.add(seq)
         self.total_prompt_tokens += seq.num_prompt_tokens
         return seq
+
+    # ---- structured outputs ----
+    def set_tokenizer(self, tokenizer) -> None:
+        """The tokenizer whose vocabulary grammars are compiled against.
+        Without one the engine loads it from cfg.model_path the way the
+        HTTP layer does, so every TP rank derives the same token table."""
+        with self._grammar_lock:
+            self._tokenizer = tokenizer
+            self._grammars = None
+
+    def compile_structured(self, sampling: SamplingParams):
+        """Compile (or fetch from the LRU) the grammar of
+        sampling.structured; ValueError on a bad spec. Safe to call from
+        another thread ahead of add_request, which then hits the LRU."""
+        from ..structured import GrammarCache, TokenTable
+
+        if sampling.ignore_eos or sampling.min_tokens > 0:
+            raise ValueError(
+                "structured outputs cannot be combined with ignore_eos or "
+                "min_tokens: the grammar decides where the output ends")
+        with self._grammar_lock:
+            if self._grammars is None:
+                tok = self._tokenizer
+                if tok is None:
+                    from ..server.tokenizer import load_tokenizer
+
+                    tok = load_tokenizer(self.cfg.model_path,
+                                         self.model_cfg.vocab_size,
+                                         self.model_cfg.eos_token_id)
+                self._grammars = GrammarCache(
+                    TokenTable.from_tokenizer(tok, self.model_cfg.vocab_size,
+                                              self.model_cfg.eos_token_id),
+                    max_states=self.cfg.structured_max_states,
+                    lock=self._grammar_lock,
+                )
+            cache = self._grammars
+        return cache.get(sampling.structured,
+                         banned=tuple(sampling.stop_token_ids))
+
+    def _attach_matcher(self, seq: Sequence) -> None:
+        if seq.sampling.structured is None:
+            return
+        from ..structured import GrammarMatcher
+
+        seq.matcher = GrammarMatcher(self.compile_structured(seq.sampling))
 
     def load_lora(self, name: str, path: str) -> None:
         """Load a PEFT-format adapter into a free GPU slot under `name`
@@ -128,6 +180,15 @@ class LLMEngine:
         from .kv_cache import BlockAllocator
 
         seq = Sequence(prompt_token_ids, sampling, request_id, arrival_time)
+        self._attach_matcher(seq)
+        if seq.matcher is not None:
+            # validate before any page is taken: append_token advances
+            # the matcher by first_token below
+            eos_ok = (first_token == self.model_cfg.eos_token_id
+                      and seq.matcher.compiled.dfa.accepting[0])
+            if not eos_ok and first_token not in seq.matcher.compiled.state(0)[1]:
+                raise ValueError(
+                    f"first_token {first_token} is not allowed by the grammar")
         need = BlockAllocator.blocks_needed(seq.num_prompt_tokens, self.cfg.block_size)
         if not self.scheduler.allocator.can_allocate(need):
             raise RuntimeError("KV cache exhausted on decode instance")

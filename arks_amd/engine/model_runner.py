@@ -622,13 +622,33 @@ class ModelRunner:
         return emitted  # type: ignore[return-value]
 
     def sample(self, logits: torch.Tensor, seqs: list[Sequence]) -> list[int]:
+        masks = mask_row = None
+        if any(s.matcher is not None for s in seqs):
+            masks, mask_row = self._structured_masks(logits, seqs)
+            if any(
+                sp.logit_bias or sp.has_penalties or sp.logprobs is not None
+                or (sp.temperature > 0.0 and (sp.top_p < 1.0 or sp.top_k > 0
+                                              or sp.min_p > 0.0))
+                for sp in (s.sampling for s in seqs)
+            ):
+                # these paths read the logits, not just a sample: mask them
+                # first so a nucleus, a penalty or a reported logprob only
+                # ever sees allowed tokens
+                logits = ops.apply_token_bitmask(
+                    logits.clone(memory_format=torch.contiguous_format),
+                    masks, mask_row)
+                masks = None
         if any(s.sampling.logit_bias or s.sampling.min_tokens for s in seqs):
             logits = self._apply_bias_min_tokens(logits, seqs)
         if any(s.sampling.has_penalties for s in seqs):
             logits = self._apply_penalties(logits, seqs)
         temps = [s.sampling.temperature for s in seqs]
         if all(t == 0.0 for t in temps):
-            ids = ops.greedy_sample(logits.contiguous())
+            if masks is not None:
+                ids = ops.greedy_sample_masked(logits.contiguous(), masks,
+                                               mask_row)
+            else:
+                ids = ops.greedy_sample(logits.contiguous())
         else:
             logits = self._apply_top_p_top_k(logits, seqs)
             t = torch.tensor(temps, dtype=torch.float32, device=logits.device)
@@ -647,10 +667,85 @@ class ModelRunner:
                         logits.shape[1], dtype=torch.float32,
                         device=logits.device, generator=gen,
                     )
-            ids = ops.sample_tokens(logits.contiguous(), t, u)
+            if masks is not None:
+                ids = ops.sample_tokens_masked(logits.contiguous(), t, u,
+                                               masks, mask_row)
+            else:
+                ids = ops.sample_tokens(logits.contiguous(), t, u)
         out = ids.tolist()
+        if mask_row is not None:
+            # a state with no allowed token at all (only possible when the
+            # request's stop_token_ids ban every one) ends the sequence
+            eos = self.model_cfg.eos_token_id
+            out = [eos if t < 0 else t for t in out]
         self._last_logprobs = self._gather_logprobs(logits, seqs, out)
         return out
+
+    # device-resident pool of packed allowed-token masks, keyed by
+    # (grammar uid, DFA state): decode steps that revisit a state upload one
+    # int per row instead of V/8 bytes
+    _mask_pool: dict | None = None
+
+    def _structured_masks(self, logits: torch.Tensor, seqs: list[Sequence]):
+        """(masks [slots, W] int32, mask_row [rows] int32) for this step;
+        mask_row is -1 for rows without a grammar."""
+        import collections
+
+        import numpy as np
+
+        dev = logits.device
+        words = (logits.shape[1] + 31) // 32
+        pool = self._mask_pool
+        if pool is None or pool["masks"].device != dev or pool["words"] != words:
+            slots = max(1, int(self.cfg.structured_mask_slots))
+            pool = self._mask_pool = {
+                "words": words,
+                "masks": torch.zeros(slots, words, dtype=torch.int32, device=dev),
+                "lru": collections.OrderedDict(),  # key -> slot, oldest first
+                "free": list(range(slots - 1, -1, -1)),
+                "stage": None,
+            }
+        wanted: dict = {}  # key -> packed mask, distinct states of this step
+        for s in seqs:
+            if s.matcher is not None and s.matcher.key not in wanted:
+                m = s.matcher.mask()
+                if m.shape[0] != words:
+                    raise RuntimeError(
+                        f"grammar mask has {m.shape[0]} words but the logits "
+                        f"need {words}: tokenizer and model vocabulary differ")
+                wanted[s.matcher.key] = m
+        lru = pool["lru"]
+        overflow = len(wanted) > pool["masks"].shape[0]
+        misses = list(wanted) if overflow else [k for k in wanted if k not in lru]
+        # pinned staging, one row per miss: sample() ends in .tolist(), so
+        # every copy of the previous step has landed before rows are reused
+        stage = pool["stage"]
+        if misses and (stage is None or stage.shape[0] < len(misses)):
+            n = max(len(misses), 8)
+            stage = torch.empty(n, words, dtype=torch.int32,
+                                pin_memory=dev.type == "cuda")
+            pool["stage"] = stage
+        np_stage = stage.numpy() if misses else None
+        for j, k in enumerate(misses):
+            np_stage[j] = wanted[k].view(np.int32)
+        if overflow:
+            # more live states than slots: this step's masks go up directly
+            # and the pool is left as it is
+            masks = stage[: len(misses)].to(dev, non_blocking=True)
+            slot_of = {k: j for j, k in enumerate(misses)}
+        else:
+            masks = pool["masks"]
+            for k in wanted:  # hits first, so eviction never takes one
+                if k in lru:
+                    lru.move_to_end(k)
+            for j, k in enumerate(misses):
+                slot = pool["free"].pop() if pool["free"] else lru.popitem(last=False)[1]
+                lru[k] = slot
+                masks[slot].copy_(stage[j], non_blocking=True)
+            slot_of = lru
+        rows = [-1 if s.matcher is None else slot_of[s.matcher.key] for s in seqs]
+        mask_row = torch.tensor(rows, dtype=torch.int32).to(dev, non_blocking=True)
+        return masks, mask_row
 
     _last_logprobs: dict | None = None
 
@@ -761,7 +856,8 @@ class ModelRunner:
                 # vLLM min_p: drop tokens with prob < min_p * max prob
                 keep[j] &= probs[j] >= sp.min_p * probs[j, 0]
             keep[j, 0] = True  # always keep the best token
-        sub = sub.masked_fill(~keep, float("-inf"))
+        # keep is in sorted order, so it masks the sorted values
+        sub = sorted_logits.masked_fill(~keep, float("-inf"))
         # scatter back to original column order
         restored = torch.full_like(sub, float("-inf"))
         restored.scatter_(1, sorted_idx, sub)

@@ -24,6 +24,10 @@ class SamplingParams:
     logit_bias: dict[int, float] | None = None  # OpenAI logit_bias
     min_tokens: int = 0  # suppress eos/stop tokens until this many emitted
     prompt_logprobs: bool = False  # score prompt tokens at prefill (echo)
+    # structured outputs: {"kind": "json_schema"|"json_object"|"regex"|
+    # "choice", "value": ...} — plain data, so it crosses the TP broadcast
+    # and the disaggregation wire like every other field
+    structured: dict | None = None
 
     @property
     def has_penalties(self) -> bool:
@@ -66,6 +70,9 @@ class Sequence:
         # model) and its GPU slot (-1 = base)
         self.lora_name: str | None = None
         self.lora_slot = -1
+        # structured outputs: the GrammarMatcher the engine attaches when
+        # sampling.structured is set; advanced by every appended token
+        self.matcher = None
         self.num_cached_tokens = 0  # tokens whose KV is already in cache
         # prompt-token logprobs (sampling.prompt_logprobs): value at index
         # q-1 scores prompt token q given tokens < q (first token unscored)
@@ -103,11 +110,17 @@ class Sequence:
         if self.first_token_time is None:
             self.first_token_time = time.time()
         self.output_token_ids.append(token_id)
+        if self.matcher is not None and not self.matcher.is_terminated:
+            self.matcher.advance(token_id)
 
     def check_finished(self, eos_token_id: int) -> bool:
         sp = self.sampling
-        if self.num_output_tokens >= sp.max_tokens:
+        if self.matcher is not None and self.matcher.is_terminated:
+            self.finish_reason = "stop"  # the grammar accepted and EOS came
+        elif self.num_output_tokens >= sp.max_tokens:
             self.finish_reason = "length"
+        elif self.matcher is not None:
+            return False  # eos/stop ids are the grammar's business
         elif not sp.ignore_eos and self.output_token_ids and (
             self.output_token_ids[-1] == eos_token_id
             or self.output_token_ids[-1] in sp.stop_token_ids

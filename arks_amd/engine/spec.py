@@ -118,6 +118,7 @@ def eligible(seq: Sequence) -> bool:
         and sp.logprobs is None
         and not sp.logit_bias
         and sp.min_tokens == 0
+        and seq.matcher is None  # structured: masks are not draft-aware
     )
 
 
@@ -136,5 +137,6 @@ def eligible_sampled(seq: Sequence) -> bool:
         and sp.logprobs is None
         and not sp.logit_bias
         and sp.min_tokens == 0
+        and seq.matcher is None  # structured: masks are not draft-aware
         and sp.seed is None
     )

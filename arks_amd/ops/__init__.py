@@ -844,3 +844,36 @@ def greedy_sample(logits):
         _native().greedy_sample(out, logits)
         return out
     return ref.greedy_sample(logits)
+
+
+def greedy_sample_masked(logits, masks, mask_row):
+    """Argmax over the tokens whose bit is set in masks[mask_row[r]]
+    (mask_row -1 = unconstrained row); -1 for a row with no bit set."""
+    if logits.is_cuda:
+        out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
+        _native().greedy_sample_masked(out, logits, masks, mask_row)
+        return out
+    return ref.greedy_sample_masked(logits, masks, mask_row)
+
+
+def sample_tokens_masked(logits, temperatures, uniform, masks, mask_row):
+    """Gumbel-max sampling restricted to each row's allowed tokens."""
+    if logits.is_cuda:
+        out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
+        _native().gumbel_sample_masked(out, logits, temperatures, uniform,
+                                       masks, mask_row)
+        return out
+    return ref.gumbel_sample_masked(logits, temperatures, uniform, masks,
+                                    mask_row)
+
+
+gumbel_sample_masked = sample_tokens_masked
+
+
+def apply_token_bitmask(logits, masks, mask_row):
+    """In place: logits[r, t] = -inf where token t's bit is clear in
+    masks[mask_row[r]]; rows with mask_row -1 are left alone."""
+    if logits.is_cuda:
+        _native().apply_token_bitmask(logits, masks, mask_row)
+        return logits
+    return ref.apply_token_bitmask(logits, masks, mask_row)

@@ -98,6 +98,18 @@ void arks_greedy_sample(void* out, const void* logits, int rows, int vocab,
 void arks_gumbel_sample(void* out, const void* logits, const void* temperatures,
                         const void* uniform, int rows, int vocab,
                         hipStream_t stream);
+void arks_greedy_sample_masked(void* out, const void* logits,
+                               const void* masks, const void* mask_row,
+                               int rows, int vocab, int slots,
+                               hipStream_t stream);
+void arks_gumbel_sample_masked(void* out, const void* logits,
+                               const void* temperatures, const void* uniform,
+                               const void* masks, const void* mask_row,
+                               int rows, int vocab, int slots,
+                               hipStream_t stream);
+void arks_apply_token_bitmask(void* logits, int is_fp32, const void* masks,
+                              const void* mask_row, int rows, int vocab,
+                              int slots, hipStream_t stream);
 void arks_ar_seq_inc(void* seq, hipStream_t stream);
 void arks_one_shot_allreduce(void* out, const void* src, void* mail_ptrs[8],
                              void* flag_ptrs[8], void* seq, int rank,
@@ -724,6 +736,62 @@ void gumbel_sample(torch::Tensor out, torch::Tensor logits,
                      current_stream());
 }
 
+// masks [slots, ceil(vocab/32)] int32, mask_row [rows] int32 (-1 = none)
+static void check_bitmask(const torch::Tensor& logits,
+                          const torch::Tensor& masks,
+                          const torch::Tensor& mask_row) {
+  TORCH_CHECK(logits.dim() == 2 && masks.dim() == 2 && mask_row.dim() == 1);
+  TORCH_CHECK(masks.is_cuda() && mask_row.is_cuda());
+  TORCH_CHECK(masks.scalar_type() == torch::kInt32 && masks.is_contiguous());
+  TORCH_CHECK(mask_row.scalar_type() == torch::kInt32 &&
+              mask_row.is_contiguous());
+  TORCH_CHECK(masks.size(1) == (logits.size(1) + 31) / 32,
+              "masks must have ceil(vocab/32) words per row");
+  TORCH_CHECK(mask_row.size(0) == logits.size(0), "one mask_row per row");
+}
+
+void greedy_sample_masked(torch::Tensor out, torch::Tensor logits,
+                          torch::Tensor masks, torch::Tensor mask_row) {
+  check_bf16_contig(logits, "logits");
+  check_bitmask(logits, masks, mask_row);
+  TORCH_CHECK(out.scalar_type() == torch::kInt64 &&
+              out.numel() == logits.size(0));
+  arks_greedy_sample_masked(out.data_ptr(), logits.data_ptr(),
+                            masks.data_ptr(), mask_row.data_ptr(),
+                            logits.size(0), logits.size(1), masks.size(0),
+                            current_stream());
+}
+
+void gumbel_sample_masked(torch::Tensor out, torch::Tensor logits,
+                          torch::Tensor temperatures, torch::Tensor uniform,
+                          torch::Tensor masks, torch::Tensor mask_row) {
+  check_bf16_contig(logits, "logits");
+  check_bitmask(logits, masks, mask_row);
+  TORCH_CHECK(out.scalar_type() == torch::kInt64 &&
+              out.numel() == logits.size(0));
+  TORCH_CHECK(temperatures.scalar_type() == torch::kFloat32 &&
+              temperatures.numel() == logits.size(0));
+  TORCH_CHECK(uniform.scalar_type() == torch::kFloat32 &&
+              uniform.is_contiguous() && uniform.numel() == logits.numel());
+  arks_gumbel_sample_masked(out.data_ptr(), logits.data_ptr(),
+                            temperatures.data_ptr(), uniform.data_ptr(),
+                            masks.data_ptr(), mask_row.data_ptr(),
+                            logits.size(0), logits.size(1), masks.size(0),
+                            current_stream());
+}
+
+void apply_token_bitmask(torch::Tensor logits, torch::Tensor masks,
+                         torch::Tensor mask_row) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous());
+  const bool f32 = logits.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(f32 || logits.scalar_type() == torch::kBFloat16,
+              "logits must be bf16 or fp32");
+  check_bitmask(logits, masks, mask_row);
+  arks_apply_token_bitmask(logits.data_ptr(), f32 ? 1 : 0, masks.data_ptr(),
+                           mask_row.data_ptr(), logits.size(0), logits.size(1),
+                           masks.size(0), current_stream());
+}
+
 // D[16,16] = A[16,32] @ B[32,16], all bf16 in / f32 out. Verifies the MFMA
 // fragment layout assumption on hardware.
 void tr16_probe(torch::Tensor out, int64_t stride_bytes) {
@@ -970,6 +1038,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache);
   m.def("greedy_sample", &greedy_sample);
   m.def("gumbel_sample", &gumbel_sample);
+  m.def("greedy_sample_masked", &greedy_sample_masked);
+  m.def("gumbel_sample_masked", &gumbel_sample_masked);
+  m.def("apply_token_bitmask", &apply_token_bitmask);
   m.def("ipc_alloc", &ipc_alloc);
   m.def("arm_flags", &arm_flags);
   m.def("ipc_alloc_free", &ipc_alloc_free);

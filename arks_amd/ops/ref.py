@@ -349,6 +349,57 @@ def gumbel_sample(
     return scaled.argmax(dim=-1)
 
 
+def bitmask_allowed(masks: torch.Tensor, mask_row: torch.Tensor,
+                    vocab: int) -> torch.Tensor:
+    """[rows, vocab] bool from packed masks: bit (t % 32) of int32 word
+    (t // 32) of masks[mask_row[r]] allows token t. Rows with mask_row -1
+    allow everything; bits at positions >= vocab are ignored."""
+    t = torch.arange(vocab, device=masks.device)
+    mr = mask_row.long()
+    words = masks[mr.clamp(min=0)][:, t // 32].long()
+    allowed = ((words >> (t % 32)) & 1).bool()
+    return allowed | (mr < 0).unsqueeze(1)
+
+
+def apply_token_bitmask(logits: torch.Tensor, masks: torch.Tensor,
+                        mask_row: torch.Tensor) -> torch.Tensor:
+    """In place: -inf where the token's bit is clear."""
+    allowed = bitmask_allowed(masks, mask_row, logits.shape[1])
+    logits.masked_fill_(~allowed, float("-inf"))
+    return logits
+
+
+def _pick_allowed(scores: torch.Tensor, allowed: torch.Tensor) -> torch.Tensor:
+    ids = scores.argmax(dim=-1)
+    # every allowed score is -inf: argmax may sit on a masked index; the
+    # lowest allowed index wins then, and a row with no bit set gives -1
+    bad = ~allowed.gather(1, ids.unsqueeze(1)).squeeze(1)
+    first = allowed.int().argmax(dim=-1)
+    first = torch.where(allowed.any(dim=-1), first, torch.full_like(first, -1))
+    return torch.where(bad, first, ids)
+
+
+def greedy_sample_masked(logits: torch.Tensor, masks: torch.Tensor,
+                         mask_row: torch.Tensor) -> torch.Tensor:
+    """greedy_sample over the allowed tokens only (NaN/+inf on a masked
+    token never win); [rows] int64, -1 for an empty mask."""
+    allowed = bitmask_allowed(masks, mask_row, logits.shape[1])
+    lf = torch.where(allowed, logits.float(), float("-inf"))
+    return _pick_allowed(lf, allowed)
+
+
+def gumbel_sample_masked(logits, temperatures, uniform, masks,
+                         mask_row) -> torch.Tensor:
+    """gumbel_sample over the allowed tokens only."""
+    allowed = bitmask_allowed(masks, mask_row, logits.shape[1])
+    lf = torch.where(allowed, logits.float(), float("-inf"))
+    t = temperatures.float().clamp(min=0.0).unsqueeze(1)
+    gumbel = -torch.log(-torch.log(uniform.float().clamp(1e-20, 1.0)))
+    scaled = torch.where(t > 0, lf / t.clamp(min=1e-8) + gumbel, lf)
+    scaled = torch.where(allowed, scaled, float("-inf"))
+    return _pick_allowed(scaled, allowed)
+
+
 def softmax_scale(head_dim: int) -> float:
     return 1.0 / math.sqrt(head_dim)
 

@@ -92,6 +92,29 @@ class StopStringTracker:
         return out
 
 
+def _structured_of(req) -> dict | None:
+    """The request's output constraint as SamplingParams.structured, None
+    when it has none. ValueError when more than one is given."""
+    specs: list[dict] = []
+    rf = getattr(req, "response_format", None)
+    if rf is not None and rf.type == "json_object":
+        specs.append({"kind": "json_object", "value": None})
+    elif rf is not None and rf.type == "json_schema":
+        if rf.json_schema is None or rf.json_schema.schema_ is None:
+            raise ValueError("response_format.json_schema.schema is required")
+        specs.append({"kind": "json_schema", "value": rf.json_schema.schema_})
+    if req.guided_json is not None:
+        specs.append({"kind": "json_schema", "value": req.guided_json})
+    if req.guided_regex is not None:
+        specs.append({"kind": "regex", "value": req.guided_regex})
+    if req.guided_choice is not None:
+        specs.append({"kind": "choice", "value": list(req.guided_choice)})
+    if len(specs) > 1:
+        raise ValueError("at most one of response_format, guided_json, "
+                         "guided_regex and guided_choice may be given")
+    return specs[0] if specs else None
+
+
 def _error(status: int, message: str) -> JSONResponse:
     return JSONResponse(
         status_code=status, content=ErrorResponse.make(message, status).model_dump()
@@ -114,6 +137,9 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
     app.state.engine = engine
     app.state.tokenizer = tokenizer
     app.state.model_name = served_model_name
+    core = getattr(engine, "engine", None)
+    if hasattr(core, "set_tokenizer"):
+        core.set_tokenizer(tokenizer)  # grammars index this vocabulary
 
     if disagg_mode == "prefill":
         from .disagg import add_prefill_routes
@@ -169,6 +195,19 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
         )
 
 
+    async def _constrain(req, sp: SamplingParams) -> str | None:
+        """Attach the request's grammar to sp; the error text for a 400
+        when the spec is bad. Compiles on the default thread pool, off the
+        engine's step thread, so the engine-side compile hits the LRU."""
+        try:
+            sp.structured = _structured_of(req)
+            if sp.structured is not None:
+                await asyncio.get_running_loop().run_in_executor(
+                    None, engine.engine.compile_structured, sp)
+        except ValueError as e:
+            return str(e)
+        return None
+
     async def _collect_choice(rid, token_ids, sp, stops, prefill_addr,
                               lora=None):
         """One non-streamed choice: (token_ids, text, finish, n_generated)."""
@@ -213,6 +252,9 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
             return _error(400, f"prompt is {len(token_ids)} tokens; "
                                f"max_model_len is {engine.cfg.max_model_len}")
         sp = _sampling(req, req.max_completion_tokens or req.max_tokens)
+        bad = await _constrain(req, sp)
+        if bad:
+            return _error(400, bad)
         rid = f"chatcmpl-{uuid.uuid4().hex}"
         if req.stream:
             if req.n > 1:
@@ -394,6 +436,9 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
             return _error(400, f"prompt is {len(token_ids)} tokens; "
                                f"max_model_len is {engine.cfg.max_model_len}")
         sp = _sampling(req, req.max_tokens)
+        bad = await _constrain(req, sp)
+        if bad:
+            return _error(400, bad)
         if req.echo:
             if req.n > 1 or req.stream:
                 return _error(400, "echo is not supported with n > 1 or stream")

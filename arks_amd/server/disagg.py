@@ -20,6 +20,11 @@ can replace httpx without touching the engine.
 TP>1 on either side: extract_kv all-gathers the KV head shards so the wire
 tensor always carries the FULL head set, and inject_kv takes each rank's
 slice — prefill and decode instances may run different TP degrees.
+
+`sampling` carries every SamplingParams field, `structured` (the output
+grammar, plain data) included: the prefill side samples the first token
+under the grammar, and the decode side's add_prefilled advances its own
+matcher by that token.
 """
 
 from __future__ import annotations

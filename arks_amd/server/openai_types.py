@@ -20,6 +20,21 @@ class ChatMessage(BaseModel):
     content: str | None = ""
 
 
+class JsonSchemaFormat(BaseModel):
+    name: str | None = None
+    description: str | None = None
+    # `schema` shadows a BaseModel attribute, hence the alias
+    schema_: dict[str, Any] | None = Field(default=None, alias="schema")
+    strict: bool | None = None
+
+    model_config = {"populate_by_name": True}
+
+
+class ResponseFormat(BaseModel):
+    type: Literal["text", "json_object", "json_schema"]
+    json_schema: JsonSchemaFormat | None = None
+
+
 class ChatCompletionRequest(BaseModel):
     model: str
     messages: list[ChatMessage]
@@ -42,6 +57,11 @@ class ChatCompletionRequest(BaseModel):
     ignore_eos: bool = False  # extension (load testing)
     logit_bias: dict[str, float] | None = None
     min_tokens: int = 0  # extension (vLLM-compatible)
+    # structured outputs (at most one of the four per request)
+    response_format: ResponseFormat | None = None
+    guided_json: dict[str, Any] | str | None = None  # extension (vLLM)
+    guided_regex: str | None = None  # extension (vLLM)
+    guided_choice: list[str] | None = None  # extension (vLLM)
 
 
 class CompletionRequest(BaseModel):
@@ -64,6 +84,10 @@ class CompletionRequest(BaseModel):
     ignore_eos: bool = False
     logit_bias: dict[str, float] | None = None
     min_tokens: int = 0  # extension (vLLM-compatible)
+    # structured outputs (at most one per request)
+    guided_json: dict[str, Any] | str | None = None  # extension (vLLM)
+    guided_regex: str | None = None  # extension (vLLM)
+    guided_choice: list[str] | None = None  # extension (vLLM)
     echo: bool = False  # return the prompt (+ its logprobs) too
 
 
