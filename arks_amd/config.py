@@ -357,6 +357,49 @@ PRESET_CONFIGS: dict[str, ModelConfig] = {
         eos_token_id=2,
         bos_token_id=1,
     ),
+    # The two below have widths the W4 expert kernels take (multiples of the
+    # 128 group, also per rank at TP=2: 8 heads x 32 and a shared width of
+    # 256 leave 128 each).
+    "tiny-qwen2moe-w4": ModelConfig(  # Qwen2-MoE naming + shared expert
+        architecture="Qwen2MoeForCausalLM",
+        vocab_size=512,
+        hidden_size=128,
+        intermediate_size=256,
+        moe_intermediate_size=128,
+        shared_expert_intermediate_size=256,
+        num_hidden_layers=2,
+        num_attention_heads=8,
+        num_key_value_heads=2,
+        head_dim=32,
+        rope_theta=10000.0,
+        max_position_embeddings=2048,
+        attention_bias=True,
+        num_local_experts=4,
+        num_experts_per_tok=2,
+        norm_topk_prob=False,
+        eos_token_id=2,
+        bos_token_id=1,
+    ),
+    "tiny-qwen3moe-w4": ModelConfig(  # Qwen3-MoE naming
+        architecture="Qwen3MoeForCausalLM",
+        vocab_size=512,
+        hidden_size=128,
+        intermediate_size=256,
+        moe_intermediate_size=128,
+        num_hidden_layers=2,
+        num_attention_heads=8,
+        num_key_value_heads=2,
+        head_dim=32,
+        rope_theta=10000.0,
+        max_position_embeddings=2048,
+        attention_bias=False,
+        qk_norm=True,
+        num_local_experts=4,
+        num_experts_per_tok=2,
+        norm_topk_prob=True,
+        eos_token_id=2,
+        bos_token_id=1,
+    ),
     "qwen3-30b-a3b": ModelConfig(  # Qwen3-30B-A3B MoE shape
         architecture="Qwen3MoeForCausalLM",
         vocab_size=151936,
@@ -477,10 +520,14 @@ class EngineConfig:
     # None | "fp8": W8A8 OCP-e4m3 for qkv/gate_up/down/lm_head GEMMs
     # (dynamic per-token activation scales; o_proj and KV stay bf16)
     # "int4": W4A16, round-to-nearest at load, group size 128, for the dense
-    # qkv/o/gate_up/down GEMMs (lm_head, embeddings, MoE experts stay bf16)
-    # "awq": a 4-bit AWQ checkpoint (auto-detected from its config.json;
-    # giving it for any other checkpoint is an error)
+    # qkv/o/gate_up/down GEMMs (lm_head, embeddings and router gates stay
+    # bf16; MoE experts stay bf16 unless quantize_experts is set)
+    # "awq": a 4-bit AWQ checkpoint, dense or MoE (auto-detected from its
+    # config.json; giving it for any other checkpoint is an error)
     quantization: str | None = None
+    # with quantization="int4" on an MoE model: also quantize the routed
+    # experts and the shared expert at load (routed grouped W4 GEMM)
+    quantize_experts: bool = False
     # "auto" (bf16) | "fp8": e4m3 KV pages (halves the decode KV stream;
     # scale 1.0, opt-in like vLLM's --kv-cache-dtype fp8)
     kv_cache_dtype: str = "auto"
@@ -514,6 +561,12 @@ class EngineConfig:
             raise ValueError(
                 f"unknown quantization {self.quantization!r}: expected "
                 "None, 'fp8', 'int4' or 'awq'"
+            )
+        if self.quantize_experts and self.quantization != "int4":
+            raise ValueError(
+                "quantize_experts needs quantization='int4', got "
+                f"quantization={self.quantization!r} (an AWQ checkpoint's "
+                "experts are 4-bit already)"
             )
         if not self.enable_lora:
             if self.lora_modules:
@@ -549,6 +602,11 @@ class EngineConfig:
     def resolve_quantization(self, model_cfg: ModelConfig) -> str | None:
         """The mode the engine runs: an AWQ checkpoint selects "awq" on its
         own and excludes every other mode; "awq" needs such a checkpoint."""
+        if self.quantize_experts and model_cfg.num_local_experts == 0:
+            raise ValueError(
+                "quantize_experts needs an MoE model, "
+                f"{model_cfg.architecture} has no experts"
+            )
         if model_cfg.quant_method == "awq":
             if self.quantization not in (None, "awq"):
                 raise ValueError(

@@ -103,7 +103,11 @@ class ModelRunner:
         if self.quantization == "fp8":
             self.model.quantize_fp8()
         elif self.quantization == "int4":
-            self.model.quantize_int4()
+            self.model.quantize_int4(self.cfg.quantize_experts)
+            if self.device.type == "cuda":
+                # the dropped bf16 weights sit in the caching allocator;
+                # hand them back so profile_num_blocks sees them as free
+                torch.cuda.empty_cache()
         elif self.quantization == "awq":
             self.model.finalize_w4()
         elif self.quantization is not None:

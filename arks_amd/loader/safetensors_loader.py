@@ -234,20 +234,20 @@ def save_awq_checkpoint(cfg, out_dir: str, seed: int = 0,
                         dequantized_dir: str | None = None,
                         split_files: bool = False) -> None:
     """Write a random-init checkpoint in the AutoAWQ "GEMM" layout: every
-    dense q/k/v/o/gate/up/down projection is quantized (ops.ref.w4_quantize)
-    and stored as .qweight/.qzeros/.scales (ops.ref.awq_pack); norms, biases,
-    embeddings and lm_head are f16 as AutoAWQ writes them. config.json
-    carries the quantization_config.
+    q/k/v/o/gate/up/down projection (of a dense MLP, of each routed MoE
+    expert under its Qwen-MoE or Mixtral w1/w3/w2 name, and of the shared
+    expert) is quantized (ops.ref.w4_quantize) and stored as
+    .qweight/.qzeros/.scales (ops.ref.awq_pack); norms, biases, embeddings,
+    lm_head and the MoE router / shared-expert gates are f16 as AutoAWQ
+    writes them. config.json carries the quantization_config.
     dequantized_dir: also write a plain bf16 checkpoint holding the
     dequantized weights (the model an AWQ engine must reproduce).
     split_files: two safetensors files, with gate_proj and up_proj tensors
     in different files (exercises the loader's carry-over)."""
     from ..ops import ref
 
-    if cfg.num_local_experts > 0:
-        raise ValueError("save_awq_checkpoint covers dense models only")
     projs = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj",
-             "down_proj")
+             "down_proj", "w1", "w2", "w3")
     awq: dict[str, torch.Tensor] = {}
     plain: dict[str, torch.Tensor] = {}
     for name, t in _random_hf_tensors(cfg, seed).items():
@@ -386,6 +386,19 @@ def _write_checkpoint(cfg, out_dir: str, tensors: dict[str, torch.Tensor],
         "bos_token_id": cfg.bos_token_id,
         "torch_dtype": "bfloat16",
     }
+    if cfg.num_local_experts > 0:
+        # Mixtral spells the expert count num_local_experts, Qwen-MoE
+        # num_experts
+        mixtral = cfg.architecture.startswith("MixtralFor")
+        hf_cfg.update({
+            "num_local_experts" if mixtral else "num_experts":
+                cfg.num_local_experts,
+            "num_experts_per_tok": cfg.num_experts_per_tok,
+            "moe_intermediate_size": cfg.moe_intermediate_size,
+            "shared_expert_intermediate_size":
+                cfg.shared_expert_intermediate_size,
+            "norm_topk_prob": cfg.norm_topk_prob,
+        })
     hf_cfg.update(extra_config or {})
     with open(os.path.join(out_dir, "config.json"), "w") as f:
         json.dump(hf_cfg, f, indent=1)

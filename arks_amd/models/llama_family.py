@@ -119,7 +119,10 @@ class Attention(nn.Module):
                 q.contiguous().view(-1, hd)).view(T, self.nq_local * hd)
             k = self.k_norm(
                 k.contiguous().view(-1, hd)).view(T, self.nkv_local * hd)
-            v = v.contiguous()  # reshape_and_cache wants one shared kv stride
+            # reshape_and_cache wants one shared kv stride. clone, not
+            # contiguous(): a one-row view counts as contiguous and would
+            # keep the fused buffer's row stride (batch-1 decode)
+            v = v.clone(memory_format=torch.contiguous_format)
         k_cache, v_cache = kv_cache
         if self.use_rope:
             q, k = ops.rope_and_cache(
@@ -261,9 +264,172 @@ class MoEMLP(nn.Module):
     # shapes make every decode batch size hipGraph-capturable.
     DENSE_TOKENS = 256
 
+    # ---- W4 experts (int4 + quantize_experts, AWQ checkpoints) ----
+    # Stacked packed buffers per local expert, ops.ref.w4_pack's format with
+    # a leading expert dimension: w13 is [gate | up] along N (N = 2I, K = H),
+    # w2 has N = H, K = I. The bf16 w13 / w2 parameters are dropped. On CPU
+    # bf16-rounded dequantized [E, in, out] buffers named w13 / w2 stand in
+    # for them and the bf16 forward runs unchanged (the weight_qdq
+    # convention of the dense layers).
+    w4 = False
+
+    def w4_check_shapes(self, name: str) -> None:
+        """What w4_moe_gemm_kernel needs of both expert GEMMs: K a multiple
+        of the 128 group, N a multiple of the 64-row tile."""
+        H, I = self.hidden, self.inter
+        if H % 128 or I % 128 or (2 * I) % 64 or H % 64:
+            raise ValueError(
+                f"{name}: MoE expert width {I} is not supported: W4 experts "
+                f"need hidden and expert widths that are multiples of the "
+                f"group size 128, got hidden={H}, expert width={I}"
+            )
+
+    def w4_packed(self, which: str):
+        return (getattr(self, f"{which}_qweight"),
+                getattr(self, f"{which}_scales"),
+                getattr(self, f"{which}_zeros"))
+
+    def init_w4(self, name: str = "moe") -> None:
+        """Switch to (empty) W4 storage; the bf16 parameters are dropped, so
+        a block switched before its weights stream in never holds them."""
+        from ..ops import ref
+
+        self.w4_check_shapes(name)
+        dev = self.w13.device
+        E, H, I = self.local_experts, self.hidden, self.inter
+        del self._parameters["w13"]
+        del self._parameters["w2"]
+        for which, (N, K) in (("w13", (2 * I, H)), ("w2", (H, I))):
+            G = K // ref.W4_GROUP
+            self.register_buffer(
+                f"{which}_qweight",
+                torch.zeros(E, N, K // 8, dtype=torch.int32, device=dev),
+                persistent=False)
+            self.register_buffer(
+                f"{which}_scales",
+                torch.zeros(E, G, N, dtype=torch.float16, device=dev),
+                persistent=False)
+            self.register_buffer(
+                f"{which}_zeros",
+                torch.zeros(E, G, N, dtype=torch.uint8, device=dev),
+                persistent=False)
+        self.w4 = True
+
+    def finalize_w4(self) -> None:
+        """After the packed buffers are filled: on CPU keep the bf16
+        dequantized experts that emulate the GPU numerics."""
+        from ..ops import ref
+
+        if self.w13_qweight.is_cuda:
+            return
+        for which in ("w13", "w2"):
+            qw, sc, zr = self.w4_packed(which)
+            deq = torch.stack([
+                ref.w4_dequant(*ref.w4_unpack((qw[e], sc[e], zr[e])))
+                .to(torch.bfloat16).t() for e in range(self.local_experts)
+            ]).contiguous()
+            if which in self._buffers:
+                del self._buffers[which]
+            self.register_buffer(which, deq, persistent=False)
+
+    def quantize_w4(self, name: str = "moe") -> None:
+        """Round-to-nearest W4 of loaded bf16 experts, one expert at a time
+        (ops.ref.w4_quantize), so the transient memory is one expert's."""
+        from ..ops import ref
+
+        self.w4_check_shapes(name)
+        bf16 = {"w13": self.w13.data, "w2": self.w2.data}
+        self.init_w4(name)
+        for which, w in bf16.items():
+            qw, sc, zr = self.w4_packed(which)
+            for e in range(self.local_experts):
+                # stored [in, out]; the quantizer takes [N, K] = [out, in]
+                packed = ref.w4_pack(*ref.w4_quantize(w[e].t()))
+                qw[e].copy_(packed[0])
+                sc[e].copy_(packed[1])
+                zr[e].copy_(packed[2])
+        del bf16
+        self.finalize_w4()
+
+    def load_awq_expert(self, name: str, le: int, proj: str, kind: str,
+                        t: torch.Tensor) -> None:
+        """One AWQ tensor (kind: qweight / qzeros / scales) of local expert
+        le's gate / up / down projection into the stacked buffers: gate
+        fills rows [0, I) of w13, up rows [I, 2I). The packed format is
+        row-major over N, so each tensor lands on its own."""
+        from ..ops import ref
+
+        if not self.w4:
+            raise ValueError(
+                f"{name}: AWQ tensor in the checkpoint but the model was not "
+                "prepared for AWQ (config.json lacks quantization_config?)"
+            )
+        H, I = self.hidden, self.inter
+        which, r0, N, K = {"gate": ("w13", 0, I, H), "up": ("w13", I, I, H),
+                           "down": ("w2", 0, H, I)}[proj]
+        G = K // ref.W4_GROUP
+        want = {"qweight": (K, N // 8), "qzeros": (G, N // 8),
+                "scales": (G, N)}[kind]
+        if tuple(t.shape) != want:
+            raise ValueError(
+                f"{name}: shape {tuple(t.shape)}, expected {want} for a "
+                f"{N}x{K} projection at group size {ref.W4_GROUP}"
+            )
+        qw, sc, zr = self.w4_packed(which)
+        t = t.cpu()
+        if kind == "scales":    # on disk [K/128, N]: our layout already
+            sc[le, :, r0:r0 + N].copy_(t.to(torch.float16))
+        elif kind == "qzeros":
+            zr[le, :, r0:r0 + N].copy_(ref._unpack_nibbles(t))
+        else:
+            rows = ref._unpack_nibbles(t).t().contiguous()  # [N, K]
+            qw[le, r0:r0 + N].copy_(ref._pack_nibbles(rows))
+
+    def _forward_w4(self, x):
+        """GPU forward over W4 experts, the same for every T: route once,
+        then two routed grouped GEMMs that stream only the experts the batch
+        selected. Up to DENSE_TOKENS the launch shapes depend on T alone (no
+        host sync; the decode graphs capture it); above it one sync per layer
+        fetches the longest expert list to size the grid."""
+        from ..parallel.comm import tp_all_reduce
+
+        T, k = x.shape[0], self.top_k
+        router_logits = torch.nn.functional.linear(x, self.gate).float()
+        weights, selected = ops.moe_topk(router_logits, k, self.norm_topk)
+        counts, pairs = ops.moe_route(selected, self.expert_base,
+                                      self.local_experts)
+        max_rows = (T if T <= self.DENSE_TOKENS
+                    else max(1, int(counts.max().item())))
+        gu = ops.w4_moe_gemm(x, self.w4_packed("w13"), counts, pairs, k,
+                             max_rows)                     # [T*k, 2I]
+        h = ops.silu_mul(gu)                               # [T*k, I]
+        # y row 0 is a zero row: the pairs of experts other ranks own are
+        # never written, and the mix multiplies whatever it reads (0 * NaN
+        # is NaN), so their slots read row 0 at weight 0.
+        y = x.new_empty(T * k + 1, self.hidden)
+        ops.w4_moe_gemm(h, self.w4_packed("w2"), counts, pairs, 1, max_rows,
+                        out=y[1:])
+        rows = torch.arange(1, T * k + 1, dtype=torch.int32,
+                            device=x.device).view(T, k)
+        if self.local_experts != self.num_experts:
+            y[0].zero_()
+            le = selected - self.expert_base
+            mine = (le >= 0) & (le < self.local_experts)
+            rows = torch.where(mine, rows, torch.zeros_like(rows))
+            weights = torch.where(mine, weights, torch.zeros_like(weights))
+        out = tp_all_reduce(ops.moe_mix_rows(y, weights, rows))
+        if self.shared is not None:
+            gate = torch.sigmoid(
+                torch.nn.functional.linear(x, self.shared_gate).float()
+            ).to(x.dtype)
+            out = out + gate * self.shared(x)
+        return out
+
     def forward(self, x):
         from ..parallel.comm import tp_all_reduce
 
+        if self.w4 and x.is_cuda:
+            return self._forward_w4(x)
         T = x.shape[0]
         router_logits = torch.nn.functional.linear(x, self.gate).float()
         # fused softmax+topk+renorm routing kernel (ops.moe_topk) replaces
@@ -466,45 +632,79 @@ class LlamaFamilyForCausalLM(nn.Module):
         quantize_module_fp8(self.lm_head)
         self.norm.fp8_out = True
 
-    def _w4_targets(self):
-        """(name, module) of the layers int4 / AWQ quantize: the dense
-        qkv/o/gate_up/down projections. lm_head and the embeddings stay bf16
-        (as in AWQ checkpoints), and so do MoE blocks."""
+    # the MoE blocks are W4 too (AWQ checkpoint, or int4 + quantize_experts)
+    _w4_experts = False
+
+    def _w4_targets(self, experts: bool = False):
+        """(name, module) of the linear layers int4 / AWQ quantize: the
+        dense qkv/o/gate_up/down projections and, with experts=True, the
+        Qwen2-MoE shared expert (an ordinary MLP). lm_head, the embeddings
+        and the router gates stay bf16 (as in AWQ checkpoints); the routed
+        experts are not linear layers, see _moe_blocks."""
         for i, layer in enumerate(self.layers):
             yield f"layers.{i}.self_attn.qkv_proj", layer.self_attn.qkv_proj
             yield f"layers.{i}.self_attn.o_proj", layer.self_attn.o_proj
-            if isinstance(layer.mlp, MoEMLP):
-                continue
-            yield f"layers.{i}.mlp.gate_up_proj", layer.mlp.gate_up_proj
-            yield f"layers.{i}.mlp.down_proj", layer.mlp.down_proj
+            mlp = layer.mlp
+            if isinstance(mlp, MoEMLP):
+                if not experts or mlp.shared is None:
+                    continue
+                mlp = mlp.shared
+                pre = f"layers.{i}.mlp.shared_expert"
+            else:
+                pre = f"layers.{i}.mlp"
+            yield f"{pre}.gate_up_proj", mlp.gate_up_proj
+            yield f"{pre}.down_proj", mlp.down_proj
 
-    def quantize_int4(self) -> None:
+    def _moe_blocks(self):
+        for i, layer in enumerate(self.layers):
+            if isinstance(layer.mlp, MoEMLP):
+                yield f"layers.{i}.mlp", layer.mlp
+
+    def quantize_int4(self, quantize_experts: bool = False) -> None:
         """W4A16 round-to-nearest (group 128) over a loaded bf16 model; the
-        activations stay bf16, so the norms and SwiGLU are unchanged."""
+        activations stay bf16, so the norms and SwiGLU are unchanged.
+        quantize_experts also quantizes the routed experts and the shared
+        expert of an MoE model; a width the grouped kernel cannot take
+        raises naming the layer."""
         from ..parallel.layers import quantize_module_w4
 
-        for name, mod in self._w4_targets():
+        if quantize_experts:
+            if self.cfg.num_local_experts == 0:
+                raise ValueError(
+                    "quantize_experts needs an MoE model, "
+                    f"{self.cfg.architecture} has no experts")
+            for name, moe in self._moe_blocks():
+                moe.w4_check_shapes(name)
+            self._w4_experts = True
+        for name, mod in self._w4_targets(quantize_experts):
             quantize_module_w4(mod, name)
+        if quantize_experts:
+            for name, moe in self._moe_blocks():
+                moe.quantize_w4(name)
 
     def prepare_awq(self) -> None:
         """Switch the quantized layers to (empty) W4 storage BEFORE an AWQ
-        checkpoint streams in, so their bf16 weights are never allocated on
-        the device; finalize_w4() completes the switch after loading."""
+        checkpoint streams in, so their bf16 weights (the experts' above
+        all) are never allocated on the device; finalize_w4() completes the
+        switch after loading."""
         from ..parallel.layers import init_module_w4
 
-        if self.cfg.num_local_experts > 0:
-            raise ValueError(
-                f"AWQ checkpoints of MoE architectures are not supported "
-                f"({self.cfg.architecture}): int4 covers dense layers only"
-            )
-        for name, mod in self._w4_targets():
+        for name, moe in self._moe_blocks():
+            moe.w4_check_shapes(name)
+        self._w4_experts = self.cfg.num_local_experts > 0
+        for name, mod in self._w4_targets(self._w4_experts):
             init_module_w4(mod, name)
+        for name, moe in self._moe_blocks():
+            moe.init_w4(name)
 
     def finalize_w4(self) -> None:
         from ..parallel.layers import finalize_module_w4
 
-        for _, mod in self._w4_targets():
+        for _, mod in self._w4_targets(self._w4_experts):
             finalize_module_w4(mod)
+        if self._w4_experts:
+            for _, moe in self._moe_blocks():
+                moe.finalize_w4()
 
     def _load_awq(self, mod, name: str, kind: str, fulls, shard_parts) -> None:
         """One AWQ tensor kind (qweight / qzeros / scales) of a projection,
@@ -650,6 +850,61 @@ class LlamaFamilyForCausalLM(nn.Module):
                         put_cat(f"layers.{li}.self_attn.qkv_proj.bias", parts)
                         for kk in keys_b:
                             del d[kk]
+                elif (parts[-1] in _AWQ_KINDS and ".".join(parts[2:-1]) in (
+                        "mlp.gate", "block_sparse_moe.gate",
+                        "mlp.shared_expert_gate")):
+                    raise ValueError(
+                        f"{name}: a quantized router gate is not supported "
+                        "(AWQ checkpoints keep the MoE gates in f16)")
+                elif (parts[-1] == "weight" and getattr(layer.mlp, "w4", False)
+                      and sub.startswith(("mlp.experts.",
+                                          "block_sparse_moe.experts."))):
+                    raise ValueError(
+                        f"{name}: plain weight of an MoE expert in an AWQ "
+                        "checkpoint (mixed-precision expert checkpoints are "
+                        "not supported)")
+                elif (parts[-1] == "weight"
+                      and sub.startswith("mlp.shared_expert.")
+                      and getattr(layer.mlp.shared.down_proj, "w4", False)):
+                    raise ValueError(
+                        f"{name}: plain weight of the shared expert in an "
+                        "AWQ checkpoint (mixed-precision expert checkpoints "
+                        "are not supported)")
+                elif (parts[-1] in _AWQ_KINDS and sub.startswith(
+                        ("mlp.experts.", "block_sparse_moe.experts."))):
+                    # experts.N.{gate,up,down}_proj.* (Qwen-MoE) or
+                    # experts.N.{w1,w3,w2}.* (Mixtral); other ranks' experts
+                    # are skipped
+                    moe = layer.mlp
+                    le = int(parts[4]) - moe.expert_base
+                    proj = {"gate_proj": "gate", "up_proj": "up",
+                            "down_proj": "down", "w1": "gate", "w3": "up",
+                            "w2": "down"}.get(parts[5])
+                    if proj is not None and 0 <= le < moe.local_experts:
+                        moe.load_awq_expert(name, le, proj, parts[-1], w)
+                elif (parts[-1] in _AWQ_KINDS
+                      and sub.startswith("mlp.shared_expert.down_proj.")):
+                    mod = layer.mlp.shared.down_proj
+                    kind = parts[-1]
+                    per = mod.in_per_rank // (1 if kind == "qweight" else 128)
+                    r = get_tp_rank()
+                    self._load_awq(
+                        mod, f"layers.{li}.mlp.shared_expert.down_proj", kind,
+                        [w], lambda full: [full[:, r * per:(r + 1) * per]])
+                elif (parts[-1] in _AWQ_KINDS and sub.startswith(
+                        ("mlp.shared_expert.gate_proj.",
+                         "mlp.shared_expert.up_proj."))):
+                    kind = parts[-1]
+                    d = pending_mlp.setdefault((li, "se", kind), {})
+                    d[sub] = w
+                    keys_a = [f"mlp.shared_expert.{p}.{kind}"
+                              for p in ("gate_proj", "up_proj")]
+                    if all(k in d for k in keys_a):
+                        gu = layer.mlp.shared.gate_up_proj
+                        self._load_awq(
+                            gu, f"layers.{li}.mlp.shared_expert.gate_up_proj",
+                            kind, [d.pop(k) for k in keys_a],
+                            gu.shard_merged_parts)
                 elif sub == "self_attn.o_proj.weight":
                     put(
                         f"layers.{li}.self_attn.o_proj.weight",

@@ -690,6 +690,36 @@ def w4_linear(x, packed, bias=None, defer: bool = False, plan=None):
     return _w4_dequant_linear(x, packed, bias)
 
 
+def w4_moe_gemm(a, packed, counts, pairs, src_div: int, max_rows: int,
+                out=None):
+    """Routed grouped W4A16 GEMM over the stacked local experts of an MoE
+    block (w4_moe_gemm_kernel): for every local expert e and every
+    p in pairs[e][:counts[e]], out[p] = a[p // src_div] @ dequant(W[e])^T.
+    packed = (qweight [E, N, K/8], scales [E, K/128, N], zeros [E, K/128, N]);
+    counts, pairs come from moe_route. src_div = k gathers token rows for the
+    w13 GEMM (a = hidden states [T, K]), src_div = 1 reads a = h [T*k, K].
+    max_rows bounds the longest expert list (T is always enough); the launch
+    shape depends on it and on the weight's shape only, so with max_rows = T
+    the call is hipGraph-capturable. Rows of `out` [T*k, N] that belong to no
+    local expert are not written. `out` and everything else allocated here
+    come from the caching allocator, i.e. from the graph's own pool under
+    capture, so no pointer a captured graph holds is ever reallocated.
+    No eager fallback on GPU: a shape the kernel cannot take raises."""
+    if not a.is_cuda:
+        return ref.w4_moe_gemm(a, packed, counts, pairs, src_div, out=out)
+    qweight, scales, zeros = packed
+    T = pairs.shape[1] if pairs.dim() == 2 else 0
+    top_k = a.shape[0] * src_div // max(T, 1)
+    if out is None:
+        out = torch.empty((T * top_k, qweight.shape[1]), dtype=a.dtype,
+                          device=a.device)
+    if not a.is_contiguous() or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    _native().w4_moe_gemm(out, a, qweight, scales, zeros, counts, pairs,
+                          top_k, src_div, max_rows)
+    return out
+
+
 def rmsnorm_fp8(x, weight, eps: float = 1e-6):
     """Fused RMSNorm -> per-token fp8 e4m3: (out8, inv_scale). GPU-only
     fast path (hidden <= 8192); otherwise compose the unfused ops."""
@@ -804,6 +834,21 @@ def moe_topk(router_logits, k: int, renorm: bool):
                            1 if renorm else 0)
         return weights, ids
     return ref.moe_topk(router_logits, k, renorm)
+
+
+def moe_route(ids, expert_base: int, n_local: int):
+    """Routing table of the W4 expert GEMM from moe_topk's ids [T, k]:
+    (counts int32 [n_local], pairs int32 [n_local, T]); local expert e's
+    first counts[e] entries of pairs[e] are the pair indices p = t*k + j
+    routed to it, ascending (the rest is unspecified). One launch, no atomics
+    and no host sync, so it is hipGraph-capturable."""
+    if not ids.is_cuda:
+        return ref.moe_route(ids, expert_base, n_local)
+    T = ids.shape[0]
+    counts = torch.empty(n_local, dtype=torch.int32, device=ids.device)
+    pairs = torch.empty(n_local, T, dtype=torch.int32, device=ids.device)
+    _native().moe_route(counts, pairs, ids.contiguous(), expert_base)
+    return counts, pairs
 
 
 def moe_mix(y, weights, ids, expert_base: int = 0):

@@ -138,6 +138,13 @@ int arks_w4_slab_rows(int m_rows);
 void arks_w4_dequant(void* out, const void* qw, const void* scales,
                      const void* zeros, int n_total, int k_total,
                      hipStream_t stream);
+void arks_w4_moe_gemm(void* out, const void* a, const void* qw,
+                      const void* scales, const void* zeros,
+                      const void* counts, const void* pairs, int n_experts,
+                      int t_cols, int n_pairs, int src_div, int slabs,
+                      int n_total, int k_total, int nw, hipStream_t stream);
+void arks_moe_route(void* counts, void* pairs, const void* ids, int n_pairs,
+                    int T, int expert_base, int n_local, hipStream_t stream);
 void arks_mfma_probe(void* d, const void* a, const void* b, hipStream_t stream);
 void arks_mfma_probe32(void* d, const void* a, const void* b, hipStream_t stream);
 void arks_tr16_probe(void* out, int stride_bytes, hipStream_t stream);
@@ -590,6 +597,75 @@ void w4_dequant(torch::Tensor out, torch::Tensor qw, torch::Tensor scales,
                   zeros.data_ptr(), (int)n, (int)k, current_stream());
 }
 
+// Routed grouped GEMM over stacked experts (w4_moe_gemm_kernel):
+//   out[p] = a[p / src_div] @ dequant(W[e])^T for p in pairs[e][:counts[e]].
+// qweight i32 [E, N, K/8], scales f16 [E, K/128, N], zeros u8 [E, K/128, N],
+// counts i32 [E], pairs i32 [E, T], out bf16 [n_pairs, N]. Everything the
+// kernel indexes by is checked here; the table's contents are clamped to
+// these extents in the kernel.
+void w4_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor qw,
+                 torch::Tensor scales, torch::Tensor zeros,
+                 torch::Tensor counts, torch::Tensor pairs, int64_t top_k,
+                 int64_t src_div, int64_t max_rows) {
+  TORCH_CHECK(qw.is_cuda() && qw.scalar_type() == torch::kInt32 &&
+              qw.dim() == 3 && qw.is_contiguous(),
+              "qweight must be contiguous int32 [E, N, K/8] on GPU");
+  const int64_t ne = qw.size(0), n = qw.size(1), k = qw.size(2) * 8;
+  TORCH_CHECK(ne >= 1 && ne <= 65535, "need 1 <= E_local <= 65535");
+  TORCH_CHECK(k >= 128 && k % 128 == 0, "W4 needs K % 128 == 0, got K=", k);
+  TORCH_CHECK(n >= 64 && n % 64 == 0, "W4 needs N % 64 == 0, got N=", n);
+  TORCH_CHECK(n * (k / 8) < ((int64_t)1 << 31), "expert weight too large");
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kFloat16 &&
+              scales.is_contiguous() && scales.dim() == 3 &&
+              scales.size(0) == ne && scales.size(1) == k / 128 &&
+              scales.size(2) == n,
+              "scales must be contiguous f16 [E, K/128, N] on GPU");
+  TORCH_CHECK(zeros.is_cuda() && zeros.scalar_type() == torch::kUInt8 &&
+              zeros.is_contiguous() && zeros.dim() == 3 &&
+              zeros.size(0) == ne && zeros.size(1) == k / 128 &&
+              zeros.size(2) == n,
+              "zeros must be contiguous uint8 [E, K/128, N] on GPU");
+  check_bf16_contig(a, "a");
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(a.dim() == 2 && a.size(1) == k, "a must be [rows, K]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "a rows must be 16-byte aligned");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == torch::kInt32 &&
+              counts.is_contiguous() && counts.dim() == 1 &&
+              counts.size(0) == ne, "counts must be int32 [E_local] on GPU");
+  TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt32 &&
+              pairs.is_contiguous() && pairs.dim() == 2 &&
+              pairs.size(0) == ne && pairs.size(1) >= 1,
+              "pairs must be int32 [E_local, T] on GPU, got ", pairs.sizes());
+  const int64_t t_cols = pairs.size(1);
+  TORCH_CHECK(top_k >= 1, "top_k must be >= 1");
+  const int64_t n_pairs = t_cols * top_k;
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == n && out.size(0) == n_pairs,
+              "out must be [T*k, N] = [", n_pairs, ", ", n, "], got ",
+              out.sizes());
+  TORCH_CHECK(n_pairs < ((int64_t)1 << 31) / 2);
+  TORCH_CHECK(src_div >= 1 && a.size(0) * src_div >= n_pairs,
+              "a has ", a.size(0), " rows, too few for ", n_pairs,
+              " pairs at src_div=", src_div);
+  TORCH_CHECK(max_rows >= 1 && max_rows <= t_cols,
+              "need 1 <= max_rows <= T, got ", max_rows);
+  const auto dev = qw.device();
+  TORCH_CHECK(scales.device() == dev && zeros.device() == dev &&
+              a.device() == dev && out.device() == dev &&
+              counts.device() == dev && pairs.device() == dev);
+  const int64_t slabs = (max_rows + 63) / 64;
+  TORCH_CHECK(slabs <= 65535, "max_rows too large");
+  // NW = 2 halves the activation re-read per tile and pays above 32 rows
+  // (ops._w4_plan); a slab of an expert's list rarely holds that many
+  // unless the batch does.
+  const int nw = (max_rows > 32 && n % 128 == 0) ? 2 : 1;
+  arks_w4_moe_gemm(out.data_ptr(), a.data_ptr(), qw.data_ptr(),
+                   scales.data_ptr(), zeros.data_ptr(), counts.data_ptr(),
+                   pairs.data_ptr(), (int)ne, (int)t_cols, (int)n_pairs,
+                   (int)src_div, (int)slabs, (int)n, (int)k, nw,
+                   current_stream());
+}
+
 // Checks shared by the consumers of split-K partials [nsplits, mrows, n].
 const void* check_partials(const torch::Tensor& part,
                            const c10::optional<torch::Tensor>& bias,
@@ -900,6 +976,29 @@ void moe_topk(torch::Tensor weights, torch::Tensor ids,
                 (int)k, (int)renorm, current_stream());
 }
 
+// counts i32 [n_local], pairs i32 [n_local, T] from ids i32 [T, k].
+void moe_route(torch::Tensor counts, torch::Tensor pairs, torch::Tensor ids,
+               int64_t expert_base) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == torch::kInt32 &&
+              ids.is_contiguous() && ids.dim() == 2 && ids.size(0) >= 1 &&
+              ids.size(1) >= 1, "ids must be contiguous int32 [T, k] on GPU");
+  const int64_t T = ids.size(0), n_pairs = ids.numel();
+  TORCH_CHECK(n_pairs < ((int64_t)1 << 30));
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == torch::kInt32 &&
+              counts.is_contiguous() && counts.dim() == 1 &&
+              counts.size(0) >= 1 && counts.size(0) <= 65535,
+              "counts must be int32 [E_local] on GPU");
+  TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt32 &&
+              pairs.is_contiguous() && pairs.dim() == 2 &&
+              pairs.size(0) == counts.size(0) && pairs.size(1) == T,
+              "pairs must be int32 [E_local, T] on GPU");
+  TORCH_CHECK(counts.device() == ids.device() &&
+              pairs.device() == ids.device());
+  arks_moe_route(counts.data_ptr(), pairs.data_ptr(), ids.data_ptr(),
+                 (int)n_pairs, (int)T, (int)expert_base, (int)counts.size(0),
+                 current_stream());
+}
+
 void moe_mix(torch::Tensor out, torch::Tensor y, torch::Tensor weights,
              torch::Tensor ids, int64_t expert_base, int64_t n_local) {
   check_bf16_contig(out, "out");
@@ -1034,6 +1133,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w4_skinny_gemm", &w4_skinny_gemm);
   m.def("w4_skinny_gemm_partials", &w4_skinny_gemm_partials);
   m.def("w4_dequant", &w4_dequant);
+  m.def("w4_moe_gemm", &w4_moe_gemm);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache);
   m.def("greedy_sample", &greedy_sample);
@@ -1049,6 +1149,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ipc_close", &ipc_close);
   m.def("one_shot_allreduce", &one_shot_allreduce);
   m.def("moe_topk", &moe_topk);
+  m.def("moe_route", &moe_route);
   m.def("moe_mix", &moe_mix);
   m.def("moe_mix_rows", &moe_mix_rows);
   m.def("lora_shrink", &lora_shrink);

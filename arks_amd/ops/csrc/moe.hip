@@ -11,6 +11,8 @@
 //              renormalization; emits (weights[T,k] f32, ids[T,k] i32).
 //   moe_mix:   out[t,h] = sum_i w[t,i] * y[ids[t,i], t, h] — the weighted
 //              gather-mix over the dense per-expert outputs y[E,T,H].
+//   moe_route: per local expert the ascending list of the (token, slot)
+//              pairs routed to it — the table the W4 expert GEMM gathers by.
 //
 // Reference parity note: the reference delegates MoE serving to external
 // images; these kernels are runtime-slot internals.
@@ -154,9 +156,59 @@ __global__ __launch_bounds__(256) void moe_mix_rows_kernel(
   }
 }
 
+// Routing table of the W4 expert GEMM (w4_gemm.hip w4_moe_gemm_kernel): one
+// workgroup per local expert walks the n_pairs = T*k ids in order, 256 at a
+// time, and appends the index p = t*k + j of every pair routed to its expert:
+//   pairs[e][0 .. counts[e]) ascending, counts[e] <= T.
+// The position of a match is a ballot/popcount prefix inside its wave plus
+// the matches of the waves and iterations before it: no atomics, no host
+// sync, a launch shape that depends on E_local only, and the same table on
+// every run. A token's k experts are distinct, so T columns suffice; a
+// position past them (ids that break that rule) is dropped, not written.
+__global__ __launch_bounds__(256) void moe_route_kernel(
+    int* __restrict__ counts,      // [E_local]
+    int* __restrict__ pairs,       // [E_local, T]
+    const int* __restrict__ ids,   // [n_pairs] global expert ids
+    const int n_pairs, const int T, const int expert_base) {
+  const int e = blockIdx.x;
+  const int want = expert_base + e;
+  const int wave = threadIdx.x / WAVE_SIZE;
+  const int lane = threadIdx.x % WAVE_SIZE;
+  __shared__ int wave_cnt[2][4];  // double-buffered: one barrier per round
+  int base = 0;
+  int slot = 0;
+  for (int i0 = 0; i0 < n_pairs; i0 += 256, slot ^= 1) {
+    const int i = i0 + threadIdx.x;
+    const bool hit = i < n_pairs && ids[i] == want;
+    const uint64_t mask = __ballot(hit);
+    if (lane == 0) wave_cnt[slot][wave] = __popcll(mask);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = wave_cnt[slot][w];
+      before += w < wave ? c : 0;
+      total += c;
+    }
+    const int pos =
+        base + before + __popcll(mask & ((uint64_t(1) << lane) - 1));
+    if (hit && pos < T) pairs[(int64_t)e * T + pos] = i;
+    base += total;
+  }
+  if (threadIdx.x == 0) counts[e] = min(base, T);
+}
+
 }  // namespace arks
 
 using namespace arks;
+
+extern "C" void arks_moe_route(void* counts, void* pairs, const void* ids,
+                               int n_pairs, int T, int expert_base,
+                               int n_local, hipStream_t stream) {
+  dim3 grid(n_local), block(256);
+  hipLaunchKernelGGL(moe_route_kernel, grid, block, 0, stream, (int*)counts,
+                     (int*)pairs, (const int*)ids, n_pairs, T, expert_base);
+}
 
 extern "C" void arks_moe_topk(void* weights, void* ids, const void* logits,
                               int T, int E, int k, int renorm,

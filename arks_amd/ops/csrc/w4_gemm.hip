@@ -44,6 +44,12 @@
 //   so splitk_add_rmsnorm / splitk_rope_cache / skinny_combine read them
 //   unchanged. N % (64*NW) == 0, K % 128 == 0, k_per_split % 128 == 0.
 //
+// w4_moe_gemm_kernel is the same chunk loop over the stacked experts of an
+// MoE block ([E, N, K/8] / [E, K/128, N]), its rows gathered and scattered
+// through the routing table that moe_route_kernel (moe.hip) writes; comment
+// at the kernel. Its body is a copy of the dense loop rather than a shared
+// template so that the dense kernel's code generation does not move.
+//
 // w4_dequant_kernel expands the packed weight to bf16 [N, K] for the library
 // GEMM (M > 64).
 #include "common.h"
@@ -306,6 +312,222 @@ __global__ __launch_bounds__(256) void w4_skinny_gemm_kernel(
   }
 }
 
+// One 64-entry slab of one expert's routing list: the chunk loop of
+// w4_skinny_gemm_kernel (same staging, W ring, folded zero-point) with the
+// activation rows GATHERED through the list and the result rows SCATTERED to
+// out[p]. MT is the slab's live 16-row tiles, so an expert with 4 rows pays
+// for one tile, not four. No split-K, no bias.
+//   prow[i] (LDS, i < 16*MT): pair index of list entry i, entries past the
+//   end clamped to the last valid one (duplicates that are never stored).
+template <int MT, int NW, int PF, typename Lds>
+__device__ __forceinline__ void w4_moe_slab(
+    Lds& lds, const int* prow, bf16* __restrict__ out,
+    const bf16* __restrict__ a, const uint32_t* __restrict__ qw,
+    const uint16_t* __restrict__ scales, const uint8_t* __restrict__ zeros,
+    const int rows, const int src_div, const int n_total, const int k_total) {
+  constexpr int NT = 64 * NW;
+  constexpr int KC = W4_KC;
+  const int n0 = blockIdx.x * NT;
+  const int tid = threadIdx.x;
+  const int wave = tid / WAVE_SIZE;
+  const int lane = tid % WAVE_SIZE;
+  const int lq = lane % 16;
+  const int la = lane / 16;
+
+  f32x4 acc[NW][MT];
+#pragma unroll
+  for (int j = 0; j < NW; ++j)
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[j][t] = {0.f, 0.f, 0.f, 0.f};
+
+  const int kwords = k_total / 8;
+  const uint32_t* qrow = qw + (int64_t)(n0 + wave * 16 + lq) * kwords + 4 * la;
+  const int nc = n0 + wave * 16 + 4 * la;
+
+  // Source rows of this thread's staging items, resolved once: the chunk
+  // loop below is then the dense kernel's, branch for branch.
+  constexpr int NIT = MT;
+  const bf16* arow[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it)
+    arow[it] = a + (int64_t)(prow[(tid + it * 256) / 16] / src_div) * k_total +
+               (tid % 16) * 8;
+  auto load_a = [&](int kc, ushort8 (&gv)[NIT]) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it)
+      gv[it] = *reinterpret_cast<const ushort8*>(arow[it] + kc);
+  };
+  auto store_a = [&](const ushort8 (&gv)[NIT], int buf) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = tid + it * 256;
+      const ushort8 v = gv[it];
+      *reinterpret_cast<ushort8*>(&lds.s.a_buf[buf][i / 16][(i % 16) * 8]) = v;
+      float sum = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sum += bf16_bits_to_float(v[e]);
+      lds.s.asum[buf][i / 16] = row16_sum(sum);
+    }
+  };
+
+  W4Chunk<NW> wreg[PF + 1];
+  auto load_w = [&](int kc, W4Chunk<NW>& dst) {
+    kc = min(kc, k_total - KC);  // branchless, see w4_skinny_gemm_kernel
+    const int64_t g = (int64_t)(kc / KC) * n_total;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+      dst.q[j] = *reinterpret_cast<const u32x4*>(
+          qrow + (int64_t)j * 64 * kwords + kc / 8);
+      dst.sc[j] =
+          *reinterpret_cast<const ushort4v*>(scales + g + nc + j * 64);
+      dst.zr[j] = *reinterpret_cast<const uint32_t*>(zeros + g + nc + j * 64);
+    }
+  };
+
+  {
+    ushort8 gv[NIT];
+    load_a(0, gv);
+#pragma unroll
+    for (int p = 0; p <= PF; ++p) load_w(p * KC, wreg[p]);
+    store_a(gv, 0);
+  }
+  __syncthreads();
+
+  int buf = 0;
+  for (int kc0 = 0; kc0 < k_total; kc0 += (PF + 1) * KC) {
+#pragma unroll
+    for (int u = 0; u <= PF; ++u) {
+      const int kc = kc0 + u * KC;
+      if (kc >= k_total) break;  // uniform
+      ushort8 gv[NIT];
+      load_a(min(kc + KC, k_total - KC), gv);
+      const W4Chunk<NW> cur = wreg[u];
+      load_w(kc + (PF + 1) * KC, wreg[u]);
+
+      f32x4 cacc[NW][MT];
+#pragma unroll
+      for (int j = 0; j < NW; ++j)
+#pragma unroll
+        for (int t = 0; t < MT; ++t) cacc[j][t] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        bf16x8 wf[NW];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) wf[j] = w4_frag(cur.q[j][s]);
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+          ushort8 af = *reinterpret_cast<const ushort8*>(
+              &lds.s.a_buf[buf][t * 16 + lq][32 * la + 8 * s]);
+#pragma unroll
+          for (int j = 0; j < NW; ++j)
+            cacc[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                wf[j], *reinterpret_cast<bf16x8*>(&af), cacc[j][t], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        float sf[4], zf[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          sf[r] = f16_bits_to_float(cur.sc[j][r]);
+          zf[r] = -(128.f + (float)((cur.zr[j] >> (8 * r)) & 0xFFu));
+        }
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+          const float as = lds.s.asum[buf][t * 16 + lq];
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            acc[j][t][r] = __builtin_fmaf(
+                sf[r], __builtin_fmaf(zf[r], as, cacc[j][t][r]), acc[j][t][r]);
+        }
+      }
+      store_a(gv, buf ^ 1);
+      __syncthreads();
+      buf ^= 1;
+    }
+  }
+
+  // Epilogue: transpose C^T through LDS, round to bf16, scatter row m of the
+  // slab to out[prow[m]]; rows >= `rows` are the clamped duplicates.
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NW; ++j)
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        lds.c_buf[j * 64 + wave * 16 + 4 * la + r][t * 16 + lq] = acc[j][t][r];
+  __syncthreads();
+  for (int i = tid; i < rows * NT; i += 256) {
+    const int m = i / NT;
+    const int n = i % NT;
+    out[(int64_t)prow[m] * n_total + n0 + n] =
+        float_to_bf16_bits(lds.c_buf[n][m]);
+  }
+}
+
+// Routed grouped W4A16 GEMM over the local experts of an MoE block:
+//   for e < E_local, i < counts[e], p = pairs[e][i]:
+//     out[p, :] = a[p / src_div, :] @ dequant(W[e])^T
+// grid = (N/(64*NW), E_local, slabs); a workgroup takes entries
+// [64*z, 64*z + 64) of its expert's list and returns before any other load
+// when the list is shorter. The grid depends on (N, E_local, max_rows) only,
+// never on the routing, so the launch is capturable.
+// The live rows of a slab are a run-time number (1..8 per expert at decode
+// while max_rows is the batch size), so the body is instantiated for
+// MT = 1..4 and picked once at the top by mt = ceil(rows / 16), uniform over
+// the workgroup: nothing inside the chunk loop branches (a branch around the
+// W loads breaks the vmcnt counting, profiles/w4_gemm.md section 2). The
+// register allocation is that of MT = 4 for every mt.
+// Every index read from memory is clamped to the extents the host passed
+// (counts to t_cols, pair indices to n_pairs), so no table content can send a
+// load or a store out of bounds.
+template <int NW, int PF>
+__global__ __launch_bounds__(256) void w4_moe_gemm_kernel(
+    bf16* __restrict__ out,              // [n_pairs, N]
+    const bf16* __restrict__ a,          // [>= ceil(n_pairs / src_div), K]
+    const uint32_t* __restrict__ qw,     // [E, N, K/8]
+    const uint16_t* __restrict__ scales, // [E, K/128, N] f16
+    const uint8_t* __restrict__ zeros,   // [E, K/128, N]
+    const int* __restrict__ counts,      // [E]
+    const int* __restrict__ pairs,       // [E, t_cols]
+    const int t_cols, const int n_pairs, const int src_div,
+    const int n_total, const int k_total) {
+  const int e = blockIdx.y;
+  const int cnt = min(max(counts[e], 0), t_cols);
+  const int r0 = blockIdx.z * 64;
+  if (r0 >= cnt) return;  // uniform
+  const int rows = min(cnt - r0, 64);
+
+  __shared__ __attribute__((aligned(16))) union {
+    struct {
+      bf16 a_buf[2][64][W4_KC + W4_AP];
+      float asum[2][64];
+    } s;
+    float c_buf[64 * NW][64 + 1];
+  } lds;
+  __shared__ int prow[64];
+  if (threadIdx.x < 64) {
+    const int p = pairs[(int64_t)e * t_cols + r0 + min((int)threadIdx.x,
+                                                       rows - 1)];
+    prow[threadIdx.x] = min(max(p, 0), n_pairs - 1);
+  }
+  __syncthreads();
+
+  const int64_t wq = (int64_t)e * n_total * (k_total / 8);
+  const int64_t wg = (int64_t)e * (k_total / W4_KC) * n_total;
+#define ARKS_W4_MOE_SLAB(MT)                                                 \
+  w4_moe_slab<MT, NW, PF>(lds, prow, out, a, qw + wq, scales + wg,           \
+                          zeros + wg, rows, src_div, n_total, k_total)
+  switch ((rows + 15) / 16) {
+    case 1: ARKS_W4_MOE_SLAB(1); break;
+    case 2: ARKS_W4_MOE_SLAB(2); break;
+    case 3: ARKS_W4_MOE_SLAB(3); break;
+    default: ARKS_W4_MOE_SLAB(4); break;
+  }
+#undef ARKS_W4_MOE_SLAB
+}
+
 // out[n][8c..8c+7] = bf16((q - z) * s): one packed word per thread, one 16 B
 // store. (q - z) * s is exact in f32 (5-bit integer times an 11-bit
 // mantissa), so the result is the RNE bf16 rounding of the true value.
@@ -382,6 +604,27 @@ extern "C" void arks_w4_skinny_gemm(void* part, void* out, const void* a,
   if (nsplits > 1 && combine)
     arks_skinny_combine(out, part, bias, m_rows, n_total, nsplits,
                         arks_w4_slab_rows(m_rows), stream);
+}
+
+// nw = 64-row N sub-tiles per workgroup (1 or 2); slabs = ceil(max_rows/64).
+extern "C" void arks_w4_moe_gemm(void* out, const void* a, const void* qw,
+                                 const void* scales, const void* zeros,
+                                 const void* counts, const void* pairs,
+                                 int n_experts, int t_cols, int n_pairs,
+                                 int src_div, int slabs, int n_total,
+                                 int k_total, int nw, hipStream_t stream) {
+  dim3 grid(n_total / (64 * nw), n_experts, slabs), block(256);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, (bf16*)out,
+                       (const bf16*)a, (const uint32_t*)qw,
+                       (const uint16_t*)scales, (const uint8_t*)zeros,
+                       (const int*)counts, (const int*)pairs, t_cols, n_pairs,
+                       src_div, n_total, k_total);
+  };
+  if (nw == 2)
+    launch(w4_moe_gemm_kernel<2, 1>);
+  else
+    launch(w4_moe_gemm_kernel<1, 1>);
 }
 
 extern "C" void arks_w4_dequant(void* out, const void* qw, const void* scales,

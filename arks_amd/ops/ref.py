@@ -498,6 +498,47 @@ def w4_linear(x: torch.Tensor, packed, bias=None) -> torch.Tensor:
     return torch.nn.functional.linear(x, w, bias)
 
 
+def moe_route(ids: torch.Tensor, expert_base: int, n_local: int):
+    """Routing table of the W4 expert GEMM from ids [T, k] (global expert
+    ids): counts int32 [n_local] and pairs int32 [n_local, T], where expert
+    e's first counts[e] entries are the pair indices p = t*k + j routed to
+    expert_base + e, ascending. Entries past counts[e] are 0 here and
+    unspecified in general."""
+    T = ids.shape[0]
+    flat = ids.reshape(-1)
+    counts = torch.zeros(n_local, dtype=torch.int32, device=ids.device)
+    pairs = torch.zeros(n_local, T, dtype=torch.int32, device=ids.device)
+    for e in range(n_local):
+        p = torch.nonzero(flat == expert_base + e).reshape(-1)[:T]
+        counts[e] = p.numel()
+        pairs[e, :p.numel()] = p.to(torch.int32)
+    return counts, pairs
+
+
+def w4_moe_gemm(a: torch.Tensor, packed, counts: torch.Tensor,
+                pairs: torch.Tensor, src_div: int, out=None) -> torch.Tensor:
+    """out[p] = a[p // src_div] @ dequant(W[e])^T for every local expert e
+    and p in pairs[e][:counts[e]]: a plain loop over experts on the
+    dequantized weights (f32 accumulate, one rounding to a's dtype). packed
+    is the stacked triple (qweight [E, N, K/8], scales [E, K/128, N], zeros
+    [E, K/128, N]). Rows of `out` that no local expert owns are left as they
+    are (zeros when out is None)."""
+    qweight, scales, zeros = packed
+    E, N = qweight.shape[0], qweight.shape[1]
+    T = pairs.shape[1]
+    n_pairs = T * (a.shape[0] * src_div // T)
+    if out is None:
+        out = torch.zeros(n_pairs, N, dtype=a.dtype, device=a.device)
+    for e in range(E):
+        p = pairs[e, :int(counts[e])].long()
+        if p.numel() == 0:
+            continue
+        w = w4_dequant(*w4_unpack((qweight[e], scales[e], zeros[e])))
+        src = torch.div(p, src_div, rounding_mode="floor")
+        out[p] = (a[src].float() @ w.t()).to(out.dtype)
+    return out
+
+
 def awq_unpack(qweight: torch.Tensor, qzeros: torch.Tensor,
                scales: torch.Tensor):
     """AutoAWQ "GEMM" on-disk layout -> (q [N, K], z [N, K/128], s [N, K/128]).

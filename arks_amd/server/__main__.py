@@ -38,6 +38,9 @@ def parse_args(argv=None):
                    default=None,
                    help="fp8: W8A8; int4: 4-bit round-to-nearest at load; "
                         "awq: a 4-bit AWQ checkpoint (also auto-detected)")
+    p.add_argument("--quantize-experts", action="store_true",
+                   help="with --quantization int4 on an MoE model: also "
+                        "quantize the routed and shared experts")
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--speculative", choices=["ngram", "draft"], default=None,
                    help="speculative decoding: ngram (prompt lookup) or "
@@ -97,6 +100,7 @@ def build_engine_config(args):
         kv_cache_blocks=args.kv_cache_blocks,
         enforce_eager=args.enforce_eager,
         quantization=args.quantization,
+        quantize_experts=args.quantize_experts,
         kv_cache_dtype=args.kv_cache_dtype,
         speculative=args.speculative,
         draft_model=args.draft_model,
