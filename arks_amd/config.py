@@ -13,6 +13,14 @@ import os
 from dataclasses import dataclass
 
 
+_BASE_MODEL_ARCHS = {
+    "Qwen3Model": "Qwen3ForCausalLM",
+    "Qwen2Model": "Qwen2ForCausalLM",
+    "MistralModel": "MistralForCausalLM",
+    "LlamaModel": "LlamaForCausalLM",
+}
+
+
 @dataclass
 class ModelConfig:
     architecture: str = "Qwen2ForCausalLM"
@@ -115,6 +123,10 @@ class ModelConfig:
     @classmethod
     def from_hf_config(cls, cfg: dict) -> "ModelConfig":
         arch = (cfg.get("architectures") or ["Qwen2ForCausalLM"])[0]
+        # base-model checkpoints (embedding models: Qwen3-Embedding ships as
+        # Qwen3Model, e5-mistral as MistralModel) are the same decoder stack
+        # without the lm_head
+        arch = _BASE_MODEL_ARCHS.get(arch, arch)
         num_heads = cfg.get("num_attention_heads", 28)
         hidden = cfg.get("hidden_size", 3584)
         eos = cfg.get("eos_token_id", 151645)
@@ -541,6 +553,8 @@ class EngineConfig:
     # path; must share the target's tokenizer/vocab)
     draft_model: str | None = None
     device: str = "cuda"
+    # "float32" runs the CPU reference path in fp32 (device="cpu" only: the
+    # kernels are bf16); anything else is bf16
     dtype: str = "bfloat16"
     seed: int = 0
     # multi-LoRA serving (off by default): PEFT adapters of the base model
@@ -555,6 +569,11 @@ class EngineConfig:
     # states, and rows of the device-resident mask pool ([slots, V/32])
     structured_max_states: int = 20000
     structured_mask_slots: int = 512
+    # embedding requests: default pooling ("auto" | "last" | "mean" | "cls")
+    # and L2 normalisation ("auto" | "true" | "false"); auto reads the
+    # checkpoint's sentence-transformers settings, else last + normalise
+    pooling: str = "auto"
+    embedding_normalize: str = "auto"
 
     def __post_init__(self):
         if self.quantization not in (None, "fp8", "int4", "awq"):

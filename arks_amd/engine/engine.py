@@ -40,6 +40,12 @@ class LLMEngine:
         for name, path in (cfg.lora_modules or {}).items():
             self.load_lora(name, path)
         self.load_seconds = time.time() - t0
+        # what an embedding request without its own pooling spec gets: the
+        # checkpoint's sentence-transformers settings, overridden by cfg
+        from ..loader.pooling_config import resolve_default_pooling
+
+        self.default_pooling = resolve_default_pooling(
+            cfg.model_path, cfg.pooling, cfg.embedding_normalize)
         allocator = self.runner.init_kv_cache()
         self.scheduler = Scheduler(
             allocator,
@@ -77,8 +83,27 @@ class LLMEngine:
         arrival_time: float | None = None,
         hold_pages: bool = False,
         lora: str | None = None,
+        pooling: dict | None = None,
     ) -> Sequence:
-        seq = Sequence(prompt_token_ids, sampling, request_id, arrival_time)
+        """pooling = {"mode": "last"|"mean"|"cls", "normalize": bool,
+        "dims": int|None} makes this an embedding request: it finishes after
+        prefill with no output token and its StepOutput carries the vector."""
+        if pooling is not None:
+            if hold_pages:
+                raise ValueError("an embedding request holds no pages")
+            dims = pooling.get("dims")
+            if isinstance(dims, int) and dims > self.model_cfg.hidden_size:
+                raise ValueError(
+                    f"pooling dims {dims} exceeds the model's hidden size "
+                    f"{self.model_cfg.hidden_size}")
+            if not prompt_token_ids:
+                raise ValueError("an embedding request needs at least one token")
+        elif not self.can_generate:
+            raise ValueError(
+                "this model is an embedding checkpoint (no lm_head): it "
+                "serves embeddings only, not generation")
+        seq = Sequence(prompt_token_ids, sampling, request_id, arrival_time,
+                       pooling=pooling)
         self._attach_matcher(seq)
         seq.hold_pages = hold_pages
         if lora is not None:
@@ -149,7 +174,15 @@ class LLMEngine:
         return list(self.runner.lora_slots)
 
     def abort_request(self, request_id: str) -> bool:
+        for s in self.scheduler.waiting:  # a chunked mean-pooled prefill
+            if s.request_id == request_id and s.pooling is not None:
+                self.runner.release_pool_slot(s)
         return self.scheduler.abort(request_id)
+
+    @property
+    def can_generate(self) -> bool:
+        """False for an embedding checkpoint, which has no lm_head."""
+        return getattr(self.runner.model, "has_lm_head", True)
 
     # ---- prefill/decode disaggregation ----
     def extract_prefilled(self, request_id: str):
@@ -226,6 +259,25 @@ class LLMEngine:
         eos = self.model_cfg.eos_token_id
         for i, (seq, tok) in enumerate(zip(sb.seqs, new_tokens)):
             if seq.status is not SeqStatus.RUNNING:  # aborted mid-step
+                continue
+            if seq.pooling is not None:
+                # embedding request: RUNNING means this chunk covered its
+                # last prompt token, so it is done, with no output token
+                seq.status = SeqStatus.FINISHED
+                seq.finish_reason = "stop"
+                seq.finish_time = time.time()
+                outputs.append(
+                    StepOutput(
+                        request_id=seq.request_id,
+                        seq_id=seq.seq_id,
+                        new_token_id=-1,
+                        finished=True,
+                        finish_reason=seq.finish_reason,
+                        num_prompt_tokens=seq.num_prompt_tokens,
+                        num_output_tokens=0,
+                        embedding=seq.embedding,
+                    )
+                )
                 continue
             seq.append_token(tok)
             self.total_output_tokens += 1
@@ -386,3 +438,18 @@ class LLMEngine:
         while self.has_work():
             self.step()
         return [s.output_token_ids for s in seqs]
+
+    def embed(
+        self, prompts: list[list[int]], pooling: dict | None = None,
+        lora: list[str | None] | None = None,
+    ) -> list:
+        """Embeddings (np.float32 [dims]) of token-id prompts; pooling
+        defaults to the checkpoint's (default_pooling)."""
+        spec = dict(self.default_pooling)
+        spec.update(pooling or {})
+        loras = lora or [None] * len(prompts)
+        seqs = [self.add_request(p, lora=l, pooling=spec)
+                for p, l in zip(prompts, loras)]
+        while self.has_work():
+            self.step()
+        return [s.embedding for s in seqs]

@@ -41,7 +41,12 @@ class ModelRunner:
             engine_cfg.device if torch.cuda.is_available() or engine_cfg.device == "cpu"
             else "cpu"
         )
-        self.dtype = torch.bfloat16
+        # the kernels are bf16; float32 is the CPU reference path's second
+        # dtype (parity tests against fp32 oracles)
+        if engine_cfg.dtype == "float32" and self.device.type != "cpu":
+            raise ValueError("dtype='float32' runs on device='cpu' only")
+        self.dtype = (torch.float32 if engine_cfg.dtype == "float32"
+                      else torch.bfloat16)
         torch.manual_seed(engine_cfg.seed)
         self._setup_tunableop()
         from ..models import create_model  # lazy: breaks the import cycle
@@ -58,6 +63,13 @@ class ModelRunner:
         self.lora_bytes = 0
         self._graph_pool = None
         self._graph_bufs: dict | None = None
+        # embedding requests: the fp32 [max_num_seqs, H] carry pool of
+        # mean-pooled sequences whose prompt spans several prefill chunks
+        # (allocated on first use), seq_id -> its row, and the free rows
+        self._pool_carry: torch.Tensor | None = None
+        self._pool_slots: dict[int, int] = {}
+        self._pool_free: list[int] = []
+        self._pool_batch: list = []
         self.use_graphs = (
             self.device.type == "cuda" and not engine_cfg.enforce_eager
         )
@@ -95,6 +107,9 @@ class ModelRunner:
             from ..loader.safetensors_loader import load_model_weights
 
             load_model_weights(self.model, self.cfg.model_path, self.device)
+            # neither lm_head.weight nor tied embeddings: an embedding
+            # checkpoint, whose (uninitialised) head must never be sampled
+            self.model.has_lm_head = self.model._lm_head_loaded
         else:
             # move first so random-init generates directly on the GPU
             self.model.to(self.device)
@@ -262,6 +277,7 @@ class ModelRunner:
             kv_lens: list[int] = []
             logits_idx: list[int] = []
             lp_meta: list[tuple[int, int, int, int]] = []
+            pool_segs: list = []
             self._lp_prefill = None
             import numpy as np
 
@@ -281,7 +297,10 @@ class ModelRunner:
                 cu.append(cu[-1] + (n - c))
                 q_lens.append(n - c)
                 kv_lens.append(n)
-                if seq.sampling.prompt_logprobs and c < seq.num_prompt_tokens:
+                if seq.pooling is not None:
+                    # embedding request: no logits row; its rows are pooled
+                    self._add_pool_segment(pool_segs, i, seq, cu[-2], c, n)
+                elif seq.sampling.prompt_logprobs and c < seq.num_prompt_tokens:
                     # echo/prompt-scoring: lm_head on EVERY row of this seq
                     # (sampling still reads the last row — see execute())
                     off = len(logits_idx)
@@ -297,6 +316,8 @@ class ModelRunner:
                 lp_by_seq = {m[0]: m for m in lp_meta}
                 g = 0
                 for i in range(len(sb.seqs)):
+                    if sb.seqs[i].pooling is not None:
+                        continue  # no logits row
                     m = lp_by_seq.get(i)
                     if m is not None:
                         sample_pos.append(g + m[2] - 1)
@@ -305,6 +326,7 @@ class ModelRunner:
                         sample_pos.append(g)
                         g += 1
                 self._lp_prefill = (lp_meta, sample_pos)
+            self._pool_batch = pool_segs
             dev = self.device
             block_tables = None
             seq_lens = None
@@ -490,10 +512,98 @@ class ModelRunner:
             logits = self._graph_decode(sb)
             return self.sample(logits, sb.seqs)
         fb = self.prepare_batch(sb)
-        logits = self.model(fb, self.kv_caches)  # [num_seqs, vocab]
-        if sb.is_prefill and self._lp_prefill is not None:
-            logits = self._finish_prompt_logprobs(logits, sb)
-        return self.sample(logits, sb.seqs)
+        if not sb.is_prefill or not any(s.pooling is not None for s in sb.seqs):
+            logits = self.model(fb, self.kv_caches)  # [num_seqs, vocab]
+            if sb.is_prefill and self._lp_prefill is not None:
+                logits = self._finish_prompt_logprobs(logits, sb)
+            return self.sample(logits, sb.seqs)
+        # embedding requests in the batch: pool their rows from the decoder
+        # stack's output; generation rows then take the usual norm + lm_head
+        # (skipped altogether when every sequence is an embedding request)
+        x, residual = self.model.forward_hidden(fb, self.kv_caches)
+        if isinstance(x, ops.SplitKPending):
+            x = x.materialize()
+        self._run_pooling(x, residual, sb)
+        gen = [s for s in sb.seqs if s.pooling is None]
+        tokens: list[int] = []
+        if gen:
+            logits = self.model.compute_logits(x, residual, fb)
+            if self._lp_prefill is not None:
+                logits = self._finish_prompt_logprobs(logits, sb)
+            tokens = self.sample(logits, gen)
+            if self._last_logprobs:
+                # sample() keys logprobs by row among `gen`: re-key by batch
+                # position, which is what the engine looks up
+                pos = [i for i, s in enumerate(sb.seqs) if s.pooling is None]
+                self._last_logprobs = {pos[k]: v for k, v
+                                       in self._last_logprobs.items()}
+        it = iter(tokens)
+        return [next(it) if s.pooling is None else -1 for s in sb.seqs]
+
+    # ---------------- embedding requests ----------------
+    def _pool_slot(self, seq: Sequence) -> int:
+        slot = self._pool_slots.get(seq.seq_id)
+        if slot is None:
+            if self._pool_carry is None:
+                self._pool_carry = torch.zeros(
+                    (self.cfg.max_num_seqs, self.model_cfg.hidden_size),
+                    dtype=torch.float32, device=self.device)
+                self._pool_free = list(range(self.cfg.max_num_seqs))[::-1]
+            if not self._pool_free:
+                raise RuntimeError("no free pooling accumulator slot")
+            slot = self._pool_slots[seq.seq_id] = self._pool_free.pop()
+        return slot
+
+    def release_pool_slot(self, seq: Sequence) -> None:
+        """Give back the accumulator row of a finished or aborted sequence."""
+        slot = self._pool_slots.pop(seq.seq_id, None)
+        if slot is not None:
+            self._pool_free.append(slot)
+
+    def _add_pool_segment(self, segs: list, i: int, seq: Sequence, row0: int,
+                          c: int, n: int) -> None:
+        """The pooling segment, if any, that prefill rows [c, n) of `seq`
+        (packed from row0) contribute: (batch index, table entry)."""
+        mode = seq.pooling["mode"]
+        final = n >= seq.num_tokens
+        if mode == "last":
+            if final:
+                segs.append((i, (row0, n - c, "last", -1, 0, 1)))
+        elif mode == "cls":
+            if c == 0:  # the vector waits on the sequence until it finishes
+                segs.append((i, (row0, n - c, "cls", -1, 0, 1)))
+        else:
+            # c == 0 restarts the sum (first chunk, or a recomputed prefill)
+            slot = self._pool_slot(seq) if (c > 0 or not final) else -1
+            segs.append((i, (row0, n - c, "mean", slot, c, int(final))))
+
+    def _run_pooling(self, x, residual, sb: ScheduledBatch) -> None:
+        """Pool this batch's segments (one pool_embed call per distinct
+        (dims, normalize), usually one) and bring the finished vectors to the
+        host in a single copy; each lands on its sequence's `embedding`."""
+        groups: dict = {}
+        for i, seg in self._pool_batch:
+            p = sb.seqs[i].pooling
+            groups.setdefault((p["dims"], p["normalize"]), []).append((i, seg))
+        self._pool_batch = []
+        outs, owners = [], []
+        for (dims, normalize), items in groups.items():
+            table = ops.build_pool_table([seg for _, seg in items], self.device)
+            out = self.model.pool(x, residual, table, self._pool_carry, dims,
+                                  normalize)
+            for k, (i, seg) in enumerate(items):
+                if seg[5]:  # final: the vector is due
+                    outs.append(out[k])
+                    owners.append(sb.seqs[i])
+        if not outs:
+            return
+        host = torch.cat(outs).cpu().numpy()  # the step's one D2H copy
+        off = 0
+        for seq, o in zip(owners, outs):
+            seq.embedding = host[off:off + o.numel()].copy()
+            off += o.numel()
+            if seq.pooling["mode"] == "mean":
+                self.release_pool_slot(seq)
 
     _lp_prefill: tuple | None = None
 

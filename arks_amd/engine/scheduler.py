@@ -143,7 +143,11 @@ class Scheduler:
                 # path). Cap at n-1 so at least one token produces logits.
                 # prompt_logprobs needs logits at EVERY prompt position, so
                 # those requests skip prefix reuse and recompute in full.
-                if seq.sampling.prompt_logprobs:
+                # mean/cls pooling reads every prompt row, likewise; last
+                # pooling needs only the final row, which the cap keeps.
+                if seq.sampling.prompt_logprobs or (
+                        seq.pooling is not None
+                        and seq.pooling["mode"] != "last"):
                     reused, ncached = [], 0
                 else:
                     reused, ncached = self.allocator.match_prefix(

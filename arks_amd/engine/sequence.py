@@ -35,6 +35,28 @@ class SamplingParams:
                 or self.repetition_penalty != 1.0)
 
 
+POOLING_MODES = ("last", "mean", "cls")
+
+
+def check_pooling(pooling: dict | None) -> dict | None:
+    """Validated copy of a pooling spec with every field present."""
+    if pooling is None:
+        return None
+    unknown = set(pooling) - {"mode", "normalize", "dims"}
+    if unknown:
+        raise ValueError(f"unknown pooling fields {sorted(unknown)}")
+    mode = pooling.get("mode", "last")
+    if mode not in POOLING_MODES:
+        raise ValueError(
+            f"pooling mode must be one of {POOLING_MODES}, got {mode!r}")
+    dims = pooling.get("dims")
+    if dims is not None and (isinstance(dims, bool) or not isinstance(dims, int)
+                             or dims < 1):
+        raise ValueError(f"pooling dims must be a positive integer, got {dims!r}")
+    return {"mode": mode, "normalize": bool(pooling.get("normalize", True)),
+            "dims": dims}
+
+
 class SeqStatus(enum.Enum):
     WAITING = "waiting"
     RUNNING = "running"
@@ -54,6 +76,7 @@ class Sequence:
         sampling: SamplingParams | None = None,
         request_id: str | None = None,
         arrival_time: float | None = None,
+        pooling: dict | None = None,
     ):
         Sequence._counter += 1
         self.seq_id = Sequence._counter
@@ -73,6 +96,12 @@ class Sequence:
         # structured outputs: the GrammarMatcher the engine attaches when
         # sampling.structured is set; advanced by every appended token
         self.matcher = None
+        # embedding request: {"mode": "last"|"mean"|"cls", "normalize": bool,
+        # "dims": int|None} (None = a generation request). Plain data, like
+        # sampling.structured. Such a sequence finishes after the prefill
+        # chunk that covers its last prompt token, with no output token.
+        self.pooling = check_pooling(pooling)
+        self.embedding = None  # np.float32 [dims], set when it is computed
         self.num_cached_tokens = 0  # tokens whose KV is already in cache
         # prompt-token logprobs (sampling.prompt_logprobs): value at index
         # q-1 scores prompt token q given tokens < q (first token unscored)
@@ -148,3 +177,6 @@ class StepOutput:
     top_logprobs: dict[int, float] | None = None
     # prompt-token logprobs (echo): set on the sequence's FIRST output
     prompt_logprobs: list[float] | None = None
+    # embedding requests: the pooled vector (np.float32 [dims]); such an
+    # output has new_token_id -1 and no output tokens
+    embedding: object | None = None

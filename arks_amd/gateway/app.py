@@ -386,6 +386,8 @@ def create_gateway_app(
         routes=[
             Route("/v1/chat/completions", proxy, methods=["POST"]),
             Route("/v1/completions", proxy, methods=["POST"]),
+            # usage carries no completion_tokens: accounted as 0
+            Route("/v1/embeddings", proxy, methods=["POST"]),
             Route("/v1/models", models, methods=["GET"]),
             Route("/metrics", metrics_ep, methods=["GET"]),
             Route("/health", health, methods=["GET"]),

@@ -607,6 +607,10 @@ class LlamaFamilyForCausalLM(nn.Module):
         )
         self.norm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, dtype)
         self.lm_head = ParallelLMHead(cfg.hidden_size, cfg.vocab_size, dtype)
+        # False once a checkpoint turned out to carry no lm_head.weight and
+        # no tied embeddings (an embedding model): pooling only
+        self.has_lm_head = True
+        self._lm_head_loaded = False
         cos_sin = self._build_cos_sin()
         self.register_buffer("rope_cos_sin", cos_sin, persistent=False)
         for layer in self.layers:
@@ -764,10 +768,31 @@ class LlamaFamilyForCausalLM(nn.Module):
 
     def forward(self, batch: ForwardBatch, kv_caches: list) -> torch.Tensor:
         """Returns logits for batch.logits_indices rows."""
+        x, residual = self.forward_hidden(batch, kv_caches)
+        return self.compute_logits(x, residual, batch)
+
+    def forward_hidden(self, batch: ForwardBatch, kv_caches: list):
+        """The decoder stack: (x, residual) of the last layer, before the
+        final norm (x may still be an ops.SplitKPending)."""
         x = self.embed_tokens(batch.input_ids)
         residual = None
         for i, layer in enumerate(self.layers):
             x, residual = layer(x, residual, batch, kv_caches[i])
+        return x, residual
+
+    def pool(self, x, residual, table, carry, dims, normalize):
+        """Embeddings of the pooled segments of `table` from forward_hidden's
+        output, which it leaves untouched: call it before compute_logits,
+        whose fused norm adds x into residual in place."""
+        return ops.pool_embed(x, residual, self.norm.weight, self.norm.eps,
+                              table, carry, dims=dims, normalize=normalize)
+
+    def compute_logits(self, x, residual, batch: ForwardBatch) -> torch.Tensor:
+        """Final norm and lm_head over batch.logits_indices rows."""
+        if not self.has_lm_head:
+            raise RuntimeError(
+                "this checkpoint has no lm_head (an embedding model): it "
+                "cannot produce logits")
         x, _ = self.norm(x, residual)
         if isinstance(x, tuple):  # fp8: (values, per-token scales)
             q8, sc = x
@@ -808,8 +833,10 @@ class LlamaFamilyForCausalLM(nn.Module):
                 put("embed_tokens.weight", w)
                 if self.cfg.tie_word_embeddings:
                     put("lm_head.weight", self.lm_head.shard(w))
+                    self._lm_head_loaded = True
             elif name in ("lm_head.weight",):
                 put("lm_head.weight", self.lm_head.shard(w))
+                self._lm_head_loaded = True
             elif name == "norm.weight":
                 put("norm.weight", w)
             elif name.startswith("layers."):

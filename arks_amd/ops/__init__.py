@@ -922,3 +922,124 @@ def apply_token_bitmask(logits, masks, mask_row):
         _native().apply_token_bitmask(logits, masks, mask_row)
         return logits
     return ref.apply_token_bitmask(logits, masks, mask_row)
+
+
+# ---------------------------------------------------------------------------
+# Embedding pooling (pooling.hip; definition in ref.pool_embed)
+# ---------------------------------------------------------------------------
+POOL_MODES = {"last": ref.POOL_LAST, "mean": ref.POOL_MEAN,
+              "cls": ref.POOL_CLS}
+POOL_SLAB_ROWS = 32  # rows per workgroup of the mean kernel (pooling.hip)
+_POOL_WS: dict = {}
+
+
+class PoolTable:
+    """Work table of one pool_embed call: the host list of segments, and on
+    GPU the int32 segment table [S, 8] (row0, nrows, mode, slot, counted,
+    final, first slab, slab count) with the slab table [NS, 4] (row0, nrows,
+    partial row, 0) that cuts every mean segment into POOL_SLAB_ROWS-row
+    slabs at fixed offsets from its first row."""
+
+    __slots__ = ("segments", "segs", "slabs", "max_row", "max_slot")
+
+    def __init__(self, segments, segs, slabs, max_row, max_slot):
+        self.segments = segments
+        self.segs = segs
+        self.slabs = slabs
+        self.max_row = max_row
+        self.max_slot = max_slot
+
+    def __len__(self) -> int:
+        return len(self.segments)
+
+
+def build_pool_table(segments, device=None) -> PoolTable:
+    """Segment table for pool_embed from (row0, nrows, mode, slot, counted,
+    final) entries; mode is "last" / "mean" / "cls". slot is the row of the
+    fp32 carry a mean-pooled sequence accumulates in across prefill chunks
+    (-1 when it needs none: a single final chunk), counted the tokens pooled
+    by its earlier chunks. Packed rows covered by no entry are never read.
+    Build once per batch, on the host, like build_lora_tiles."""
+    host, segs, slabs = [], [], []
+    max_row, max_slot, used = 0, -1, set()
+    for row0, nrows, mode, slot, counted, final in segments:
+        m = POOL_MODES[mode] if isinstance(mode, str) else int(mode)
+        if m not in (ref.POOL_LAST, ref.POOL_MEAN, ref.POOL_CLS):
+            raise ValueError(f"unknown pooling mode {mode!r}")
+        if row0 < 0 or nrows < 1 or counted < 0:
+            raise ValueError(f"bad pooling segment {(row0, nrows, counted)}")
+        final = 1 if final else 0
+        part0 = len(slabs)
+        if m == ref.POOL_MEAN:
+            if counted > 0 or not final:
+                if slot < 0 or slot in used:
+                    raise ValueError(
+                        f"mean segment needs its own carry slot, got {slot}")
+                used.add(slot)
+                max_slot = max(max_slot, slot)
+            for r in range(0, nrows, POOL_SLAB_ROWS):
+                slabs.append((row0 + r, min(POOL_SLAB_ROWS, nrows - r),
+                              len(slabs), 0))
+        elif counted or not final:
+            raise ValueError("last/cls segments are single final chunks")
+        max_row = max(max_row, row0 + nrows)
+        host.append((row0, nrows, m, slot, counted, final))
+        segs.append((row0, nrows, m, slot, counted, final, part0,
+                     len(slabs) - part0))
+    dev = torch.device(device) if device is not None else None
+    if dev is None or dev.type != "cuda":
+        return PoolTable(host, None, None, max_row, max_slot)
+    # one H2D copy for both tables
+    flat = torch.tensor([v for e in segs for v in e]
+                        + [v for e in slabs for v in e],
+                        dtype=torch.int32).to(dev)
+    n = len(segs) * 8
+    return PoolTable(host, flat[:n].view(-1, 8), flat[n:].view(-1, 4),
+                     max_row, max_slot)
+
+
+def pool_embed(x, residual, weight, eps: float, table: PoolTable, carry=None,
+               dims: int | None = None, normalize: bool = True):
+    """Final-norm + pooling + truncation + L2 normalisation of the decoder
+    stack's (x, residual) output, packed rows [T, H]: fp32
+    [num_segments, dims], one vector per entry of `table` (a non-final mean
+    chunk's row is zero; it only updates carry [slots, H] fp32 in place).
+    x and residual are not modified. x may be a SplitKPending (small
+    prefills take the skinny split-K path): it is materialised first.
+    Native on GPU, no fallback; ref.pool_embed on CPU."""
+    if isinstance(x, SplitKPending):
+        x = x.materialize()
+    T, H = x.shape
+    if tuple(residual.shape) != (T, H):
+        raise ValueError(f"residual {tuple(residual.shape)} vs x {(T, H)}")
+    if H % 8 != 0:
+        raise ValueError(f"pool_embed requires H % 8 == 0, got {H}")
+    dims = H if dims is None else int(dims)
+    if not 1 <= dims <= H:
+        raise ValueError(f"dims must be in [1, {H}], got {dims}")
+    if len(table) == 0:
+        raise ValueError("empty pooling table")
+    if table.max_row > T:
+        raise ValueError(f"pooling table covers row {table.max_row}, batch "
+                         f"has {T}")
+    if table.max_slot >= 0 and (carry is None
+                                or table.max_slot >= carry.shape[0]
+                                or carry.shape[1] != H):
+        raise ValueError(f"carry must be fp32 [> {table.max_slot}, {H}]")
+    if not x.is_cuda:
+        return ref.pool_embed(x, residual, weight, eps, table.segments, carry,
+                              dims, normalize)
+    if table.segs is None:
+        raise ValueError("pooling table was built for the CPU")
+    if carry is None:
+        carry = torch.empty((0, H), dtype=torch.float32, device=x.device)
+    need = table.slabs.shape[0] * H
+    key = (x.device.index,)
+    ws = _POOL_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+        _POOL_WS[key] = ws
+    out = torch.empty((len(table), dims), dtype=torch.float32, device=x.device)
+    _native().pool_embed(out, carry, ws, x, residual, weight, table.segs,
+                         table.slabs, eps, dims, bool(normalize))
+    return out

@@ -33,6 +33,7 @@ SOURCES = [
     os.path.join(CSRC, "moe.hip"),
     os.path.join(CSRC, "allreduce.hip"),
     os.path.join(CSRC, "lora.hip"),
+    os.path.join(CSRC, "pooling.hip"),
 ]
 
 

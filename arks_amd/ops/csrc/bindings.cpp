@@ -20,6 +20,12 @@ void arks_fused_add_rmsnorm(void* out, const void* input, void* residual,
                             hipStream_t stream);
 void arks_silu_mul(void* out, const void* gate_up, int64_t rows, int d,
                    hipStream_t stream);
+int arks_pool_max_hidden();
+void arks_pool_embed(void* out, void* carry, void* part, const void* x,
+                     const void* residual, const void* weight,
+                     const void* segs, const void* slabs, int nsegs,
+                     int nslabs, float eps, int hidden, int dims,
+                     int normalize, hipStream_t stream);
 void arks_rope_inplace(const void* positions, void* q, void* k,
                        const void* cos_sin, int num_tokens, int head_dim,
                        int num_q_heads, int num_kv_heads, int64_t q_stride,
@@ -1097,6 +1103,58 @@ void lora_expand(torch::Tensor y, torch::Tensor h, torch::Tensor b,
                    current_stream());
 }
 
+// Embedding pooling (pooling.hip): one f32 vector per row of the segment
+// table. The table's contents are validated where it is built
+// (ops.build_pool_table); here the buffers are checked against its shape.
+void pool_embed(torch::Tensor out, torch::Tensor carry, torch::Tensor part,
+                torch::Tensor x, torch::Tensor residual, torch::Tensor weight,
+                torch::Tensor segs, torch::Tensor slabs, double eps,
+                int64_t dims, bool normalize) {
+  check_bf16_contig(x, "x");
+  check_bf16_contig(residual, "residual");
+  check_bf16_contig(weight, "weight");
+  TORCH_CHECK(x.dim() == 2 && x.sizes() == residual.sizes(),
+              "x and residual are [T, H]");
+  const int64_t H = x.size(1);
+  TORCH_CHECK(H % 8 == 0, "pool_embed requires H % 8 == 0, got ", H);
+  TORCH_CHECK(H <= arks_pool_max_hidden(), "pool_embed supports H <= ",
+              arks_pool_max_hidden(), ", got ", H);
+  TORCH_CHECK(weight.numel() == H, "weight must be [H]");
+  TORCH_CHECK(dims >= 1 && dims <= H, "dims must be in [1, ", H, "], got ",
+              dims);
+  auto i32 = [](const torch::Tensor& t, int64_t cols, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
+                    t.is_contiguous() && t.dim() == 2 && t.size(1) == cols,
+                name, " must be a contiguous int32 [n, ", cols, "] GPU tensor");
+  };
+  i32(segs, 8, "segs");
+  i32(slabs, 4, "slabs");
+  auto f32 = [](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                    t.is_contiguous(),
+                name, " must be a contiguous f32 GPU tensor");
+  };
+  f32(out, "out");
+  f32(carry, "carry");
+  f32(part, "part");
+  const int64_t S = segs.size(0), NS = slabs.size(0);
+  TORCH_CHECK(S >= 1, "empty segment table");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == S && out.size(1) == dims,
+              "out must be [num_segments, dims]");
+  TORCH_CHECK(carry.dim() == 2 && carry.size(1) == H, "carry must be [slots, H]");
+  TORCH_CHECK(part.numel() >= NS * H, "partial workspace too small");
+  check_align16(x, "x");
+  check_align16(residual, "residual");
+  check_align16(weight, "weight");
+  if (NS > 0) check_align16(part, "part");
+  if (carry.numel() > 0) check_align16(carry, "carry");
+  arks_pool_embed(out.data_ptr(), carry.data_ptr(), part.data_ptr(),
+                  x.data_ptr(), residual.data_ptr(), weight.data_ptr(),
+                  segs.data_ptr(), slabs.data_ptr(), (int)S, (int)NS,
+                  (float)eps, (int)H, (int)dims, normalize ? 1 : 0,
+                  current_stream());
+}
+
 void mfma_probe(torch::Tensor d, torch::Tensor a, torch::Tensor b) {
   check_bf16_contig(a, "a");
   check_bf16_contig(b, "b");
@@ -1154,6 +1212,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_mix_rows", &moe_mix_rows);
   m.def("lora_shrink", &lora_shrink);
   m.def("lora_expand", &lora_expand);
+  m.def("pool_embed", &pool_embed);
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma_probe32", &mfma_probe32);
   m.def("tr16_probe", &tr16_probe);

@@ -561,3 +561,53 @@ def awq_pack(q: torch.Tensor, z: torch.Tensor, s: torch.Tensor):
     return (_pack_nibbles(q.t().contiguous()),
             _pack_nibbles(z.t().contiguous()),
             s.t().contiguous().to(torch.float16))
+
+
+POOL_LAST, POOL_MEAN, POOL_CLS = 0, 1, 2
+
+
+def pool_embed(x, residual, weight, eps, segments, carry=None,
+               dims: int | None = None, normalize: bool = True):
+    """Embedding pooling over packed rows [T, H]: one fp32 vector per entry
+    of `segments`, a list of (row0, nrows, mode, slot, counted, final).
+    For a segment of rows [a, b):
+      r_i = (x_i + residual_i) rounded to the input dtype (the rounding
+            fused_add_rmsnorm gives the residual stream);
+      y_i = r_i * rsqrt(mean(r_i^2) + eps) * w, in fp32, never rounded;
+      last: v = y_{b-1}; cls: v = y_a; mean: v = (carry + sum y_i) / count,
+      where carry [slots, H] fp32 holds the sum over the `counted` tokens of
+      earlier prefill chunks (ignored when counted == 0) and count =
+      counted + nrows. A non-final mean chunk only writes the updated carry
+      (its output row is zero).
+    v is cut to v[:dims] and, with normalize, divided by max(|v|_2, 1e-12).
+    Returns fp32 [num_segments, dims]; x and residual are not modified."""
+    H = x.shape[-1]
+    dims = H if dims is None else dims
+    if not 1 <= dims <= H:
+        raise ValueError(f"dims must be in [1, {H}], got {dims}")
+    wf = weight.float()
+    out = torch.zeros((len(segments), dims), dtype=torch.float32,
+                      device=x.device)
+
+    def normed(rows):
+        r = (x[rows].float() + residual[rows].float()).to(x.dtype).float()
+        var = r.pow(2).mean(dim=-1, keepdim=True)
+        return r * torch.rsqrt(var + eps) * wf
+
+    for s, (row0, nrows, mode, slot, counted, final) in enumerate(segments):
+        if mode == POOL_MEAN:
+            v = normed(slice(row0, row0 + nrows)).sum(dim=0)
+            if counted > 0:
+                v = carry[slot] + v
+            if not final:
+                carry[slot] = v
+                continue
+            v = v / float(counted + nrows)
+        else:
+            row = row0 + nrows - 1 if mode == POOL_LAST else row0
+            v = normed(slice(row, row + 1))[0]
+        v = v[:dims]
+        if normalize:
+            v = v / v.norm().clamp_min(1e-12)
+        out[s] = v
+    return out

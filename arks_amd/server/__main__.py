@@ -61,6 +61,15 @@ def parse_args(argv=None):
     p.add_argument("--max-loras", type=int, default=4)
     p.add_argument("--max-lora-rank", type=int, default=16,
                    choices=[16, 32, 64])
+    # embedding requests (/v1/embeddings)
+    p.add_argument("--pooling", choices=["auto", "last", "mean", "cls"],
+                   default="auto",
+                   help="embedding pooling; auto reads the checkpoint's "
+                        "sentence-transformers settings, else last token")
+    p.add_argument("--embedding-normalize", choices=["auto", "true", "false"],
+                   default="auto",
+                   help="L2-normalise embeddings; auto follows the checkpoint "
+                        "(a Normalize module), else true")
     # multi-node group flags (LWS leader/worker topology): workers join the
     # leader's torch.distributed rendezvous
     p.add_argument("--leader-address", default=None)
@@ -110,6 +119,8 @@ def build_engine_config(args):
         max_loras=args.max_loras,
         max_lora_rank=args.max_lora_rank,
         lora_modules=lora_modules,
+        pooling=args.pooling,
+        embedding_normalize=args.embedding_normalize,
     )
 
 

@@ -33,6 +33,10 @@ from .openai_types import (
     CompletionChoice,
     CompletionRequest,
     CompletionResponse,
+    EmbeddingData,
+    EmbeddingRequest,
+    EmbeddingResponse,
+    EmbeddingUsage,
     ErrorResponse,
     ModelCard,
     ModelList,
@@ -113,6 +117,38 @@ def _structured_of(req) -> dict | None:
         raise ValueError("at most one of response_format, guided_json, "
                          "guided_regex and guided_choice may be given")
     return specs[0] if specs else None
+
+
+MAX_EMBEDDING_INPUTS = 2048  # OpenAI's documented cap on items per request
+
+
+def _embedding_items(inp, tokenizer) -> list[list[int]]:
+    """Token lists of an embeddings `input` (a string, strings, token ids or
+    lists of token ids). ValueError names what is wrong."""
+    if isinstance(inp, str):
+        items = [inp]
+    elif inp and all(isinstance(t, int) and not isinstance(t, bool)
+                     for t in inp):
+        items = [list(inp)]
+    else:
+        items = list(inp)
+    if not items:
+        raise ValueError("input must not be empty")
+    if len(items) > MAX_EMBEDDING_INPUTS:
+        raise ValueError(f"input has {len(items)} items; at most "
+                         f"{MAX_EMBEDDING_INPUTS} are accepted per request")
+    out = []
+    for i, item in enumerate(items):
+        if isinstance(item, str):
+            # the default adds the checkpoint's special tokens (Qwen3-
+            # Embedding relies on its trailing EOS)
+            ids = tokenizer.encode(item)
+        else:
+            ids = list(item)
+        if not ids:
+            raise ValueError(f"input {i} is empty")
+        out.append(ids)
+    return out
 
 
 def _error(status: int, message: str) -> JSONResponse:
@@ -242,10 +278,77 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
         text = text_acc if stops else tokenizer.decode(out_ids)
         return out_ids, text, finish or "stop", len(out_ids)
 
+    def _can_generate() -> bool:
+        return getattr(getattr(engine, "engine", None), "can_generate", True)
+
+    NO_HEAD = ("this model is an embedding checkpoint (it has no lm_head): "
+               "it serves /v1/embeddings only")
+
+    @app.post("/v1/embeddings")
+    async def embeddings(req: EmbeddingRequest, raw: Request):
+        if not _known_model(req.model):
+            return _error(404, f"model {req.model!r} not found")
+        if disagg_mode == "decode":
+            return _error(400, "a --disaggregation-mode decode server does "
+                               "not serve embeddings")
+        try:
+            items = _embedding_items(req.input, tokenizer)
+        except ValueError as e:
+            return _error(400, str(e))
+        vocab = engine.model_cfg.vocab_size
+        for i, ids in enumerate(items):
+            if len(ids) > engine.cfg.max_model_len:
+                return _error(400, f"input {i} is {len(ids)} tokens; "
+                                   f"max_model_len is {engine.cfg.max_model_len}")
+            if any(t < 0 or t >= vocab for t in ids):
+                return _error(400, f"input {i} has a token id outside "
+                                   f"[0, {vocab})")
+        hidden = engine.model_cfg.hidden_size
+        if req.dimensions is not None and not 1 <= req.dimensions <= hidden:
+            return _error(400, f"dimensions must be in [1, {hidden}], got "
+                               f"{req.dimensions}")
+        pooling = dict(engine.engine.default_pooling)
+        pooling["dims"] = req.dimensions
+        rid = f"embd-{uuid.uuid4().hex}"
+        task = asyncio.ensure_future(
+            engine.embed(rid, items, pooling, lora=_lora_of(req.model)))
+        try:
+            while not task.done():
+                # a client that went away aborts the outstanding items
+                if await raw.is_disconnected():
+                    task.cancel()
+                    break
+                await asyncio.wait([task], timeout=0.25)
+            vectors = await task
+        except asyncio.CancelledError:
+            task.cancel()
+            raise
+        except ValueError as e:
+            return _error(400, str(e))
+        if req.encoding_format == "base64":
+            import base64
+
+            import numpy as np
+
+            payload = [base64.b64encode(
+                np.ascontiguousarray(v, dtype="<f4").tobytes()).decode()
+                for v in vectors]
+        else:
+            payload = [v.tolist() for v in vectors]
+        n = sum(len(ids) for ids in items)
+        return EmbeddingResponse(
+            data=[EmbeddingData(index=i, embedding=e)
+                  for i, e in enumerate(payload)],
+            model=req.model,
+            usage=EmbeddingUsage(prompt_tokens=n, total_tokens=n),
+        ).model_dump()
+
     @app.post("/v1/chat/completions")
     async def chat_completions(req: ChatCompletionRequest, raw: Request):
         if not _known_model(req.model):
             return _error(404, f"model {req.model!r} not found")
+        if not _can_generate():
+            return _error(400, NO_HEAD)
         prompt = tokenizer.apply_chat_template([m.model_dump() for m in req.messages])
         token_ids = tokenizer.encode(prompt)
         if len(token_ids) > engine.cfg.max_model_len:
@@ -420,6 +523,8 @@ def create_app(engine: AsyncEngine, served_model_name: str, tokenizer,
     async def completions(req: CompletionRequest, raw: Request):
         if not _known_model(req.model):
             return _error(404, f"model {req.model!r} not found")
+        if not _can_generate():
+            return _error(400, NO_HEAD)
         # normalize prompt to a single token list (n=1, single prompt v0)
         p = req.prompt
         if isinstance(p, list) and p and isinstance(p[0], int):

@@ -32,6 +32,7 @@ class RequestAdd:
     sampling: dict  # SamplingParams fields (picklable for broadcast)
     hold_pages: bool = False  # disaggregated prefill: keep pages for extract
     lora: str | None = None  # adapter name (TP workers admit identically)
+    pooling: dict | None = None  # embedding request (Sequence.pooling)
 
 
 def apply_msg(engine: LLMEngine, msg: dict) -> list[str]:
@@ -44,6 +45,7 @@ def apply_msg(engine: LLMEngine, msg: dict) -> list[str]:
             engine.add_request(
                 add.token_ids, SamplingParams(**add.sampling), add.request_id,
                 hold_pages=add.hold_pages, lora=add.lora,
+                pooling=add.pooling,
             )
         except ValueError:
             rejected.append(add.request_id)
@@ -126,7 +128,8 @@ class AsyncEngine:
     # ---- request API ----
     def submit(self, request_id: str, token_ids: list[int],
                sampling: SamplingParams, hold_pages: bool = False,
-               lora: str | None = None) -> _Stream:
+               lora: str | None = None,
+               pooling: dict | None = None) -> _Stream:
         st = _Stream()
         if self.failed is not None:  # engine loop is gone — end immediately
             st.queue.put_nowait(None)
@@ -134,7 +137,7 @@ class AsyncEngine:
         self.streams[request_id] = st
         self.pending_adds.append(
             RequestAdd(request_id, token_ids, sampling.__dict__.copy(),
-                       hold_pages, lora)
+                       hold_pages, lora, pooling)
         )
         self.metrics.prompt_tokens.inc(len(token_ids))
         if self._wakeup:
@@ -264,7 +267,8 @@ class AsyncEngine:
                 else:
                     self.metrics.tpot.observe(now - st.prev_token_time)
                 st.prev_token_time = now
-                self.metrics.generation_tokens.inc()
+                if out.embedding is None:  # an embedding emits no token
+                    self.metrics.generation_tokens.inc()
                 st.queue.put_nowait(out)
                 if out.finished:
                     self.metrics.record_finished(
@@ -296,6 +300,31 @@ class AsyncEngine:
                     self.engine.spec_accepted_tokens
                     - self.metrics.spec_accepted_tokens._value.get()
                 )
+
+    async def embed(self, request_id: str, items: list[list[int]],
+                    pooling: dict, lora: str | None = None) -> list:
+        """Embeddings (np.float32 [dims]) of `items`, submitted together so
+        they share prefill batches and gathered in order. Cancellation (the
+        client went away) aborts whatever is still outstanding. ValueError
+        when the engine rejects an item at admission."""
+        rids = [f"{request_id}-{i}" for i in range(len(items))]
+        streams = [self.submit(rid, ids, SamplingParams(max_tokens=1),
+                               lora=lora, pooling=pooling)
+                   for rid, ids in zip(rids, items)]
+        vectors = []
+        try:
+            for i, st in enumerate(streams):
+                out = await st.queue.get()
+                if out is None:
+                    raise ValueError(f"input {i} was rejected by the engine")
+                await st.queue.get()  # sentinel
+                vectors.append(out.embedding)
+        except BaseException:
+            for rid in rids[len(vectors):]:
+                if rid in self.streams:
+                    self.abort(rid)
+            raise
+        return vectors
 
     async def generate_stream(self, request_id: str, token_ids: list[int],
                               sampling: SamplingParams,

@@ -166,3 +166,31 @@ class ErrorResponse(BaseModel):
     @classmethod
     def make(cls, message: str, code: int, type_: str = "invalid_request_error"):
         return cls(error={"message": message, "type": type_, "code": code})
+
+
+class EmbeddingRequest(BaseModel):
+    model: str
+    # a string, a list of strings, a list of token ids, or a list of lists
+    # of token ids
+    input: str | list[int] | list[list[int]] | list[str]
+    dimensions: int | None = None
+    encoding_format: Literal["float", "base64"] = "float"
+    user: str | None = None  # accepted and ignored
+
+
+class EmbeddingData(BaseModel):
+    object: str = "embedding"
+    index: int
+    embedding: list[float] | str  # base64: little-endian float32 bytes
+
+
+class EmbeddingUsage(BaseModel):
+    prompt_tokens: int
+    total_tokens: int
+
+
+class EmbeddingResponse(BaseModel):
+    object: str = "list"
+    data: list[EmbeddingData]
+    model: str
+    usage: EmbeddingUsage
