@@ -57,9 +57,13 @@ class ModelConfig:
     eos_token_id: int = 151645
     bos_token_id: int = 151643
     torch_dtype: str = "bfloat16"
-    # "awq" when the checkpoint's quantization_config declares 4-bit AWQ
-    # (the only on-disk quantization read); None for plain checkpoints
+    # "awq" when the checkpoint's quantization_config declares 4-bit AWQ,
+    # "fp8_block" when it declares block-scaled FP8 (e4m3, 128x128 blocks,
+    # f32 scales, dynamic activations); None for plain checkpoints
     quant_method: str | None = None
+    # fp8_block: module-name fragments the checkpoint left unquantized
+    # (modules_to_not_convert / ignored_layers)
+    quant_skip_modules: tuple = ()
 
     def __post_init__(self):
         # Sliding-window attention is implemented end to end: the
@@ -105,6 +109,8 @@ class ModelConfig:
         layout; anything else raises naming the offending field."""
         if not qc:
             return None
+        if str(qc.get("quant_method")).lower() == "fp8":
+            return ModelConfig._check_fp8_config(qc)
         want = {"quant_method": "awq", "bits": 4, "group_size": 128,
                 "zero_point": True, "version": "gemm"}
         for field, ok in want.items():
@@ -119,6 +125,52 @@ class ModelConfig:
                     "zero-points, GEMM layout)"
                 )
         return "awq"
+
+    @staticmethod
+    def _check_fp8_config(qc: dict) -> str:
+        """Accepts exactly the block-scaled FP8 format transformers writes
+        ("fine-grained FP8": Qwen3-*-FP8, DeepSeek-V3 style): e4m3 weights,
+        128x128 blocks with f32 scales, dynamic activation scheme; anything
+        else raises naming the offending field."""
+        want = {"fmt": "e4m3", "weight_block_size": [128, 128],
+                "activation_scheme": "dynamic"}
+        for field, ok in want.items():
+            got = qc.get(field)
+            if isinstance(got, str):
+                got = got.lower()
+            if isinstance(got, tuple):
+                got = list(got)
+            if got != ok:
+                raise ValueError(
+                    f"unsupported quantization_config: {field}="
+                    f"{qc.get(field)!r} (only {field}={ok!r} is supported; "
+                    "the engine reads block-scaled FP8 with e4m3 weights, "
+                    "128x128 blocks, f32 scales and dynamic activations)"
+                )
+        scale_fmt = qc.get("scale_fmt")
+        if scale_fmt is not None and str(scale_fmt).lower() != "float":
+            raise ValueError(
+                f"unsupported quantization_config: scale_fmt={scale_fmt!r} "
+                "(only scale_fmt='float' or none is supported; the engine "
+                "reads block-scaled FP8 with f32 scales)"
+            )
+        return "fp8_block"
+
+    @staticmethod
+    def _fp8_skip_modules(qc: dict | None) -> tuple:
+        """modules_to_not_convert and its alias ignored_layers, merged."""
+        if not qc or str(qc.get("quant_method")).lower() != "fp8":
+            return ()
+        out: list[str] = []
+        for key in ("modules_to_not_convert", "ignored_layers"):
+            val = qc.get(key) or []
+            if isinstance(val, str) or not all(isinstance(v, str)
+                                               for v in val):
+                raise ValueError(
+                    f"unsupported quantization_config: {key}={val!r} "
+                    "(expected a list of module names)")
+            out.extend(v for v in val if v not in out)
+        return tuple(out)
 
     @classmethod
     def from_hf_config(cls, cfg: dict) -> "ModelConfig":
@@ -170,6 +222,8 @@ class ModelConfig:
             bos_token_id=cfg.get("bos_token_id", 1),
             torch_dtype=cfg.get("torch_dtype", "bfloat16"),
             quant_method=cls._check_quantization_config(
+                cfg.get("quantization_config")),
+            quant_skip_modules=cls._fp8_skip_modules(
                 cfg.get("quantization_config")),
         )
 
@@ -620,12 +674,25 @@ class EngineConfig:
 
     def resolve_quantization(self, model_cfg: ModelConfig) -> str | None:
         """The mode the engine runs: an AWQ checkpoint selects "awq" on its
-        own and excludes every other mode; "awq" needs such a checkpoint."""
+        own and excludes every other mode; "awq" needs such a checkpoint. A
+        block-scaled FP8 checkpoint selects "fp8_block" on its own; "fp8"
+        on it is accepted and means the same, on any other checkpoint it is
+        the W8A8 path."""
         if self.quantize_experts and model_cfg.num_local_experts == 0:
             raise ValueError(
                 "quantize_experts needs an MoE model, "
                 f"{model_cfg.architecture} has no experts"
             )
+        if model_cfg.quant_method == "fp8_block":
+            # the checkpoint's own format: "fp8" on it means exactly that,
+            # not the load-time W8A8 re-quantization of a bf16 checkpoint
+            if self.quantization not in (None, "fp8"):
+                raise ValueError(
+                    f"quantization={self.quantization!r} cannot be applied "
+                    "to a block-scaled FP8 checkpoint: its weights are "
+                    "already e4m3 (leave quantization unset or give 'fp8')"
+                )
+            return "fp8_block"
         if model_cfg.quant_method == "awq":
             if self.quantization not in (None, "awq"):
                 raise ValueError(

@@ -103,6 +103,10 @@ class ModelRunner:
             # W4 storage first: the bf16 weights of the quantized layers are
             # never allocated on the device
             self.model.prepare_awq()
+        elif self.quantization == "fp8_block":
+            # likewise for a block-scaled FP8 checkpoint: the e4m3 bytes
+            # stream straight into the layers' W8 buffers
+            self.model.prepare_fp8_checkpoint()
         if self.cfg.model_path:
             from ..loader.safetensors_loader import load_model_weights
 
@@ -125,6 +129,8 @@ class ModelRunner:
                 torch.cuda.empty_cache()
         elif self.quantization == "awq":
             self.model.finalize_w4()
+        elif self.quantization == "fp8_block":
+            self.model.finalize_w8()
         elif self.quantization is not None:
             raise ValueError(f"unknown quantization {self.quantization!r}")
         # serving past max_position_embeddings: the rope table must cover

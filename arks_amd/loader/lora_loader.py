@@ -50,7 +50,9 @@ def _fused_layers(layer) -> dict[str, tuple]:
 
 
 def _local_shape(mod) -> tuple[int, int]:
-    """(N, K) of a linear layer's local weight, W4-quantized or not."""
+    """(N, K) of a linear layer's local weight, W4/W8-quantized or not."""
+    if getattr(mod, "w8", False):
+        return mod.w8_shape
     return mod.w4_shape if getattr(mod, "w4", False) else tuple(mod.weight.shape)
 
 

@@ -24,6 +24,7 @@ def _iter_safetensors(model_path: str):
     for f in files:
         with safe_open(f, framework="pt", device="cpu") as sf:
             for name in sf.keys():
+                _st_dtype(name, sf.get_slice(name).get_dtype())
                 yield name, sf.get_tensor(name)
 
 
@@ -49,7 +50,20 @@ _ST_DTYPES = {
     "F64": torch.float64, "I64": torch.int64, "I32": torch.int32,
     "I16": torch.int16, "I8": torch.int8, "U8": torch.uint8,
     "BOOL": torch.bool,
+    # OCP e4m3fn: the weights of a block-scaled FP8 checkpoint, and the
+    # device's own FP8 format on gfx950 (no fnuz conversion)
+    "F8_E4M3": torch.float8_e4m3fn,
 }
+
+
+def _st_dtype(name: str, dtype: str) -> torch.dtype:
+    if dtype == "F8_E5M2":
+        raise ValueError(
+            f"{name}: F8_E5M2 tensors are not supported (FP8 checkpoints are "
+            "read in e4m3 only)")
+    if dtype not in _ST_DTYPES:
+        raise ValueError(f"{name}: unsupported safetensors dtype {dtype!r}")
+    return _ST_DTYPES[dtype]
 
 
 def _parse_header(path: str):
@@ -63,7 +77,7 @@ def _parse_header(path: str):
         header = json.loads(f.read(hlen))
     data_start = 8 + hlen
     ts = [
-        (name, _ST_DTYPES[m["dtype"]], m["shape"],
+        (name, _st_dtype(name, m["dtype"]), m["shape"],
          m["data_offsets"][0], m["data_offsets"][1])
         for name, m in header.items() if name != "__metadata__"
     ]
@@ -274,6 +288,62 @@ def save_awq_checkpoint(cfg, out_dir: str, seed: int = 0,
     _write_checkpoint(cfg, out_dir, awq, files=files,
                       extra_config={"quantization_config": dict(_AWQ_CONFIG),
                                     "torch_dtype": "float16"})
+    if dequantized_dir is not None:
+        _write_checkpoint(cfg, dequantized_dir, plain)
+
+
+_FP8_CONFIG = {"quant_method": "fp8", "fmt": "e4m3",
+               "activation_scheme": "dynamic",
+               "weight_block_size": [128, 128]}
+
+
+def save_fp8_checkpoint(cfg, out_dir: str, seed: int = 0,
+                        dequantized_dir: str | None = None,
+                        skip: tuple = ()) -> None:
+    """Write a random-init checkpoint in the block-scaled ("fine-grained")
+    FP8 layout transformers writes: every q/k/v/o/gate/up/down projection
+    (of a dense MLP, of each routed MoE expert under its Qwen-MoE or Mixtral
+    w1/w3/w2 name, and of the shared expert) is quantized
+    (ops.ref.w8_quantize) and stored as .weight e4m3fn [N, K] plus
+    .weight_scale_inv f32 [ceil(N/128), ceil(K/128)]; everything else is
+    bf16. config.json carries the quantization_config.
+    skip: projection names (e.g. "down_proj", or a full module name) left in
+    bf16 and listed under modules_to_not_convert together with lm_head.
+    dequantized_dir: also write a plain bf16 checkpoint holding the
+    dequantized weights (the model an FP8 engine must reproduce)."""
+    from ..ops import ref
+
+    projs = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj",
+             "down_proj", "w1", "w2", "w3")
+
+    def skipped(stem: str) -> bool:
+        comps = stem.split(".")
+        for entry in skip:
+            e = entry.split(".")
+            if any(comps[i:i + len(e)] == e
+                   for i in range(len(comps) - len(e) + 1)):
+                return True
+        return False
+
+    fp8: dict[str, torch.Tensor] = {}
+    plain: dict[str, torch.Tensor] = {}
+    for name, t in _random_hf_tensors(cfg, seed).items():
+        stem, _, param = name.rpartition(".")
+        if (param == "weight" and stem.rsplit(".", 1)[-1] in projs
+                and not skipped(stem)):
+            w8, blocks = ref.w8_quantize(t)
+            fp8[name] = w8
+            fp8[f"{stem}.weight_scale_inv"] = blocks
+            plain[name] = ref.w8_dequant(
+                w8, ref.w8_expand_scales(blocks, w8.shape[0])
+            ).to(torch.bfloat16)
+        else:
+            fp8[name] = t.to(torch.bfloat16)
+            plain[name] = t.to(torch.bfloat16)
+    qc = dict(_FP8_CONFIG)
+    qc["modules_to_not_convert"] = ["lm_head", *skip]
+    _write_checkpoint(cfg, out_dir, fp8,
+                      extra_config={"quantization_config": qc})
     if dequantized_dir is not None:
         _write_checkpoint(cfg, dequantized_dir, plain)
 

@@ -710,6 +710,280 @@ class LlamaFamilyForCausalLM(nn.Module):
             for _, moe in self._moe_blocks():
                 moe.finalize_w4()
 
+    # ---- block-scaled FP8 checkpoints (W8A16; format in ops/ref.py) ----
+    # X.weight e4m3fn [N, K] + X.weight_scale_inv f32 [ceil(N/128),
+    # ceil(K/128)] per quantized projection. The candidate layers are
+    # _w4_targets(experts=True); the routed experts have no grouped W8 kernel
+    # and are dequantized to bf16 at load, as is a quantized lm_head.
+    _W8_KINDS = ("weight", "weight_scale_inv")
+
+    @staticmethod
+    def _w8_hf_parts(name: str) -> list[str]:
+        """HF module names behind one of our (possibly fused) layers."""
+        pre, _, leaf = name.rpartition(".")
+        group = {"qkv_proj": ("q_proj", "k_proj", "v_proj"),
+                 "gate_up_proj": ("gate_proj", "up_proj")}.get(leaf, (leaf,))
+        return [f"model.{pre}.{p}" for p in group]
+
+    def _w8_skipped(self, hf_name: str) -> bool:
+        """modules_to_not_convert semantics: an entry names a module when its
+        dotted components occur in a row in the module's name."""
+        comps = hf_name.split(".")
+        for entry in self.cfg.quant_skip_modules:
+            e = entry.split(".")
+            if any(comps[i:i + len(e)] == e
+                   for i in range(len(comps) - len(e) + 1)):
+                return True
+        return False
+
+    def quantize_w8(self) -> None:
+        """Block-scaled W8A16 of a loaded bf16 model in memory
+        (quantize_module_w8 over the layers an FP8 checkpoint quantizes; the
+        routed experts stay bf16). For tests and benchmarks: serving reads
+        the format from a checkpoint, there is no --quantization value."""
+        from ..parallel.layers import quantize_module_w8
+
+        for name, mod in self._w4_targets(experts=True):
+            quantize_module_w8(mod, name)
+
+    def prepare_fp8_checkpoint(self) -> None:
+        """Switch the quantized layers to (empty) W8 storage BEFORE a
+        block-scaled FP8 checkpoint streams in, so their bf16 weights are
+        never allocated on the device; finalize_w8() completes the switch
+        after loading. The parts of a fused projection must all be quantized
+        or all be on the checkpoint's skip list."""
+        from ..parallel.layers import init_module_w8
+
+        self._w8_pending = {}
+        self._w8_experts_logged = False
+        for name, mod in self._w4_targets(experts=True):
+            skipped = [self._w8_skipped(p) for p in self._w8_hf_parts(name)]
+            if all(skipped):
+                continue
+            if any(skipped):
+                raise ValueError(
+                    f"{name}: the checkpoint quantizes only some parts of "
+                    "this fused projection "
+                    f"({dict(zip(self._w8_hf_parts(name), skipped))}: True = "
+                    "left in bf16); they must all be FP8 or all plain")
+            init_module_w8(mod, name)
+            mod._w8_got = set()
+
+    def finalize_w8(self) -> None:
+        from ..parallel.layers import finalize_module_w8
+
+        for key, held in getattr(self, "_w8_pending", {}).items():
+            for stem, kinds in held.items():
+                if key[0] != "dequant":
+                    raise ValueError(
+                        f"{stem}.{key[1]}: the fused partners of this FP8 "
+                        f"tensor ({key[0]}) are missing from the checkpoint")
+                if "weight" not in kinds:
+                    raise ValueError(
+                        f"{stem}.weight_scale_inv: a scale without its "
+                        "weight in the checkpoint")
+                raise ValueError(
+                    f"{stem}.weight: an FP8 weight without its "
+                    "weight_scale_inv in the checkpoint")
+        for name, mod in self._w4_targets(experts=True):
+            if not getattr(mod, "w8", False):
+                continue
+            missing = set(self._W8_KINDS) - mod._w8_got
+            if missing == {"weight"}:
+                raise ValueError(
+                    f"{name}: a scale without its weight in the checkpoint")
+            if missing:
+                raise ValueError(
+                    f"{name}: the checkpoint has no {sorted(missing)} for "
+                    "this FP8 layer")
+            finalize_module_w8(mod)
+
+    def _w8_target(self, stem: str):
+        """(module, our name, fused HF partner stems or None, how) of the HF
+        module `stem` (no "model." prefix) for an FP8 tensor; how is "col"
+        (column-parallel, maybe fused), "row", "dequant" (dequantize to bf16
+        and load as a plain weight) or "skip" (another rank's expert). None
+        for a module that never holds FP8."""
+        if stem == "lm_head":
+            return None, "lm_head", None, "dequant"
+        parts = stem.split(".")
+        if parts[0] != "layers" or len(parts) < 4:
+            return None
+        li = int(parts[1])
+        if li >= len(self.layers):
+            return None
+        layer = self.layers[li]
+        pre = f"layers.{li}"
+        sub = ".".join(parts[2:])
+        if parts[2] == "self_attn":
+            attn = layer.self_attn
+            if parts[3] in ("q_proj", "k_proj", "v_proj") and len(parts) == 4:
+                return (attn.qkv_proj, f"{pre}.self_attn.qkv_proj",
+                        [f"{pre}.self_attn.{p}"
+                         for p in ("q_proj", "k_proj", "v_proj")], "col")
+            if sub == "self_attn.o_proj":
+                return attn.o_proj, f"{pre}.self_attn.o_proj", None, "row"
+            return None
+        if sub.startswith(("mlp.experts.", "block_sparse_moe.experts.")):
+            if not isinstance(layer.mlp, MoEMLP) or len(parts) != 6:
+                return None
+            le = int(parts[4]) - layer.mlp.expert_base
+            local = 0 <= le < layer.mlp.local_experts
+            return None, stem, None, "dequant" if local else "skip"
+        if sub.startswith("mlp.shared_expert."):
+            if not isinstance(layer.mlp, MoEMLP) or layer.mlp.shared is None:
+                return None
+            mlp, mpre = layer.mlp.shared, f"{pre}.mlp.shared_expert"
+        elif parts[2] == "mlp" and isinstance(layer.mlp, MLP):
+            mlp, mpre = layer.mlp, f"{pre}.mlp"
+        else:
+            return None
+        leaf = parts[-1]
+        if stem != f"{mpre}.{leaf}":
+            return None
+        if leaf in ("gate_proj", "up_proj"):
+            return (mlp.gate_up_proj, f"{mpre}.gate_up_proj",
+                    [f"{mpre}.gate_proj", f"{mpre}.up_proj"], "col")
+        if leaf == "down_proj":
+            return mlp.down_proj, f"{mpre}.down_proj", None, "row"
+        return None
+
+    def _route_w8(self, full_name: str, w: torch.Tensor) -> bool:
+        """Takes the tensors of a block-scaled FP8 checkpoint (e4m3 weights
+        and their weight_scale_inv) out of load_hf_state_dict's stream; True
+        when the tensor was consumed here."""
+        name = full_name.removeprefix("model.")
+        stem, _, kind = name.rpartition(".")
+        is_fp8 = w.dtype == torch.float8_e4m3fn
+        if not is_fp8 and kind != "weight_scale_inv":
+            if kind == "weight":
+                tgt = self._w8_target(stem)
+                if (tgt is not None and tgt[0] is not None
+                        and getattr(tgt[0], "w8", False)):
+                    raise ValueError(
+                        f"{full_name}: plain {w.dtype} weight, but "
+                        f"{tgt[1]} was prepared for FP8 (the checkpoint's "
+                        "quantization_config does not list it under "
+                        "modules_to_not_convert)")
+            return False
+        if is_fp8 and kind != "weight":
+            raise ValueError(f"{full_name}: unexpected FP8 tensor (only "
+                             "linear weights are read in FP8)")
+        tgt = self._w8_target(stem)
+        if tgt is None:
+            raise ValueError(
+                f"{full_name}: FP8 tensor for a module that is never "
+                "quantized (embeddings, norms and router gates are read "
+                "in bf16)")
+        mod, modname, group, how = tgt
+        if how == "skip":
+            return True
+        if not hasattr(self, "_w8_pending"):
+            raise ValueError(
+                f"{full_name}: FP8 tensor in the checkpoint but the model "
+                "was not prepared for FP8 (config.json lacks "
+                "quantization_config?)")
+        if how == "dequant":
+            self._w8_dequant_load(full_name, stem, kind, w)
+            return True
+        if not getattr(mod, "w8", False):
+            raise ValueError(
+                f"{full_name}: FP8 tensor in the checkpoint but {modname} "
+                "was not prepared for FP8 (it is on the checkpoint's skip "
+                "list)")
+        if group is None:
+            self._load_w8(mod, modname, kind, [w], how)
+            return True
+        held = self._w8_pending.setdefault((modname, kind), {})
+        held[stem] = {kind: w}
+        if all(g in held for g in group):
+            fulls = [held[g][kind] for g in group]
+            del self._w8_pending[(modname, kind)]
+            self._load_w8(mod, modname, kind, fulls, how)
+        return True
+
+    def _load_w8(self, mod, name: str, kind: str, fulls, how: str) -> None:
+        """One tensor kind (weight / weight_scale_inv) of a projection, or
+        of the fused partners `fulls`, into the module's W8 buffers. The
+        block scales are expanded to one row per output channel first, so a
+        column-parallel shard slices rows like the weight does and fused
+        parts concatenate along N; a row-parallel shard slices K in whole
+        128-blocks. The two kinds are independent, so they may arrive in
+        different chunks."""
+        from ..ops import ref
+
+        B = ref.W8_BLOCK
+        r = get_tp_rank()
+        if kind == "weight":
+            rows = list(fulls)
+        else:
+            rows = []
+            for t in fulls:
+                if t.dim() != 2:
+                    raise ValueError(
+                        f"{name}: weight_scale_inv {tuple(t.shape)} is not "
+                        "a 2-D block scale")
+                rows.append(t.float().repeat_interleave(B, dim=0))
+        N, K = mod.w8_shape
+        if how == "row":
+            per = mod.in_per_rank if kind == "weight" else mod.in_per_rank // B
+            # [:N]: the expanded scale rows run to the end of the last block
+            parts = [rows[0][:N, r * per:(r + 1) * per]]
+        elif len(rows) == 3:
+            parts = mod.shard_qkv_parts(*rows)
+        elif len(rows) == 2:
+            parts = mod.shard_merged_parts(*rows)
+        else:
+            parts = [mod.shard(rows[0])]
+        cols = K if kind == "weight" else K // B
+        off = 0
+        for part in parts:
+            n = part.shape[0]
+            if part.shape[1] != cols or off + n > N:
+                raise ValueError(
+                    f"{name}: FP8 {kind} part {tuple(part.shape)} does not "
+                    f"fit the layer's {N}x{K} at block size {B}")
+            if kind == "weight":
+                mod.w8_weight[off:off + n].copy_(part)
+            else:
+                mod.w8_scales[:, off:off + n].copy_(part.t())
+            off += n
+        if off != N:
+            raise ValueError(f"{name}: FP8 {kind} covers {off} of {N} rows")
+        mod._w8_got.add(kind)
+
+    def _w8_dequant_load(self, full_name: str, stem: str, kind: str,
+                         w: torch.Tensor) -> None:
+        """A routed expert or lm_head that arrives in FP8: hold the tensor
+        until its partner is here, then dequantize to bf16 on the model's
+        device and load it as the plain weight it replaces. One projection
+        at a time, so the transient memory is one expert's."""
+        import logging
+
+        from ..ops import ref
+
+        held = self._w8_pending.setdefault(("dequant", stem), {})
+        pair = held.setdefault(stem, {})
+        # the partner may come with a later chunk, after the staging buffer
+        # this view points into has been recycled
+        pair[kind] = w.clone()
+        if len(pair) < 2:
+            return
+        del self._w8_pending[("dequant", stem)]
+        if stem != "lm_head" and not self._w8_experts_logged:
+            self._w8_experts_logged = True
+            logging.getLogger(__name__).warning(
+                "FP8 routed experts are dequantized to bf16 at load (no "
+                "grouped W8 kernel): the model holds its experts at bf16 "
+                "size")
+        dev = self.embed_tokens.weight.device
+        w8 = pair["weight"].to(dev)
+        scales = ref.w8_expand_scales(pair["weight_scale_inv"].to(dev),
+                                      w8.shape[0])
+        plain = ref.w8_dequant(w8, scales).to(self.dtype)
+        pre = "" if stem == "lm_head" else "model."
+        self.load_hf_state_dict({f"{pre}{stem}.weight": plain})
+
     def _load_awq(self, mod, name: str, kind: str, fulls, shard_parts) -> None:
         """One AWQ tensor kind (qweight / qzeros / scales) of a projection,
         or of the fused partners `fulls`: unpack on the host to row form
@@ -828,6 +1102,8 @@ class LlamaFamilyForCausalLM(nn.Module):
             assert off == p.shape[0], (name, off, p.shape)
 
         for name, w in tensors.items():
+            if self._route_w8(name, w):
+                continue
             name = name.removeprefix("model.")
             if name == "embed_tokens.weight":
                 put("embed_tokens.weight", w)

@@ -690,6 +690,148 @@ def w4_linear(x, packed, bias=None, defer: bool = False, plan=None):
     return _w4_dequant_linear(x, packed, bias)
 
 
+# ---------------------------------------------------------------------------
+# W8A16 (block-scaled e4m3fn weights, 128x128 blocks; format in ops/ref.py)
+# ---------------------------------------------------------------------------
+W8_SKINNY_MAX_M = 64
+# 64 < M <= this: the skinny kernel once per 64-row slab; above it the
+# weight is dequantized into the workspace for the library GEMM. Set from
+# the M = 96 / 128 / 256 rows of profiles/w8_gemm.md (numbers in w8_linear's
+# docstring).
+W8_SLAB_MAX_M = 128
+
+
+def _w8_plan(M: int, N: int, K: int):
+    """Routing rule of the W8 skinny GEMM: (nw, nsplits, k_per_split, mrows),
+    with the meaning of _w4_plan's tuple: nw = 64-row N sub-tiles per
+    workgroup, mrows = 16 * MT the slab height of the split-K partials,
+    k_per_split a multiple of the 128 scale block.
+
+    The kernel shares the W4 kernel's staging, grid and partial layout, so
+    the rule is the W4 one (its nw x nsplits sweep is in
+    profiles/w4_gemm.md); it was not swept again cell by cell for W8.
+    MEASURED as a whole on an MI355X with scripts/bench_w8.py (in-graph,
+    weights cycled past the LLC; profiles/w8_gemm.md): with this plan every
+    M <= 64 row of the Qwen2.5-7B shapes beats bf16 (qkv 10.1-16.5 us vs
+    14.1-19.3, o 9.9-14.7 vs 12.1-15.9, gate_up 34.0-51.7 vs 56.8-63.1, down
+    22.3-29.5 vs 42.4-110.9), gate_up unsplit at 4.1 TB/s of weight bytes
+    at M = 1."""
+    nw = 2 if (M > 32 and N % 128 == 0) else 1
+    ntiles = N // (64 * nw)
+    chunks = K // 128
+    if ntiles >= 256:
+        nsplits = 1
+    else:
+        target = 800 if nw == 1 else 448
+        nsplits = max(1, min(-(-target // ntiles), chunks // 4))
+    k_per_split = -(-chunks // nsplits) * 128
+    nsplits = -(-K // k_per_split)
+    return nw, nsplits, k_per_split, 16 * min(-(-M // 16), 4)
+
+
+def w8_dequant(weight, out=None):
+    """bf16 [N, K] from a W8 weight (w8_weight, w8_scales), via
+    w8_dequant_kernel on GPU."""
+    w8, scales = weight
+    N, K = w8.shape
+    if not w8.is_cuda:
+        return ref.w8_dequant(w8, scales).to(torch.bfloat16)
+    if out is None:
+        out = torch.empty(N * K, dtype=torch.bfloat16, device=w8.device)
+    _native().w8_dequant(out, w8, scales)
+    return out[: N * K].view(N, K)
+
+
+def _w8_skinny(x, weight, bias, defer: bool, plan, out=None):
+    """One launch of the W8 skinny kernel for M <= 64 rows (plus the combine
+    when it splits K and the result is not deferred)."""
+    w8, scales = weight
+    M, K = x.shape
+    N = w8.shape[0]
+    if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    nw, nsplits, k_per_split, mrows = plan or _w8_plan(M, N, K)
+    part = (_skinny_ws(nsplits, N, mrows, x.device) if nsplits > 1
+            else x.new_empty(0, dtype=torch.float32))
+    if defer and nsplits > 1 and _SPLITK_FUSE:
+        _native().w8_skinny_gemm_partials(part, x, w8, scales, k_per_split,
+                                          nsplits, nw)
+        return SplitKPending(part, nsplits, mrows, M, N, bias,
+                             (x.device.index,))
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    _native().w8_skinny_gemm(out, part, x, w8, scales, bias, k_per_split,
+                             nsplits, nw)
+    return out
+
+
+def _w8_slabs(x, weight, bias):
+    """M > 64 through the skinny kernel, 64 rows at a time, each slab
+    written straight into its rows of the output."""
+    M = x.shape[0]
+    out = torch.empty((M, weight[0].shape[0]), dtype=x.dtype, device=x.device)
+    for r in range(0, M, W8_SKINNY_MAX_M):
+        _w8_skinny(x[r:r + W8_SKINNY_MAX_M], weight, bias, False, None,
+                   out=out[r:r + W8_SKINNY_MAX_M])
+    return out
+
+
+def _w8_dequant_linear(x, weight, bias):
+    """M above the slab limit through the library GEMM on the weight
+    expanded to bf16 in the device's reserved dequant workspace (the one
+    w4_reserve_workspace manages: a model is W4 or W8, never both at once,
+    and either way the scratch is one bf16 [N*K] of its largest layer)."""
+    N, K = weight[0].shape
+    ws = _W4_DEQUANT_WS.get((x.device.index,))
+    if ws is None or ws.numel() < N * K:
+        raise RuntimeError(
+            f"dequant workspace missing or smaller than {N}x{K}: "
+            "call ops.w4_reserve_workspace when the layer is quantized"
+        )
+    import torch.nn.functional as F
+
+    return F.linear(x, w8_dequant(weight, ws), bias)
+
+
+def w8_linear(x, weight, bias=None, defer: bool = False, plan=None):
+    """y = x @ dequant(weight)^T + bias for a W8 weight (w8_weight e4m3fn
+    [N, K], w8_scales f32 [K/128, N]). On GPU: the W8 streaming kernel for
+    M <= 64 (defer=True returns a SplitKPending when it splits K, as
+    skinny_gemm does); M up to W8_SLAB_MAX_M runs that kernel per 64-row
+    slab; above it the weight is expanded to bf16 in the preallocated
+    workspace and the library GEMM runs on it. No eager fallback: a shape the
+    kernels cannot take raises. On CPU: the reference emulation.
+    plan overrides _w8_plan for M <= 64 (tests force a split count with it).
+
+    M > 64 crossover, MEASURED with scripts/bench_w8.py on an MI355X
+    (in-graph us, slabs vs dequant+library; profiles/w8_gemm.md):
+    M=96: qkv 25.9 vs 32.1, o 24.3 vs 30.9, gate_up 85.5 vs 147, down 52.1
+    vs 102; M=128: qkv 31.3 vs 33.7, o 28.3 vs 32.4, gate_up 96.5 vs 151,
+    down 55.0 vs 110 — slabs win everywhere. M=256: qkv 61.4 vs 45.3, o 55.6
+    vs 28.8, gate_up 181 vs 156 — the library GEMM wins (down alone still
+    favours slabs, 106 vs 140). 192 was not measured; W8_SLAB_MAX_M sits at
+    the last size where slabs were seen to win. Above M = 64 bf16 weights are
+    faster than either route on qkv/o/gate_up (23 / 23 / 70 us at 128); down
+    stays faster in W8 up to 128 rows."""
+    w8, scales = weight
+    if not x.is_cuda:
+        return ref.w8_linear(x, w8, scales, bias)
+    if x.dim() != 2 or x.dtype != torch.bfloat16:
+        raise ValueError(f"w8_linear needs a 2-D bf16 input, got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    M, K = x.shape
+    N = w8.shape[0]
+    if w8.shape[1] != K:
+        raise ValueError(f"w8_linear: x has K={K}, weight K={w8.shape[1]}")
+    if M == 0:
+        return x.new_empty((0, N))
+    if M <= W8_SKINNY_MAX_M:
+        return _w8_skinny(x, weight, bias, defer, plan)
+    if M <= W8_SLAB_MAX_M:
+        return _w8_slabs(x, weight, bias)
+    return _w8_dequant_linear(x, weight, bias)
+
+
 def w4_moe_gemm(a, packed, counts, pairs, src_div: int, max_rows: int,
                 out=None):
     """Routed grouped W4A16 GEMM over the stacked local experts of an MoE

@@ -149,6 +149,14 @@ void arks_w4_moe_gemm(void* out, const void* a, const void* qw,
                       const void* counts, const void* pairs, int n_experts,
                       int t_cols, int n_pairs, int src_div, int slabs,
                       int n_total, int k_total, int nw, hipStream_t stream);
+void arks_w8_skinny_gemm(void* part, void* out, const void* a, const void* w8,
+                         const void* scales, const void* bias, int m_rows,
+                         int n_total, int k_total, int k_per_split,
+                         int nsplits, int64_t a_stride, int nw, bool combine,
+                         hipStream_t stream);
+int arks_w8_slab_rows(int m_rows);
+void arks_w8_dequant(void* out, const void* w8, const void* scales,
+                     int n_total, int k_total, hipStream_t stream);
 void arks_moe_route(void* counts, void* pairs, const void* ids, int n_pairs,
                     int T, int expert_base, int n_local, hipStream_t stream);
 void arks_mfma_probe(void* d, const void* a, const void* b, hipStream_t stream);
@@ -601,6 +609,103 @@ void w4_dequant(torch::Tensor out, torch::Tensor qw, torch::Tensor scales,
   TORCH_CHECK(n * (k / 8) < (int64_t)1 << 39);
   arks_w4_dequant(out.data_ptr(), qw.data_ptr(), scales.data_ptr(),
                   zeros.data_ptr(), (int)n, (int)k, current_stream());
+}
+
+// W8 weight (w8_gemm.hip): e4m3fn [N, K] as in the checkpoint, scales f32
+// [K/128, N] (block scales expanded per output row). Returns (n, k).
+std::pair<int64_t, int64_t> check_w8_weight(const torch::Tensor& w8,
+                                            const torch::Tensor& scales) {
+  TORCH_CHECK(w8.is_cuda() && w8.scalar_type() == at::kFloat8_e4m3fn &&
+              w8.dim() == 2 && w8.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(w8.data_ptr()) % 16 == 0,
+              "w8 weight must be contiguous float8_e4m3fn [N, K] on GPU");
+  const int64_t n = w8.size(0), k = w8.size(1);
+  TORCH_CHECK(k >= 128 && k % 128 == 0, "W8 needs K % 128 == 0, got K=", k);
+  TORCH_CHECK(n % 64 == 0, "W8 needs N % 64 == 0, got N=", n);
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kFloat32 &&
+              scales.is_contiguous() && scales.dim() == 2 &&
+              scales.size(0) == k / 128 && scales.size(1) == n &&
+              reinterpret_cast<uintptr_t>(scales.data_ptr()) % 16 == 0,
+              "scales must be contiguous f32 [K/128, N] on GPU");
+  TORCH_CHECK(scales.device() == w8.device());
+  return {n, k};
+}
+
+// nw = 64-row N sub-tiles per workgroup (1 or 2); combine = false leaves the
+// split-K partials in `part` (bias is then applied by the consumer).
+void w8_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
+                         torch::Tensor a, torch::Tensor w8,
+                         torch::Tensor scales,
+                         c10::optional<torch::Tensor> bias,
+                         int64_t k_per_split, int64_t nsplits, int64_t nw,
+                         bool combine) {
+  const auto [n, k] = check_w8_weight(w8, scales);
+  check_bf16_rowstrided(a, "a");
+  TORCH_CHECK(a.dim() == 2 && a.size(1) == k, "a must be [M, K]");
+  TORCH_CHECK(a.device() == w8.device());
+  const int64_t m = a.size(0);
+  TORCH_CHECK(m >= 1 && m <= 64, "w8_skinny_gemm needs 1 <= M <= 64");
+  TORCH_CHECK(a.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "a rows must be 16-byte aligned");
+  TORCH_CHECK((nw == 1 || nw == 2) && n % (64 * nw) == 0,
+              "nw in {1, 2} with N % (64 * nw) == 0");
+  TORCH_CHECK(nsplits >= 1 && k_per_split >= 128 && k_per_split % 128 == 0 &&
+              nsplits * k_per_split >= k && (nsplits - 1) * k_per_split < k,
+              "splits of a multiple of 128 must cover K exactly");
+  const int mrows = arks_w8_slab_rows((int)m);
+  const void* bias_ptr = nullptr;
+  if (combine) {
+    check_bf16_contig(out, "out");
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == m && out.size(1) == n);
+    if (bias.has_value()) {
+      check_bf16_contig(*bias, "bias");
+      TORCH_CHECK(bias->numel() == n);
+      bias_ptr = bias->data_ptr();
+    }
+  } else {
+    TORCH_CHECK(nsplits > 1, "partials-only needs nsplits > 1");
+  }
+  if (nsplits > 1) {
+    TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
+                part.is_contiguous() &&
+                part.numel() >= nsplits * n * mrows &&
+                reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
+                "w8_skinny_gemm workspace too small");
+  }
+  arks_w8_skinny_gemm(nsplits > 1 ? part.data_ptr() : nullptr,
+                      combine ? out.data_ptr() : nullptr, a.data_ptr(),
+                      w8.data_ptr(), scales.data_ptr(), bias_ptr, (int)m,
+                      (int)n, (int)k, (int)k_per_split, (int)nsplits,
+                      a.stride(0), (int)nw, combine, current_stream());
+}
+
+void w8_skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
+                    torch::Tensor w8, torch::Tensor scales,
+                    c10::optional<torch::Tensor> bias, int64_t k_per_split,
+                    int64_t nsplits, int64_t nw) {
+  w8_skinny_gemm_impl(out, part, a, w8, scales, bias, k_per_split, nsplits,
+                      nw, true);
+}
+
+void w8_skinny_gemm_partials(torch::Tensor part, torch::Tensor a,
+                             torch::Tensor w8, torch::Tensor scales,
+                             int64_t k_per_split, int64_t nsplits,
+                             int64_t nw) {
+  w8_skinny_gemm_impl(torch::Tensor(), part, a, w8, scales, c10::nullopt,
+                      k_per_split, nsplits, nw, false);
+}
+
+// out bf16 [>= N*K elements] receives the dequantized [N, K] weight.
+void w8_dequant(torch::Tensor out, torch::Tensor w8, torch::Tensor scales) {
+  const auto [n, k] = check_w8_weight(w8, scales);
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(out.numel() >= n * k && out.device() == w8.device() &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "w8_dequant output too small");
+  TORCH_CHECK(n * (k / 16) < (int64_t)1 << 39);
+  arks_w8_dequant(out.data_ptr(), w8.data_ptr(), scales.data_ptr(), (int)n,
+                  (int)k, current_stream());
 }
 
 // Routed grouped GEMM over stacked experts (w4_moe_gemm_kernel):
@@ -1192,6 +1297,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w4_skinny_gemm_partials", &w4_skinny_gemm_partials);
   m.def("w4_dequant", &w4_dequant);
   m.def("w4_moe_gemm", &w4_moe_gemm);
+  m.def("w8_skinny_gemm", &w8_skinny_gemm);
+  m.def("w8_skinny_gemm_partials", &w8_skinny_gemm_partials);
+  m.def("w8_dequant", &w8_dequant);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache);
   m.def("greedy_sample", &greedy_sample);

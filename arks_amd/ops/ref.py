@@ -563,6 +563,69 @@ def awq_pack(q: torch.Tensor, z: torch.Tensor, s: torch.Tensor):
             s.t().contiguous().to(torch.float16))
 
 
+# ---------------------------------------------------------------------------
+# W8A16: OCP e4m3fn weights scaled per 128x128 block (the "fine-grained FP8"
+# checkpoint format of transformers):
+#   w[n, k] = float(w8[n, k]) * block_scale[n // 128, k // 128]
+# On disk: weight e4m3fn [N, K] and weight_scale_inv f32
+# [ceil(N/128), ceil(K/128)]. In a layer the weight is kept as it is and the
+# scales are expanded to one value per (k-block, output row), f32
+# [ceil(K/128), N]: the orientation of the W4 scales, so that fused
+# projections concatenate along N and a shard can cut at any row.
+# ---------------------------------------------------------------------------
+W8_BLOCK = 128
+W8_MAX = 448.0  # largest e4m3fn value
+
+
+def w8_quantize(w: torch.Tensor):
+    """Block-wise amax / 448 scaling with round-to-nearest-even:
+    (w8 e4m3fn [N, K], block scales f32 [ceil(N/128), ceil(K/128)]), the two
+    tensors a checkpoint stores as weight / weight_scale_inv. An all-zero
+    block gets scale 1."""
+    N, K = w.shape
+    B = W8_BLOCK
+    nb, kb = -(-N // B), -(-K // B)
+    wf = torch.zeros(nb * B, kb * B, dtype=torch.float32, device=w.device)
+    wf[:N, :K] = w.float()
+    blocks = wf.view(nb, B, kb, B)
+    amax = blocks.abs().amax(dim=(1, 3))
+    s = torch.where(amax > 0, amax / W8_MAX, torch.ones_like(amax))
+    q = (blocks / s[:, None, :, None]).clamp(-W8_MAX, W8_MAX)
+    w8 = q.reshape(nb * B, kb * B)[:N, :K].contiguous().to(torch.float8_e4m3fn)
+    return w8, s
+
+
+def w8_expand_scales(block_scales: torch.Tensor, N: int) -> torch.Tensor:
+    """Block scales [ceil(N/128), ceil(K/128)] -> per-row f32
+    [ceil(K/128), N]: out[kb, n] = block_scales[n // 128, kb]."""
+    if block_scales.dim() != 2 or block_scales.shape[0] != -(-N // W8_BLOCK):
+        raise ValueError(
+            f"block scales {tuple(block_scales.shape)} do not cover N={N} "
+            f"at block size {W8_BLOCK}")
+    rows = block_scales.float().repeat_interleave(W8_BLOCK, dim=0)[:N]
+    return rows.t().contiguous()
+
+
+def w8_dequant(w8: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """f32 [N, K] = float(w8) * scales[k // 128, n] for the expanded scales
+    [ceil(K/128), N] of a layer."""
+    N, K = w8.shape
+    if tuple(scales.shape) != (-(-K // W8_BLOCK), N):
+        raise ValueError(
+            f"scales {tuple(scales.shape)} do not match a {N}x{K} weight: "
+            f"expected [{-(-K // W8_BLOCK)}, {N}]")
+    per_k = scales.float().t().repeat_interleave(W8_BLOCK, dim=1)[:, :K]
+    return w8.float() * per_k
+
+
+def w8_linear(x: torch.Tensor, w8: torch.Tensor, scales: torch.Tensor,
+              bias=None) -> torch.Tensor:
+    """The CPU emulation of a W8 layer: a GEMM on the dequantized weight
+    rounded to the activation dtype."""
+    return torch.nn.functional.linear(
+        x, w8_dequant(w8, scales).to(x.dtype), bias)
+
+
 POOL_LAST, POOL_MEAN, POOL_CLS = 0, 1, 2
 
 

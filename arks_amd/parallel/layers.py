@@ -160,6 +160,90 @@ def _w4_linear(mod: nn.Module, x, bias, defer: bool):
                          bias, defer=defer)
 
 
+def _w8_check_shape(mod: nn.Module, name: str) -> tuple[int, int]:
+    from ..ops import ref
+
+    N, K = mod.weight.shape
+    if K % ref.W8_BLOCK != 0:
+        raise ValueError(
+            f"{name}: block-scaled fp8 needs the per-rank input width to be "
+            f"a multiple of the block size {ref.W8_BLOCK}, got K={K} at TP="
+            f"{get_tp_world_size()}"
+        )
+    if N % 64 != 0:
+        raise ValueError(
+            f"{name}: block-scaled fp8 needs the per-rank output width to "
+            f"be a multiple of 64, got N={N} at TP={get_tp_world_size()}"
+        )
+    return N, K
+
+
+def init_module_w8(mod: nn.Module, name: str = "linear") -> None:
+    """Switch a linear layer to (empty) W8 storage: w8_weight e4m3fn [N, K]
+    exactly as a block-scaled FP8 checkpoint stores it, w8_scales f32
+    [K/128, N]. The bf16 parameter is dropped, so a model switched before
+    its weights stream in never holds it."""
+    from .. import ops
+    from ..ops import ref
+
+    N, K = _w8_check_shape(mod, name)
+    dev = mod.weight.device
+    mod.w8_dtype = mod.weight.dtype
+    del mod._parameters["weight"]
+    mod.weight = None
+    mod.register_buffer(
+        "w8_weight", torch.zeros(N, K, dtype=torch.float8_e4m3fn, device=dev),
+        persistent=False)
+    mod.register_buffer(
+        "w8_scales",
+        torch.ones(K // ref.W8_BLOCK, N, dtype=torch.float32, device=dev),
+        persistent=False)
+    mod.w8 = True
+    mod.w8_shape = (N, K)
+    ops.w4_reserve_workspace(N * K, dev)
+
+
+def finalize_module_w8(mod: nn.Module) -> None:
+    """After the W8 buffers are filled: reserve the device's dequant
+    workspace (the module may have moved since it was switched) and, on CPU,
+    keep the dequantized weight in the layer's dtype so that the CPU path is
+    F.linear on it."""
+    from .. import ops
+    from ..ops import ref
+
+    dev = mod.w8_weight.device
+    if dev.type == "cuda":
+        ops.w4_reserve_workspace(mod.w8_shape[0] * mod.w8_shape[1], dev)
+        return
+    mod.register_buffer(
+        "weight_qdq",
+        ref.w8_dequant(mod.w8_weight, mod.w8_scales).to(mod.w8_dtype),
+        persistent=False,
+    )
+
+
+def quantize_module_w8(mod: nn.Module, name: str = "linear") -> None:
+    """Switch a loaded linear layer to W8A16 in memory: block-wise amax/448
+    e4m3 weights (ops.ref.w8_quantize). For tests and benchmarks; serving
+    reads the format from a checkpoint."""
+    from ..ops import ref
+
+    N, _ = _w8_check_shape(mod, name)
+    w8, blocks = ref.w8_quantize(mod.weight.data)
+    init_module_w8(mod, name)
+    mod.w8_weight.copy_(w8)
+    mod.w8_scales.copy_(ref.w8_expand_scales(blocks, N))
+    finalize_module_w8(mod)
+
+
+def _w8_linear(mod: nn.Module, x, bias, defer: bool):
+    if not x.is_cuda:
+        return F.linear(x, mod.weight_qdq, bias)
+    from .. import ops
+
+    return ops.w8_linear(x, (mod.w8_weight, mod.w8_scales), bias, defer=defer)
+
+
 class LoRAState:
     """Per-layer multi-LoRA slot tensors (arks_amd/loader/lora_loader.py):
     A [max_loras, S*R, K] and B [max_loras, N, R] bf16 over the layer's LOCAL
@@ -213,12 +297,13 @@ class ColumnParallelLinear(nn.Module):
 
     fp8 = False
     w4 = False
+    w8 = False  # block-scaled e4m3 weights (init_module_w8)
     lora: LoRAState | None = None  # set when the engine runs enable_lora
 
     def forward(self, x, lora_tiles=None, defer: bool = False):
         """defer=True: the caller can consume an ops.SplitKPending in place
         of the tensor (see ops.skinny_gemm). Granted only where the fused
-        consumers are valid: bf16 or W4 GEMM, TP world size 1, no LoRA
+        consumers are valid: bf16, W4 or W8 GEMM, TP world size 1, no LoRA
         delta."""
         if isinstance(x, tuple):  # pre-quantized by the producing kernel
             return _fp8_linear_prequant(self, *x)
@@ -230,6 +315,8 @@ class ColumnParallelLinear(nn.Module):
         defer = defer and not use_lora and get_tp_world_size() == 1
         if self.w4:
             y = _w4_linear(self, x, self.bias, defer)
+        elif self.w8:
+            y = _w8_linear(self, x, self.bias, defer)
         else:
             y = ops.linear_bf16(x, self.weight, self.bias, defer=defer)
         if use_lora:
@@ -323,6 +410,7 @@ class RowParallelLinear(nn.Module):
 
     fp8 = False
     w4 = False
+    w8 = False  # block-scaled e4m3 weights (init_module_w8)
     lora: LoRAState | None = None  # set when the engine runs enable_lora
 
     def forward(self, x, lora_tiles=None, defer: bool = False):
@@ -345,6 +433,8 @@ class RowParallelLinear(nn.Module):
                      and get_tp_world_size() == 1)
             if self.w4:
                 y = _w4_linear(self, x, None, defer)
+            elif self.w8:
+                y = _w8_linear(self, x, None, defer)
             else:
                 y = ops.linear_bf16(x, self.weight, defer=defer)
             if isinstance(y, ops.SplitKPending):

@@ -36,7 +36,9 @@ def parse_args(argv=None):
                    default=None)
     p.add_argument("--quantization", choices=["fp8", "int4", "awq"],
                    default=None,
-                   help="fp8: W8A8; int4: 4-bit round-to-nearest at load; "
+                   help="fp8: W8A8 at load (on a block-scaled FP8 checkpoint, "
+                        "which is also auto-detected: its own W8A16 format); "
+                        "int4: 4-bit round-to-nearest at load; "
                         "awq: a 4-bit AWQ checkpoint (also auto-detected)")
     p.add_argument("--quantize-experts", action="store_true",
                    help="with --quantization int4 on an MoE model: also "
