@@ -2,20 +2,43 @@
 // M <= 64 (one decode token per sequence). At these shapes the GEMM is pure
 // weight streaming (arithmetic intensity M/2 flop/byte), but hipBLASLt's
 // tuned algos reach only 1.3-2.9 TB/s on the decode shapes
-// (profiles/r01_p2, profiles/data/dec_top r2). This kernel streams W at
-// near-HBM rate:
+// (profiles/r01_p2, profiles/data/dec_top r2).
 //
-//   grid = (N/64, nsplits): a workgroup owns a 64-row N-tile and a K-range.
-//   W is read exactly once, 16 B/lane (guide G13), staged PF chunks ahead
-//   in registers; A (the activations, tiny, L2/LLC-hot) is staged through
-//   a ring of AB LDS buffers. What actually governs throughput here (r2
-//   ISA audit, profiles/r02_final.md): the staging loops must be BATCHED
-//   and BRANCHLESS — with per-item guards the compiler emits
-//   global_load -> s_waitcnt vmcnt(0) -> ds_write per item, and because
-//   vmcnt is an issue-ordered counter each of those waits also drains
-//   every in-flight W prefetch, pinning the stream at ~3 TB/s no matter
-//   how deep PF is. With batched staging, PF=1/AB=3 reaches ~3.9 TB/s on
-//   the down-proj shape (hipBLASLt in-graph: 2.9).
+//   grid = (N/64, nsplits), or (N/128, nsplits) for the tall-K configs: a
+//   workgroup owns an N-tile of 16 rows per wave and a K-range.
+//   W is read exactly once, 16 B/lane (guide G13), into a register ring of
+//   SK_D = 4 chunks of 128 k per wave (16 KB of W per wave in flight).
+//   A (the activations, tiny, L2-hot) rides in the same ring, one chunk
+//   piece per thread issued right ahead of the W loads of its chunk, and
+//   reaches the MFMAs through two ping-pong LDS buffers.
+//   Two things bound this kernel (profiles/r05_skinny_stream.md):
+//   (1) What a CU can fetch. A workgroup stages M x 128 of A per chunk
+//   against (16 x waves) x 128 of W, through the same load path, so with
+//   four waves at M = 64 half of a CU's fetches are A re-read from L2; a
+//   probe build without the A loads ran the down-proj 9 us (23 %) faster.
+//   The tall-K configs therefore run eight waves per workgroup: the same W
+//   per CU against half the A.
+//   (2) The s_waitcnt pattern of the compiled loop, because vmcnt retires
+//   in issue order (ISA audits: profiles/r02_final.md and r05). On its own
+//   the pattern below did not move the measured time (the loop was fetch-
+//   bound, not latency-bound), and neither did (1) on the old shifted ring
+//   (down-proj, cold: 39.7 us; ring alone 39.0; eight waves alone 37.8;
+//   both 32.4): with half the A, the loop is latency-bound again unless W
+//   stays in flight. The rules the loop follows:
+//     - per-item guards in a staging loop compile to load -> vmcnt(0) ->
+//       ds_write per item: the staging is batched and branchless;
+//     - a ring that is shifted (wreg[p] = wreg[p+1]) copies registers whose
+//       loads are still out, which costs a vmcnt(0) per chunk: the ring is
+//       indexed statically, the loop body is one whole turn of it;
+//     - a branch around a load makes every later count conservative: the
+//       steady-state turn has none, K-ranges of at most four chunks (qkv,
+//       o_proj) are issued whole in the prologue, and each possible number
+//       of trailing chunks has its own straight-line path;
+//     - the scheduler moves loads and ds_writes across one another, which
+//       changes the counts: sched_barrier fences pin the issue order.
+//   In the compiled steady state every wait is a counted vmcnt(N) that
+//   leaves three chunks of W outstanding; vmcnt(0) appears only where the
+//   last chunk of a K-range is consumed.
 //   Swapped operands (A-frag = W rows, B-frag = activations) put the C
 //   fragment at [n, m], n = 4*la+r, col = lane%16 (same trick as the
 //   attention kernels, guide common-mistake #6).
@@ -29,14 +52,14 @@
 //   splitk_reduce (common.h); skinny_combine_kernel is the fallback that
 //   materialises a bf16 [M, N].
 //
-// The file builds seven kernels: skinny_gemm_kernel<MT, 128, 1> for MT 1..4
-// (AB=2 ring; launch config 0, MT from M), the tall-K kernel
-// <4, 128, 2, AB=3> for the down-proj shape (config 1), the same with
+// The file builds seven kernels: skinny_gemm_kernel<MT> for MT 1..4 (launch
+// config 0, MT from M, four waves), <4, false, 8> for the tall-K plan of
+// the down-proj shape (config 1, eight waves), <4, true, 8> with
 // non-temporal W loads (config 2), and skinny_combine_kernel. The
-// experiments that lost to these — global-direct A reads, wave-private
-// barrier-free staging, silu_mul fused into the A staging, other (KC, PF)
-// pairs — are recorded with their numbers in profiles/r02_final.md; the MLP
-// runs silu_mul_kernel (elementwise.hip) ahead of the down-proj.
+// experiments that lost — global-direct A reads, wave-private barrier-free
+// staging, silu_mul fused into the A staging, shifted rings of other
+// (KC, PF) — are recorded with their numbers in profiles/r02_final.md; the
+// MLP runs silu_mul_kernel (elementwise.hip) ahead of the down-proj.
 //
 // N must be a multiple of 64 and K of 32 (true for every Qwen/Llama shape;
 // the Python wrapper falls back to hipBLASLt otherwise).
@@ -44,6 +67,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <type_traits>
 
 namespace arks {
 
@@ -54,7 +78,6 @@ __device__ __forceinline__ f32x4 sk_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-constexpr int SK_NT = 64;  // N rows per workgroup (16 per wave)
 constexpr int SK_AP = 8;   // a_lds row pad (bf16): rows stay 16B-aligned
 
 // Split-K epilogue: f32 partials [split][m][n] (row stride n_total, 16*MT
@@ -72,14 +95,39 @@ __device__ __forceinline__ void store_partials(float* __restrict__ part,
     *reinterpret_cast<f32x4*>(p + (int64_t)(t * 16 + lq) * n_total) = acc[t];
 }
 
+constexpr int SK_KC = 128;  // K elements per chunk (four MFMA k-steps)
+constexpr int SK_D = 4;     // chunks a wave keeps in flight (register ring)
+
 // MT = number of 16-row M tiles (M <= 16*MT, MT in 1..4).
-// KC = K elements per staged chunk (ping-pong pair in LDS).
-// PF = W register-prefetch distance in chunks (in-flight W = PF*KC*2 B/row).
-// AB = depth of the A ring in LDS (chunks staged AB-1 ahead).
 // NT: non-temporal W loads (W is streamed exactly once; keeps it out of
 // the LLC so KV/activation lines survive across decode steps).
-template <int MT, int KC, int PF, int AB = 2, bool NT = false>
-__global__ __launch_bounds__(256) void skinny_gemm_kernel(
+//
+// Pipeline (per workgroup, chunk i = K columns [kb + 128 i, +128)):
+//   prologue  issue A_0 W_0 A_1 W_1 ... A_{D-1} W_{D-1}, no wait between
+//             them; ds_write A_0; barrier
+//   step i    MFMAs of chunk i (W from ring slot i % D, A from LDS i & 1)
+//             issue A_{i+D}, W_{i+D} into the slot just consumed
+//             ds_write A_{i+1} into LDS (i+1) & 1; barrier
+// vmcnt retires in issue order, so the order above is what keeps the
+// stream up: A_j and W_j sit together in the queue (within a chunk the
+// compiler may interleave its A pieces among its W loads), the wait for
+// W_i leaves chunks i+1 .. i+D-1 outstanding and the wait for A_{i+1}
+// leaves W_{i+1} and everything newer. The ring is indexed statically
+// (the loop body is one turn of D steps, no register is copied while its
+// load is in flight); the up to 2D-1 chunks after the last full turn take
+// one straight-line path per count, so every wait on every path is an
+// exact compile-time count. 16 (W) + 1024*MT/threads (A) VGPRs per chunk in
+// flight; the launch bound of two waves per SIMD keeps two 4-wave
+// workgroups (or one 8-wave workgroup) on a CU.
+//
+// WAVES = waves per workgroup, 16 rows of W each (N tile = 16*WAVES). The A
+// chunk a workgroup stages is as many bytes as the W chunk of four waves,
+// and it comes through the same per-CU load path (from L2), so at WAVES = 4
+// half of what a CU fetches is A. The tall-K configs run WAVES = 8, one
+// 128-row workgroup per CU: the same W per CU against half the A. A wave's
+// MFMA sequence does not depend on WAVES.
+template <int MT, bool NT = false, int WAVES = 4>
+__global__ __launch_bounds__(64 * WAVES, 2) void skinny_gemm_kernel(
     float* __restrict__ part,   // [nsplits, 16*MT, N] (nsplits > 1)
     bf16* __restrict__ out,     // [M, N] (nsplits == 1)
     const bf16* __restrict__ a, // [M, K] (row stride a_stride)
@@ -87,11 +135,21 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
     const bf16* __restrict__ bias,  // [N] or null (applied when nsplits==1)
     const int m_rows, const int n_total, const int k_total,
     const int k_per_split, const int nsplits, const int64_t a_stride) {
-  constexpr int MROWS = 16 * MT;
+  constexpr int KC = SK_KC;
+  constexpr int D = SK_D;
   constexpr int KSTEPS = KC / 32;
-  const int n0 = blockIdx.x * SK_NT;
+  constexpr int CPT = KC / 8;  // 16 B column-groups per A row
+  constexpr int THREADS = 64 * WAVES;
+  constexpr int NTW = 16 * WAVES;        // N rows per workgroup
+  constexpr int RPP = THREADS / CPT;     // A rows staged per pass
+  constexpr int NIT = 16 * MT / RPP;     // A loads per thread per chunk
+  static_assert(D % 2 == 0, "LDS slot parity follows the ring slot");
+  static_assert(NIT * RPP == 16 * MT, "A chunk must divide over the threads");
+  const int n0 = blockIdx.x * NTW;
   const int kb = blockIdx.y * k_per_split;
   const int ke = min(k_total, kb + k_per_split);
+  const int klen = max(ke - kb, 0);        // multiple of 32
+  const int nch = (klen + KC - 1) / KC;    // chunks, the last may be short
 
   const int tid = threadIdx.x;
   const int wave = tid / WAVE_SIZE;
@@ -102,101 +160,72 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
   // Ping-pong A buffers; the direct-path C transpose reuses the same LDS
   // after the main loop.
   __shared__ __attribute__((aligned(16))) union {
-    bf16 a_buf[AB][64][KC + SK_AP];
-    float c_buf[SK_NT][64 + 1];
+    bf16 a_buf[2][64][KC + SK_AP];
+    float c_buf[NTW][64 + 1];
   } lds;
 
   f32x4 acc[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
 
-  const bf16* wrow = w + (int64_t)(n0 + wave * 16 + lq) * k_total;
+  // The last workgroup of a WAVES = 8 launch may hang over N (N % 128 = 64):
+  // its upper waves stream the last row again and store nothing.
+  const bool wave_live = n0 + wave * 16 < n_total;
+  const bf16* wrow =
+      w + (int64_t)min(n0 + wave * 16 + lq, n_total - 1) * k_total + 8 * la;
 
-  // Cooperative A staging of one chunk into buffer `buf` (no barrier here).
-  // The thread->(row, col) map divides by the COMPILE-TIME chunk width, not
-  // the runtime tail width: a runtime divisor compiles to a ~30-op integer
-  // division sequence per index — PMC r2 (profiles/data/pmc_skinny_r2)
-  // measured 2,200 VALU insts/wave (15x the MFMA count) from exactly this,
-  // serializing the inter-barrier path. Tail chunks just predicate columns.
-  // BRANCHLESS batched staging: all loads issue back-to-back into
-  // registers, then all ds_writes. With per-item guards (`continue` /
-  // row<m_rows branches) the compiler emitted load -> s_waitcnt vmcnt(0) ->
-  // ds_write per item — four FULL vmem drains per chunk that serialized the
-  // whole W stream (ISA audit r2, profiles/data/pmc_skinny_r2). Guards are
-  // replaced by address clamps: duplicated rows / tail columns load real
-  // in-bounds values that the MFMA loop never consumes.
-  auto stage_a = [&](int kc, int buf) {
-    constexpr int CPT = KC / 8;  // 16 B column-groups per row
-    constexpr int NIT = MROWS * CPT / 256;
-    ushort8 gv[NIT];
+  // Cooperative A staging: thread -> (row, 16 B column group) by the
+  // COMPILE-TIME chunk width (a runtime divisor costs a ~30-op division per
+  // index, PMC r2). Branchless: rows past m_rows and columns past k_total
+  // are clamped to real in-bounds values that the MFMAs never consume.
+  const int acol = (tid % CPT) * 8;
+  const bf16* arow[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it)
+    arow[it] = a + (int64_t)min(tid / CPT + it * RPP, m_rows - 1) * a_stride;
+
+  // The register ring: W fragments and the A piece of D chunks.
+  ushort8 wreg[D][KSTEPS];
+  ushort8 areg[D][NIT];
+
+  // Issue every load of chunk `ch`, A ahead of W, nothing waited for.
+  // Addresses past the K-range are clamped into the row (k-steps past ke
+  // are never consumed), so nothing reads past the end of A or W.
+  // A chunk that does not exist (`live` false; prologue of a K-range shorter
+  // than the ring) is still issued, so that the counts stay exact, but
+  // every lane reads the first 16 B of the operand: one line, not sixteen.
+  auto issue = [&](int ch, ushort8 (&wd)[KSTEPS], ushort8 (&ad)[NIT],
+                   bool live) {
+    const int kc = kb + ch * KC;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * 256;
-      const int row = min(i / CPT, m_rows - 1);
-      const int kcol = min(kc + (i % CPT) * 8, k_total - 8);
-      const bf16* base = a + (int64_t)row * a_stride + kcol;
-      gv[it] = *reinterpret_cast<const ushort8*>(base);
+      const bf16* src = arow[it] + min(kc + acol, k_total - 8);
+      ad[it] = *reinterpret_cast<const ushort8*>(live ? src : a);
     }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * 256;
-      const int row = i / CPT;
-      const int col8 = (i % CPT) * 8;
-      ushort8 v = gv[it];
-      *reinterpret_cast<ushort8*>(&lds.a_buf[buf][row][col8]) = v;
-    }
-  };
-
-  // W fragments, register-staged PF chunks ahead (ring of PF+1 buffers,
-  // shifted each chunk — the shifts are v_movs that dual-issue with MFMA).
-  ushort8 wreg[PF + 1][KSTEPS];
-  auto load_w = [&](int kc, ushort8 (&dst)[KSTEPS]) {
-    if (kc >= ke) {
-#pragma unroll
-      for (int s = 0; s < KSTEPS; ++s) dst[s] = ushort8{};
-      return;
-    }
-    const int kw = min(KC, ke - kc);
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
+      const bf16* wsrc = wrow + min(kc + s * 32, k_total - 32);
       const ushort8* src =
-          reinterpret_cast<const ushort8*>(wrow + kc + s * 32 + 8 * la);
-      if (s * 32 >= kw)
-        dst[s] = ushort8{};
-      else if constexpr (NT)
-        dst[s] = __builtin_nontemporal_load(src);
+          reinterpret_cast<const ushort8*>(live ? wsrc : w);
+      if constexpr (NT)
+        wd[s] = __builtin_nontemporal_load(src);
       else
-        dst[s] = *src;
+        wd[s] = *src;
     }
   };
-
-  // A staging issues BEFORE the W prefetch: vmcnt is an ISSUE-ORDERED
-  // counter, so a ds_write waiting on a later-issued A load would otherwise
-  // drain every in-flight W prefetch each chunk — serializing the W stream
-  // (measured: ~2x loss; the reordered kernel overlaps W with compute).
+  auto write_a = [&](const ushort8 (&ad)[NIT], int buf) {
 #pragma unroll
-  for (int p = 0; p < AB - 1; ++p)
-    if (kb + p * KC < ke) stage_a(kb + p * KC, p);
-#pragma unroll
-  for (int p = 0; p <= PF; ++p) load_w(kb + p * KC, wreg[p]);
-  __syncthreads();
-
-  int buf = 0;  // LDS slot holding the current chunk (ring of AB slots)
-  for (int kc = kb; kc < ke; kc += KC) {
-    const int kw = min(KC, ke - kc);  // multiple of 32
-    if (kc + (AB - 1) * KC < ke) {
-      int tgt = buf + (AB - 1);
-      if (tgt >= AB) tgt -= AB;
-      stage_a(kc + (AB - 1) * KC, tgt);  // A loads + ds_writes first (see
-                                         // vmcnt note above)
-    }
-    ushort8 wnext[KSTEPS];
-    load_w(kc + (PF + 1) * KC, wnext);  // issues during this chunk's MFMAs
-
+    for (int it = 0; it < NIT; ++it)
+      *reinterpret_cast<ushort8*>(
+          &lds.a_buf[buf][tid / CPT + it * RPP][acol]) = ad[it];
+  };
+  // MFMAs of one chunk, ascending k; kw = valid width (multiple of 32).
+  auto mfma_chunk = [&](const ushort8 (&wd)[KSTEPS], int buf, int kw) {
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
       if (s * 32 >= kw) break;
-      bf16x8 wfrag = *reinterpret_cast<bf16x8*>(&wreg[0][s]);
+      ushort8 wv = wd[s];
+      bf16x8 wfrag = *reinterpret_cast<bf16x8*>(&wv);
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
         ushort8 af = *reinterpret_cast<const ushort8*>(
@@ -204,19 +233,73 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
         acc[t] = sk_mfma(wfrag, *reinterpret_cast<bf16x8*>(&af), acc[t]);
       }
     }
+  };
+
 #pragma unroll
-    for (int p = 0; p < PF; ++p)
-#pragma unroll
-      for (int s = 0; s < KSTEPS; ++s) wreg[p][s] = wreg[p + 1][s];
-#pragma unroll
-    for (int s = 0; s < KSTEPS; ++s) wreg[PF][s] = wnext[s];
-    __syncthreads();  // staged writes have had >= one full compute phase to
-                      // land; also fences slot reuse
-    buf = (buf + 1 == AB) ? 0 : buf + 1;
+  for (int p = 0; p < D; ++p) {
+    issue(p, wreg[p], areg[p], p < nch);
+    __builtin_amdgcn_sched_barrier(0);  // chunks enter the queue in order
   }
+  write_a(areg[0], 0);
+  __syncthreads();
+
+  int c = 0;  // next chunk to consume; a multiple of D, so it is in slot 0
+  // One turn of the ring: D full chunks from slots 0..D-1, the first
+  // `nrefill` of them refilled with chunk c + D + s (which must exist; it
+  // may be the short tail). Straight-line code, no branch around a load.
+  auto ring_turn = [&](auto nrefill) {
+    constexpr int R = decltype(nrefill)::value;
+#pragma unroll
+    for (int s = 0; s < D; ++s) {
+      // The fences pin the order the counts above rely on: left alone, the
+      // scheduler hoists the ds_writes (and their wait) over the refill.
+      mfma_chunk(wreg[s], s & 1, KC);
+      __builtin_amdgcn_sched_barrier(0);
+      if (s < R) issue(c + D + s, wreg[s], areg[s], true);
+      __builtin_amdgcn_sched_barrier(0);
+      if (s + 1 < D || R > 0) {
+        write_a(areg[(s + 1) % D], (s + 1) & 1);
+        __syncthreads();
+      }
+    }
+    c += D;
+  };
+  // The last `n` chunks (slots 0..n-1), nothing refilled; only the last
+  // one may be short.
+  auto drain = [&](auto nleft) {
+    constexpr int R = decltype(nleft)::value;
+#pragma unroll
+    for (int s = 0; s < R; ++s) {
+      mfma_chunk(wreg[s], s & 1, s + 1 < R ? KC : klen - (c + s) * KC);
+      if (s + 1 < R) {
+        write_a(areg[s + 1], (s + 1) & 1);
+        __syncthreads();
+      }
+    }
+  };
+  using std::integral_constant;
+  // Steady state: every slot refilled, no branch and no vmcnt(0) inside.
+  while (c + 2 * D <= nch) ring_turn(integral_constant<int, D>{});
+  // D..2D-1 chunks left: one partly refilled turn, then the rest. Each
+  // count has its own straight-line path, so its waits are exact counts.
+  switch (nch - c) {
+    case 7: ring_turn(integral_constant<int, 3>{});
+            drain(integral_constant<int, 3>{}); break;
+    case 6: ring_turn(integral_constant<int, 2>{});
+            drain(integral_constant<int, 2>{}); break;
+    case 5: ring_turn(integral_constant<int, 1>{});
+            drain(integral_constant<int, 1>{}); break;
+    case 4: drain(integral_constant<int, 4>{}); break;
+    case 3: drain(integral_constant<int, 3>{}); break;
+    case 2: drain(integral_constant<int, 2>{}); break;
+    case 1: drain(integral_constant<int, 1>{}); break;
+    default: break;  // empty K-range
+  }
+  static_assert(D == 4, "the tail switch is written out for D = 4");
 
   if (nsplits > 1) {
-    store_partials<MT>(part, acc, n_total, n0 + wave * 16 + 4 * la, lq);
+    if (wave_live)
+      store_partials<MT>(part, acc, n_total, n0 + wave * 16 + 4 * la, lq);
     return;
   }
 
@@ -231,9 +314,11 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
     }
   }
   __syncthreads();
-  for (int i = tid; i < m_rows * SK_NT; i += 256) {
-    const int m = i / SK_NT;
-    const int n = i % SK_NT;
+  const int nvalid = min(NTW, n_total - n0);  // 64 or NTW
+  for (int i = tid; i < m_rows * NTW; i += THREADS) {
+    const int m = i / NTW;
+    const int n = i % NTW;
+    if (n >= nvalid) continue;
     float v = lds.c_buf[n][m];
     if (bias != nullptr) v += bf16_bits_to_float(bias[n0 + n]);
     out[(int64_t)m * n_total + n0 + n] = float_to_bf16_bits(v);
@@ -284,9 +369,9 @@ extern "C" void arks_skinny_combine(void* out, const void* part,
                      n_total, nsplits, (int64_t)mrows_pad * n_total);
 }
 
-// M tiles of the kernel that `config` launches for m_rows rows: the default
-// ring (config 0) takes MT from M, the tall-K kernels (1, 2) are built for
-// MT = 4 only.
+// M tiles of the kernel that `config` launches for m_rows rows: config 0
+// takes MT from M, the tall-K configs (1, 2) always run MT = 4 (64-row
+// slabs, which the tall-K plan's consumers expect).
 static int skinny_mt(int m_rows, int config) {
   return config == 0 ? std::min((m_rows + 15) / 16, 4) : 4;
 }
@@ -296,7 +381,7 @@ extern "C" int arks_skinny_slab_rows(int m_rows, int config) {
   return 16 * skinny_mt(m_rows, config);
 }
 
-// config 0: default AB=2 ring, MT from M; 1: tall-K (PF=2, AB=3, MT=4);
+// config 0: MT from M, four waves; 1: tall-K plan (MT=4, eight waves);
 // 2: tall-K with non-temporal W loads.
 // combine = false (nsplits > 1 only) stops after the GEMM: the f32 partials
 // stay in `part` for a consumer kernel that reduces them itself.
@@ -305,7 +390,10 @@ extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
                                  int n_total, int k_total, int k_per_split,
                                  int nsplits, int64_t a_stride, int config,
                                  bool combine, hipStream_t stream) {
-  dim3 grid(n_total / SK_NT, nsplits), block(256);
+  // The tall-K configs run 8 waves (128 rows of W) per workgroup.
+  const int waves = config == 0 ? 4 : 8;
+  dim3 grid((n_total + 16 * waves - 1) / (16 * waves), nsplits);
+  dim3 block(64 * waves);
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, (float*)part,
                        (bf16*)out, (const bf16*)a, (const bf16*)w,
@@ -313,15 +401,15 @@ extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
                        k_per_split, nsplits, a_stride);
   };
   if (config == 2) {
-    launch(skinny_gemm_kernel<4, 128, 2, 3, true>);
+    launch(skinny_gemm_kernel<4, true, 8>);
   } else if (config == 1) {
-    launch(skinny_gemm_kernel<4, 128, 2, 3>);
+    launch(skinny_gemm_kernel<4, false, 8>);
   } else {
     switch (skinny_mt(m_rows, config)) {
-      case 1: launch(skinny_gemm_kernel<1, 128, 1>); break;
-      case 2: launch(skinny_gemm_kernel<2, 128, 1>); break;
-      case 3: launch(skinny_gemm_kernel<3, 128, 1>); break;
-      default: launch(skinny_gemm_kernel<4, 128, 1>); break;
+      case 1: launch(skinny_gemm_kernel<1>); break;
+      case 2: launch(skinny_gemm_kernel<2>); break;
+      case 3: launch(skinny_gemm_kernel<3>); break;
+      default: launch(skinny_gemm_kernel<4>); break;
     }
   }
   if (nsplits > 1 && combine)
