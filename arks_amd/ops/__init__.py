@@ -11,6 +11,7 @@ are unit-testable without a GPU.
 from __future__ import annotations
 
 import os
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -531,37 +532,72 @@ def linear_bf16(x, weight, bias=None, defer: bool = False):
 
 
 # ---------------------------------------------------------------------------
-# W4A16 (4-bit AWQ-style weights, group 128; format in ops/ref.py)
+# Quantized weights, group / block size 128 along K (formats in ops/ref.py):
+#   W4A16  4-bit AWQ-style, packed (qweight, scales, zeros)
+#   W8A16  block-scaled e4m3fn, (w8_weight [N, K], w8_scales f32 [K/128, N])
+# Both run the streaming chunk loop of csrc/wq_stream.h, so one path serves
+# them, driven by a format descriptor.
 # ---------------------------------------------------------------------------
-W4_SKINNY_MAX_M = 64
-# bf16 [N*K] scratch per device for the M > 64 path (dequantize, then the
-# library GEMM). Reserved when a layer is quantized and never grown inside
-# w4_linear, so the pointer captured into decode graphs stays valid.
-_W4_DEQUANT_WS: dict = {}
+# Rows one launch of the shared skinny kernel takes (MT <= 4 tiles of 16).
+W4_SKINNY_MAX_M = W8_SKINNY_MAX_M = _WQ_SKINNY_MAX_M = 64
+# 64 < M <= this: the skinny kernel once per 64-row slab; above it the
+# weight is dequantized into the workspace for the library GEMM. Measured
+# separately per format: crossovers and numbers in w4_linear's and
+# w8_linear's docstrings (W8: the M = 96 / 128 / 256 rows of
+# profiles/w8_gemm.md).
+W4_SLAB_MAX_M = 128
+W8_SLAB_MAX_M = 128
+# bf16 [N*K] scratch per device for the path above the slab limit
+# (dequantize, then the library GEMM): a model is W4 or W8, never both at
+# once, and either way the scratch is one bf16 [N*K] of its largest layer.
+# Reserved when a layer is quantized and never grown inside w4_linear /
+# w8_linear, so the pointer captured into decode graphs stays valid.
+_DEQUANT_WS: dict = {}
 
 
-def w4_reserve_workspace(numel: int, device) -> None:
-    """Make the device's W4 dequant workspace hold at least `numel` bf16
+def reserve_dequant_workspace(numel: int, device) -> None:
+    """Make the device's dequant workspace hold at least `numel` bf16
     elements (the largest quantized layer). Call before capturing graphs."""
     device = torch.device(device)
     if device.type != "cuda":
         return
     key = (device.index if device.index is not None
            else torch.cuda.current_device(),)
-    ws = _W4_DEQUANT_WS.get(key)
+    ws = _DEQUANT_WS.get(key)
     if ws is None or ws.numel() < numel:
-        _W4_DEQUANT_WS[key] = torch.empty(numel, dtype=torch.bfloat16,
-                                          device=device)
+        _DEQUANT_WS[key] = torch.empty(numel, dtype=torch.bfloat16,
+                                       device=device)
 
 
-def _w4_plan(M: int, N: int, K: int):
-    """Routing rule of the W4 skinny GEMM: (nw, nsplits, k_per_split, mrows).
-    nw = 64-row N sub-tiles per workgroup, mrows = 16 * MT the slab height of
-    the split-K partials, k_per_split a multiple of the 128 group.
+class _WqFormat(NamedTuple):
+    """What the shared path needs to know about a weight format. The native
+    entry points are {name}_skinny_gemm, {name}_skinny_gemm_partials and
+    {name}_dequant, each taking the weight's tensors in place of one."""
+    name: str
+    shape: Callable        # weight tuple -> (N, K)
+    ref_linear: Callable   # CPU reference: (x, weight tuple, bias) -> y
+    ref_dequant: Callable  # CPU reference: weight tuple -> f32 [N, K]
+    slab_max_m: int        # W4_SLAB_MAX_M / W8_SLAB_MAX_M
 
-    MEASURED on an MI355X (in-graph, weights cycled past the LLC; sweep over
-    nw x nsplits at M = 1/16/32/64 on the Qwen2.5-7B shapes, tables in
-    profiles/w4_gemm.md):
+
+_W4 = _WqFormat(
+    "w4", lambda w: (w[0].shape[0], w[0].shape[1] * 8), ref.w4_linear,
+    lambda w: ref.w4_dequant(*ref.w4_unpack(w)), W4_SLAB_MAX_M)
+_W8 = _WqFormat(
+    "w8", lambda w: tuple(w[0].shape),
+    lambda x, w, bias: ref.w8_linear(x, *w, bias),
+    lambda w: ref.w8_dequant(*w), W8_SLAB_MAX_M)
+
+
+def _wq_plan(M: int, N: int, K: int):
+    """Routing rule of the W4 and W8 skinny GEMMs: (nw, nsplits, k_per_split,
+    mrows). nw = 64-row N sub-tiles per workgroup, mrows = 16 * MT the slab
+    height of the split-K partials, k_per_split a multiple of the 128 group /
+    scale block.
+
+    MEASURED for W4 on an MI355X (in-graph, weights cycled past the LLC;
+    sweep over nw x nsplits at M = 1/16/32/64 on the Qwen2.5-7B shapes,
+    tables in profiles/w4_gemm.md):
     - nw = 2 pays only above M = 32, where the activation re-read per tile
       outweighs the halved workgroup count (down-proj M=64: 27.8 us vs 30.6;
       M=16: 19.5 vs 17.5; qkv/o/gate_up within 0.6 us of each other at 32).
@@ -570,7 +606,16 @@ def _w4_plan(M: int, N: int, K: int):
       32-38 unsplit), down-proj 14-15 (28 us vs 150-180 unsplit).
     - once the N tiles alone reach 256 workgroups a split's partials cost
       more than they hide (gate_up at nw=1, M=16: 26.4 us unsplit, 32.4 with
-      2 splits, 28.8 with 3; at M=64/nw=2 3 splits would gain 7%)."""
+      2 splits, 28.8 with 3; at M=64/nw=2 3 splits would gain 7%).
+
+    The W8 kernel shares the W4 kernel's staging, grid and partial layout, so
+    it takes the W4 rule; it was not swept again cell by cell for W8.
+    MEASURED as a whole on an MI355X with scripts/bench_w8.py (in-graph,
+    weights cycled past the LLC; profiles/w8_gemm.md): with this plan every
+    M <= 64 row of the Qwen2.5-7B shapes beats bf16 (qkv 10.1-16.5 us vs
+    14.1-19.3, o 9.9-14.7 vs 12.1-15.9, gate_up 34.0-51.7 vs 56.8-63.1, down
+    22.3-29.5 vs 42.4-110.9), gate_up unsplit at 4.1 TB/s of weight bytes
+    at M = 1."""
     nw = 2 if (M > 32 and N % 128 == 0) else 1
     ntiles = N // (64 * nw)
     chunks = K // 128
@@ -584,71 +629,97 @@ def _w4_plan(M: int, N: int, K: int):
     return nw, nsplits, k_per_split, 16 * min(-(-M // 16), 4)
 
 
-def w4_dequant(packed, out=None):
-    """bf16 [N, K] from a packed W4 weight, via w4_dequant_kernel on GPU."""
-    qweight, scales, zeros = packed
-    N, K = qweight.shape[0], qweight.shape[1] * 8
-    if not qweight.is_cuda:
-        return ref.w4_dequant(*ref.w4_unpack(packed)).to(torch.bfloat16)
+_w4_plan = _w8_plan = _wq_plan
+
+
+def _wq_dequant(fmt: _WqFormat, weight, out=None):
+    N, K = fmt.shape(weight)
+    if not weight[0].is_cuda:
+        return fmt.ref_dequant(weight).to(torch.bfloat16)
     if out is None:
-        out = torch.empty(N * K, dtype=torch.bfloat16, device=qweight.device)
-    _native().w4_dequant(out, qweight, scales, zeros)
+        out = torch.empty(N * K, dtype=torch.bfloat16,
+                          device=weight[0].device)
+    getattr(_native(), fmt.name + "_dequant")(out, *weight)
     return out[: N * K].view(N, K)
 
 
-# 64 < M <= this: the skinny kernel once per 64-row slab; above it the
-# weight is dequantized into the workspace for the library GEMM. Crossover
-# and numbers in w4_linear's docstring.
-W4_SLAB_MAX_M = 128
+def w4_dequant(packed, out=None):
+    """bf16 [N, K] from a packed W4 weight, via w4_dequant_kernel on GPU."""
+    return _wq_dequant(_W4, packed, out)
 
 
-def _w4_skinny(x, packed, bias, defer: bool, plan, out=None):
-    """One launch of the W4 skinny kernel for M <= 64 rows (plus the combine
-    when it splits K and the result is not deferred)."""
-    qweight, scales, zeros = packed
+def w8_dequant(weight, out=None):
+    """bf16 [N, K] from a W8 weight (w8_weight, w8_scales), via
+    w8_dequant_kernel on GPU."""
+    return _wq_dequant(_W8, weight, out)
+
+
+def _wq_skinny(fmt: _WqFormat, x, weight, bias, defer: bool, plan, out=None):
+    """One launch of the format's skinny kernel for M <= 64 rows (plus the
+    combine when it splits K and the result is not deferred)."""
     M, K = x.shape
-    N = qweight.shape[0]
+    N = fmt.shape(weight)[0]
     if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
         x = x.contiguous()
-    nw, nsplits, k_per_split, mrows = plan or _w4_plan(M, N, K)
+    nw, nsplits, k_per_split, mrows = plan or _wq_plan(M, N, K)
     part = (_skinny_ws(nsplits, N, mrows, x.device) if nsplits > 1
             else x.new_empty(0, dtype=torch.float32))
     if defer and nsplits > 1 and _SPLITK_FUSE:
-        _native().w4_skinny_gemm_partials(part, x, qweight, scales, zeros,
-                                          k_per_split, nsplits, nw)
+        getattr(_native(), fmt.name + "_skinny_gemm_partials")(
+            part, x, *weight, k_per_split, nsplits, nw)
         return SplitKPending(part, nsplits, mrows, M, N, bias,
                              (x.device.index,))
     if out is None:
         out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    _native().w4_skinny_gemm(out, part, x, qweight, scales, zeros, bias,
-                             k_per_split, nsplits, nw)
+    getattr(_native(), fmt.name + "_skinny_gemm")(
+        out, part, x, *weight, bias, k_per_split, nsplits, nw)
     return out
 
 
-def _w4_slabs(x, packed, bias):
+def _wq_slabs(fmt: _WqFormat, x, weight, bias):
     """M > 64 through the skinny kernel, 64 rows at a time, each slab
     written straight into its rows of the output."""
     M = x.shape[0]
-    out = torch.empty((M, packed[0].shape[0]), dtype=x.dtype, device=x.device)
-    for r in range(0, M, W4_SKINNY_MAX_M):
-        _w4_skinny(x[r:r + W4_SKINNY_MAX_M], packed, bias, False, None,
-                   out=out[r:r + W4_SKINNY_MAX_M])
+    out = torch.empty((M, fmt.shape(weight)[0]), dtype=x.dtype,
+                      device=x.device)
+    for r in range(0, M, _WQ_SKINNY_MAX_M):
+        _wq_skinny(fmt, x[r:r + _WQ_SKINNY_MAX_M], weight, bias, False, None,
+                   out=out[r:r + _WQ_SKINNY_MAX_M])
     return out
 
 
-def _w4_dequant_linear(x, packed, bias):
-    """M > 64 through the library GEMM on the weight expanded to bf16 in the
-    device's reserved workspace."""
-    N, K = packed[0].shape[0], packed[0].shape[1] * 8
-    ws = _W4_DEQUANT_WS.get((x.device.index,))
+def _wq_dequant_linear(fmt: _WqFormat, x, weight, bias):
+    """M above the slab limit through the library GEMM on the weight
+    expanded to bf16 in the device's reserved dequant workspace."""
+    N, K = fmt.shape(weight)
+    ws = _DEQUANT_WS.get((x.device.index,))
     if ws is None or ws.numel() < N * K:
         raise RuntimeError(
-            f"W4 dequant workspace missing or smaller than {N}x{K}: "
-            "call ops.w4_reserve_workspace when the layer is quantized"
+            f"dequant workspace missing or smaller than {N}x{K}: "
+            "call ops.reserve_dequant_workspace when the layer is quantized"
         )
     import torch.nn.functional as F
 
-    return F.linear(x, w4_dequant(packed, ws), bias)
+    return F.linear(x, _wq_dequant(fmt, weight, ws), bias)
+
+
+def _wq_linear(fmt: _WqFormat, x, weight, bias, defer: bool, plan):
+    if not x.is_cuda:
+        return fmt.ref_linear(x, weight, bias)
+    if x.dim() != 2 or x.dtype != torch.bfloat16:
+        raise ValueError(f"{fmt.name}_linear needs a 2-D bf16 input, got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    M, K = x.shape
+    N, wk = fmt.shape(weight)
+    if wk != K:
+        raise ValueError(f"{fmt.name}_linear: x has K={K}, weight K={wk}")
+    if M == 0:
+        return x.new_empty((0, N))
+    if M <= _WQ_SKINNY_MAX_M:
+        return _wq_skinny(fmt, x, weight, bias, defer, plan)
+    if M <= fmt.slab_max_m:
+        return _wq_slabs(fmt, x, weight, bias)
+    return _wq_dequant_linear(fmt, x, weight, bias)
 
 
 def w4_linear(x, packed, bias=None, defer: bool = False, plan=None):
@@ -670,127 +741,7 @@ def w4_linear(x, packed, bias=None, defer: bool = False, plan=None):
     size where slabs were seen to win. Above M = 64 bf16 weights are faster
     than either route on qkv/o/gate_up (23 / 23 / 70 us at 128): int4 trades
     large-batch and prefill speed for decode speed and memory."""
-    qweight, scales, zeros = packed
-    if not x.is_cuda:
-        return ref.w4_linear(x, packed, bias)
-    if x.dim() != 2 or x.dtype != torch.bfloat16:
-        raise ValueError(f"w4_linear needs a 2-D bf16 input, got "
-                         f"{tuple(x.shape)} {x.dtype}")
-    M, K = x.shape
-    N = qweight.shape[0]
-    if qweight.shape[1] * 8 != K:
-        raise ValueError(f"w4_linear: x has K={K}, weight K="
-                         f"{qweight.shape[1] * 8}")
-    if M == 0:
-        return x.new_empty((0, N))
-    if M <= W4_SKINNY_MAX_M:
-        return _w4_skinny(x, packed, bias, defer, plan)
-    if M <= W4_SLAB_MAX_M:
-        return _w4_slabs(x, packed, bias)
-    return _w4_dequant_linear(x, packed, bias)
-
-
-# ---------------------------------------------------------------------------
-# W8A16 (block-scaled e4m3fn weights, 128x128 blocks; format in ops/ref.py)
-# ---------------------------------------------------------------------------
-W8_SKINNY_MAX_M = 64
-# 64 < M <= this: the skinny kernel once per 64-row slab; above it the
-# weight is dequantized into the workspace for the library GEMM. Set from
-# the M = 96 / 128 / 256 rows of profiles/w8_gemm.md (numbers in w8_linear's
-# docstring).
-W8_SLAB_MAX_M = 128
-
-
-def _w8_plan(M: int, N: int, K: int):
-    """Routing rule of the W8 skinny GEMM: (nw, nsplits, k_per_split, mrows),
-    with the meaning of _w4_plan's tuple: nw = 64-row N sub-tiles per
-    workgroup, mrows = 16 * MT the slab height of the split-K partials,
-    k_per_split a multiple of the 128 scale block.
-
-    The kernel shares the W4 kernel's staging, grid and partial layout, so
-    the rule is the W4 one (its nw x nsplits sweep is in
-    profiles/w4_gemm.md); it was not swept again cell by cell for W8.
-    MEASURED as a whole on an MI355X with scripts/bench_w8.py (in-graph,
-    weights cycled past the LLC; profiles/w8_gemm.md): with this plan every
-    M <= 64 row of the Qwen2.5-7B shapes beats bf16 (qkv 10.1-16.5 us vs
-    14.1-19.3, o 9.9-14.7 vs 12.1-15.9, gate_up 34.0-51.7 vs 56.8-63.1, down
-    22.3-29.5 vs 42.4-110.9), gate_up unsplit at 4.1 TB/s of weight bytes
-    at M = 1."""
-    nw = 2 if (M > 32 and N % 128 == 0) else 1
-    ntiles = N // (64 * nw)
-    chunks = K // 128
-    if ntiles >= 256:
-        nsplits = 1
-    else:
-        target = 800 if nw == 1 else 448
-        nsplits = max(1, min(-(-target // ntiles), chunks // 4))
-    k_per_split = -(-chunks // nsplits) * 128
-    nsplits = -(-K // k_per_split)
-    return nw, nsplits, k_per_split, 16 * min(-(-M // 16), 4)
-
-
-def w8_dequant(weight, out=None):
-    """bf16 [N, K] from a W8 weight (w8_weight, w8_scales), via
-    w8_dequant_kernel on GPU."""
-    w8, scales = weight
-    N, K = w8.shape
-    if not w8.is_cuda:
-        return ref.w8_dequant(w8, scales).to(torch.bfloat16)
-    if out is None:
-        out = torch.empty(N * K, dtype=torch.bfloat16, device=w8.device)
-    _native().w8_dequant(out, w8, scales)
-    return out[: N * K].view(N, K)
-
-
-def _w8_skinny(x, weight, bias, defer: bool, plan, out=None):
-    """One launch of the W8 skinny kernel for M <= 64 rows (plus the combine
-    when it splits K and the result is not deferred)."""
-    w8, scales = weight
-    M, K = x.shape
-    N = w8.shape[0]
-    if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
-    nw, nsplits, k_per_split, mrows = plan or _w8_plan(M, N, K)
-    part = (_skinny_ws(nsplits, N, mrows, x.device) if nsplits > 1
-            else x.new_empty(0, dtype=torch.float32))
-    if defer and nsplits > 1 and _SPLITK_FUSE:
-        _native().w8_skinny_gemm_partials(part, x, w8, scales, k_per_split,
-                                          nsplits, nw)
-        return SplitKPending(part, nsplits, mrows, M, N, bias,
-                             (x.device.index,))
-    if out is None:
-        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    _native().w8_skinny_gemm(out, part, x, w8, scales, bias, k_per_split,
-                             nsplits, nw)
-    return out
-
-
-def _w8_slabs(x, weight, bias):
-    """M > 64 through the skinny kernel, 64 rows at a time, each slab
-    written straight into its rows of the output."""
-    M = x.shape[0]
-    out = torch.empty((M, weight[0].shape[0]), dtype=x.dtype, device=x.device)
-    for r in range(0, M, W8_SKINNY_MAX_M):
-        _w8_skinny(x[r:r + W8_SKINNY_MAX_M], weight, bias, False, None,
-                   out=out[r:r + W8_SKINNY_MAX_M])
-    return out
-
-
-def _w8_dequant_linear(x, weight, bias):
-    """M above the slab limit through the library GEMM on the weight
-    expanded to bf16 in the device's reserved dequant workspace (the one
-    w4_reserve_workspace manages: a model is W4 or W8, never both at once,
-    and either way the scratch is one bf16 [N*K] of its largest layer)."""
-    N, K = weight[0].shape
-    ws = _W4_DEQUANT_WS.get((x.device.index,))
-    if ws is None or ws.numel() < N * K:
-        raise RuntimeError(
-            f"dequant workspace missing or smaller than {N}x{K}: "
-            "call ops.w4_reserve_workspace when the layer is quantized"
-        )
-    import torch.nn.functional as F
-
-    return F.linear(x, w8_dequant(weight, ws), bias)
+    return _wq_linear(_W4, x, packed, bias, defer, plan)
 
 
 def w8_linear(x, weight, bias=None, defer: bool = False, plan=None):
@@ -813,23 +764,7 @@ def w8_linear(x, weight, bias=None, defer: bool = False, plan=None):
     the last size where slabs were seen to win. Above M = 64 bf16 weights are
     faster than either route on qkv/o/gate_up (23 / 23 / 70 us at 128); down
     stays faster in W8 up to 128 rows."""
-    w8, scales = weight
-    if not x.is_cuda:
-        return ref.w8_linear(x, w8, scales, bias)
-    if x.dim() != 2 or x.dtype != torch.bfloat16:
-        raise ValueError(f"w8_linear needs a 2-D bf16 input, got "
-                         f"{tuple(x.shape)} {x.dtype}")
-    M, K = x.shape
-    N = w8.shape[0]
-    if w8.shape[1] != K:
-        raise ValueError(f"w8_linear: x has K={K}, weight K={w8.shape[1]}")
-    if M == 0:
-        return x.new_empty((0, N))
-    if M <= W8_SKINNY_MAX_M:
-        return _w8_skinny(x, weight, bias, defer, plan)
-    if M <= W8_SLAB_MAX_M:
-        return _w8_slabs(x, weight, bias)
-    return _w8_dequant_linear(x, weight, bias)
+    return _wq_linear(_W8, x, weight, bias, defer, plan)
 
 
 def w4_moe_gemm(a, packed, counts, pairs, src_div: int, max_rows: int,

@@ -140,7 +140,7 @@ void arks_w4_skinny_gemm(void* part, void* out, const void* a, const void* qw,
                          int k_total, int k_per_split, int nsplits,
                          int64_t a_stride, int nw, bool combine,
                          hipStream_t stream);
-int arks_w4_slab_rows(int m_rows);
+int arks_wq_slab_rows(int m_rows);
 void arks_w4_dequant(void* out, const void* qw, const void* scales,
                      const void* zeros, int n_total, int k_total,
                      hipStream_t stream);
@@ -154,7 +154,6 @@ void arks_w8_skinny_gemm(void* part, void* out, const void* a, const void* w8,
                          int n_total, int k_total, int k_per_split,
                          int nsplits, int64_t a_stride, int nw, bool combine,
                          hipStream_t stream);
-int arks_w8_slab_rows(int m_rows);
 void arks_w8_dequant(void* out, const void* w8, const void* scales,
                      int n_total, int k_total, hipStream_t stream);
 void arks_moe_route(void* counts, void* pairs, const void* ids, int n_pairs,
@@ -532,20 +531,29 @@ std::pair<int64_t, int64_t> check_w4_packed(const torch::Tensor& qw,
   return {n, k};
 }
 
-// nw = 64-row N sub-tiles per workgroup (1 or 2); combine = false leaves the
-// split-K partials in `part` (bias is then applied by the consumer).
-void w4_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
-                         torch::Tensor a, torch::Tensor qw,
-                         torch::Tensor scales, torch::Tensor zeros,
-                         c10::optional<torch::Tensor> bias,
-                         int64_t k_per_split, int64_t nsplits, int64_t nw,
-                         bool combine) {
-  const auto [n, k] = check_w4_packed(qw, scales, zeros);
+// Everything a dense quantized skinny GEMM (w4_/w8_skinny_gemm[_partials])
+// checks that does not depend on the weight format, for a weight [n, k] on
+// `dev`. nw = 64-row N sub-tiles per workgroup (1 or 2); combine = false
+// leaves the split-K partials in `part` (bias is then applied by the
+// consumer). Returns the pointers the launch takes: part, out and bias, each
+// null where the kernel must not touch it.
+struct WqSkinnyArgs {
+  void* part;
+  void* out;
+  const void* bias;
+};
+WqSkinnyArgs check_wq_skinny(const torch::Tensor& out,
+                             const torch::Tensor& part,
+                             const torch::Tensor& a,
+                             const c10::optional<torch::Tensor>& bias,
+                             int64_t n, int64_t k, c10::Device dev,
+                             int64_t k_per_split, int64_t nsplits, int64_t nw,
+                             bool combine) {
   check_bf16_rowstrided(a, "a");
   TORCH_CHECK(a.dim() == 2 && a.size(1) == k, "a must be [M, K]");
-  TORCH_CHECK(a.device() == qw.device());
+  TORCH_CHECK(a.device() == dev);
   const int64_t m = a.size(0);
-  TORCH_CHECK(m >= 1 && m <= 64, "w4_skinny_gemm needs 1 <= M <= 64");
+  TORCH_CHECK(m >= 1 && m <= 64, "wq_skinny_gemm needs 1 <= M <= 64");
   TORCH_CHECK(a.stride(0) % 8 == 0 &&
               reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
               "a rows must be 16-byte aligned");
@@ -554,15 +562,15 @@ void w4_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
   TORCH_CHECK(nsplits >= 1 && k_per_split >= 128 && k_per_split % 128 == 0 &&
               nsplits * k_per_split >= k && (nsplits - 1) * k_per_split < k,
               "splits of a multiple of 128 must cover K exactly");
-  const int mrows = arks_w4_slab_rows((int)m);
-  const void* bias_ptr = nullptr;
+  WqSkinnyArgs r{nullptr, nullptr, nullptr};
   if (combine) {
     check_bf16_contig(out, "out");
     TORCH_CHECK(out.dim() == 2 && out.size(0) == m && out.size(1) == n);
+    r.out = out.data_ptr();
     if (bias.has_value()) {
       check_bf16_contig(*bias, "bias");
       TORCH_CHECK(bias->numel() == n);
-      bias_ptr = bias->data_ptr();
+      r.bias = bias->data_ptr();
     }
   } else {
     TORCH_CHECK(nsplits > 1, "partials-only needs nsplits > 1");
@@ -570,14 +578,26 @@ void w4_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
   if (nsplits > 1) {
     TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
                 part.is_contiguous() &&
-                part.numel() >= nsplits * n * mrows &&
+                part.numel() >= nsplits * n * arks_wq_slab_rows((int)m) &&
                 reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
-                "w4_skinny_gemm workspace too small");
+                "wq_skinny_gemm workspace too small");
+    r.part = part.data_ptr();
   }
-  arks_w4_skinny_gemm(nsplits > 1 ? part.data_ptr() : nullptr,
-                      combine ? out.data_ptr() : nullptr, a.data_ptr(),
-                      qw.data_ptr(), scales.data_ptr(), zeros.data_ptr(),
-                      bias_ptr, (int)m, (int)n, (int)k, (int)k_per_split,
+  return r;
+}
+
+void w4_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
+                         torch::Tensor a, torch::Tensor qw,
+                         torch::Tensor scales, torch::Tensor zeros,
+                         c10::optional<torch::Tensor> bias,
+                         int64_t k_per_split, int64_t nsplits, int64_t nw,
+                         bool combine) {
+  const auto [n, k] = check_w4_packed(qw, scales, zeros);
+  const auto p = check_wq_skinny(out, part, a, bias, n, k, qw.device(),
+                                 k_per_split, nsplits, nw, combine);
+  arks_w4_skinny_gemm(p.part, p.out, a.data_ptr(), qw.data_ptr(),
+                      scales.data_ptr(), zeros.data_ptr(), p.bias,
+                      (int)a.size(0), (int)n, (int)k, (int)k_per_split,
                       (int)nsplits, a.stride(0), (int)nw, combine,
                       current_stream());
 }
@@ -631,8 +651,6 @@ std::pair<int64_t, int64_t> check_w8_weight(const torch::Tensor& w8,
   return {n, k};
 }
 
-// nw = 64-row N sub-tiles per workgroup (1 or 2); combine = false leaves the
-// split-K partials in `part` (bias is then applied by the consumer).
 void w8_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
                          torch::Tensor a, torch::Tensor w8,
                          torch::Tensor scales,
@@ -640,44 +658,12 @@ void w8_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
                          int64_t k_per_split, int64_t nsplits, int64_t nw,
                          bool combine) {
   const auto [n, k] = check_w8_weight(w8, scales);
-  check_bf16_rowstrided(a, "a");
-  TORCH_CHECK(a.dim() == 2 && a.size(1) == k, "a must be [M, K]");
-  TORCH_CHECK(a.device() == w8.device());
-  const int64_t m = a.size(0);
-  TORCH_CHECK(m >= 1 && m <= 64, "w8_skinny_gemm needs 1 <= M <= 64");
-  TORCH_CHECK(a.stride(0) % 8 == 0 &&
-              reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
-              "a rows must be 16-byte aligned");
-  TORCH_CHECK((nw == 1 || nw == 2) && n % (64 * nw) == 0,
-              "nw in {1, 2} with N % (64 * nw) == 0");
-  TORCH_CHECK(nsplits >= 1 && k_per_split >= 128 && k_per_split % 128 == 0 &&
-              nsplits * k_per_split >= k && (nsplits - 1) * k_per_split < k,
-              "splits of a multiple of 128 must cover K exactly");
-  const int mrows = arks_w8_slab_rows((int)m);
-  const void* bias_ptr = nullptr;
-  if (combine) {
-    check_bf16_contig(out, "out");
-    TORCH_CHECK(out.dim() == 2 && out.size(0) == m && out.size(1) == n);
-    if (bias.has_value()) {
-      check_bf16_contig(*bias, "bias");
-      TORCH_CHECK(bias->numel() == n);
-      bias_ptr = bias->data_ptr();
-    }
-  } else {
-    TORCH_CHECK(nsplits > 1, "partials-only needs nsplits > 1");
-  }
-  if (nsplits > 1) {
-    TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
-                part.is_contiguous() &&
-                part.numel() >= nsplits * n * mrows &&
-                reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
-                "w8_skinny_gemm workspace too small");
-  }
-  arks_w8_skinny_gemm(nsplits > 1 ? part.data_ptr() : nullptr,
-                      combine ? out.data_ptr() : nullptr, a.data_ptr(),
-                      w8.data_ptr(), scales.data_ptr(), bias_ptr, (int)m,
-                      (int)n, (int)k, (int)k_per_split, (int)nsplits,
-                      a.stride(0), (int)nw, combine, current_stream());
+  const auto p = check_wq_skinny(out, part, a, bias, n, k, w8.device(),
+                                 k_per_split, nsplits, nw, combine);
+  arks_w8_skinny_gemm(p.part, p.out, a.data_ptr(), w8.data_ptr(),
+                      scales.data_ptr(), p.bias, (int)a.size(0), (int)n,
+                      (int)k, (int)k_per_split, (int)nsplits, a.stride(0),
+                      (int)nw, combine, current_stream());
 }
 
 void w8_skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
@@ -767,7 +753,7 @@ void w4_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor qw,
   const int64_t slabs = (max_rows + 63) / 64;
   TORCH_CHECK(slabs <= 65535, "max_rows too large");
   // NW = 2 halves the activation re-read per tile and pays above 32 rows
-  // (ops._w4_plan); a slab of an expert's list rarely holds that many
+  // (ops._wq_plan); a slab of an expert's list rarely holds that many
   // unless the batch does.
   const int nw = (max_rows > 32 && n % 128 == 0) ? 2 : 1;
   arks_w4_moe_gemm(out.data_ptr(), a.data_ptr(), qw.data_ptr(),

@@ -18,42 +18,24 @@
 // high halves into a bf16 pair. 8 VALU ops per 8 weights, no rounding
 // anywhere.
 //
-// w8_skinny_gemm_kernel (M <= 64) is w4_skinny_gemm_kernel's design fed by
-// bytes (read the notes there and in skinny_gemm.hip first): grid =
-// (N/(64*NW), nsplits); swapped operands (A-frag = W rows, B-frag =
-// activations), C fragment at [n = 4*la+r, m = lane%16]; A staged through a
-// 2-slot LDS ring, batched and branchless, its loads issued BEFORE the W
-// prefetch (vmcnt is issue-ordered) and its LDS writes after the chunk's
-// MFMAs; W prefetched PF chunks ahead in a register ring with compile-time
-// slots, 16 B per lane per load.
-//   A lane's W bytes of a chunk are 32 CONSECUTIVE k of its row (two 16 B
-//   loads; k = 32*la + 8*s + j for the chunk's four k-steps s), and the
-//   activation fragment is read from LDS at the same 32*la + 8*s.
+// w8_skinny_gemm_kernel (M <= 64) is the streaming chunk loop of wq_stream.h
+// (design, staging and issue order are described there) fed by bytes:
+//   grid = (N/(64*NW), nsplits). A lane's chunk of W is two 16 B loads per
+//   sub-tile, the 32 bytes k = 32*la .. 32*la + 31 of its row, two dwords
+//   per k-step, plus the f32 scales of its four C-fragment rows.
 //   KC = 128 = one scale block along K, so a chunk's scale is constant per n
 //   row: the chunk accumulates into its own f32 fragment and contributes
 //       s[n] * acc_chunk.
-//   No zero-point, hence no activation sums (the W4 kernel's asum).
-//   Split-K partials use skinny_gemm.hip's [split][16*MT rows][N] f32 layout
-//   so splitk_add_rmsnorm / splitk_rope_cache / skinny_combine read them
-//   unchanged. N % (64*NW) == 0, K % 128 == 0, k_per_split % 128 == 0.
-// The body is a copy of the W4 loop rather than a shared template so that
-// the W4 kernel's code generation does not move.
+//   No zero-point, hence no activation sums (the W4 format's asum) and no
+//   LDS for them.
 //
 // w8_dequant_kernel expands the weight to bf16 [N, K] for the library GEMM
 // (M above the slab limit).
-#include "common.h"
-
-#include <algorithm>
+#include "wq_stream.h"
 
 namespace arks {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-constexpr int W8_KC = 128;  // K per chunk = scale block
-constexpr int W8_AP = 8;    // a_lds row pad (bf16): rows stay 16B-aligned
 
 // Two e4m3 bytes (the low or the high half of `w`) as a bf16 pair, exact.
 template <bool HI>
@@ -81,12 +63,64 @@ __device__ __forceinline__ bf16x8 w8_frag(const uint32_t d0,
   return c.b;
 }
 
-// One chunk of W for a lane: per N sub-tile the 32 bytes of its A-fragment
-// row, plus the scales of the four C-fragment rows it accumulates.
-template <int NW>
-struct W8Chunk {
-  u32x4 q[NW][2];
-  f32x4 sc[NW];
+// The W8 weight format of wq_stream: one [N, K] weight as a lane sees it.
+template <int NW_>
+struct W8Weights {
+  static constexpr int NW = NW_;
+  static constexpr bool ASUM = false;
+
+  // One chunk of W for a lane: per N sub-tile the 32 bytes of its A-fragment
+  // row, plus the scales of the four C-fragment rows it accumulates.
+  struct Chunk {
+    u32x4 q[NW][2];
+    f32x4 sc[NW];
+  };
+
+  const uint8_t* wrow;  // this lane's 32 B of chunk 0 in sub-tile 0
+  const float* scales;  // [K/128, N]
+  int nc, n_total, k_total;
+
+  __device__ __forceinline__ W8Weights(const WqLane& ln, const uint8_t* w8,
+                                       const float* scales, const int n_total,
+                                       const int k_total)
+      : wrow(w8 + (int64_t)(ln.n0 + ln.wave * 16 + ln.lq) * k_total +
+             32 * ln.la),
+        scales(scales),
+        nc(ln.nc),
+        n_total(n_total),
+        k_total(k_total) {}
+
+  __device__ __forceinline__ void load(const int kc, Chunk& dst) const {
+    const int64_t g = (int64_t)(kc / WQ_KC) * n_total;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+      const uint8_t* p = wrow + (int64_t)j * 64 * k_total + kc;
+      dst.q[j][0] = *reinterpret_cast<const u32x4*>(p);
+      dst.q[j][1] = *reinterpret_cast<const u32x4*>(p + 16);
+      dst.sc[j] = *reinterpret_cast<const f32x4*>(scales + g + nc + j * 64);
+    }
+  }
+
+  static __device__ __forceinline__ bf16x8 frag(const Chunk& c, const int j,
+                                                const int s) {
+    return w8_frag(c.q[j][s / 2][2 * (s % 2)], c.q[j][s / 2][2 * (s % 2) + 1]);
+  }
+
+  // acc += s * cacc
+  template <int MT, typename Lds>
+  static __device__ __forceinline__ void scale(f32x4 (&acc)[NW][MT],
+                                               const f32x4 (&cacc)[NW][MT],
+                                               const Chunk& c, const Lds&,
+                                               const int, const int) {
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+#pragma unroll
+      for (int t = 0; t < MT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          acc[j][t][r] =
+              __builtin_fmaf(c.sc[j][r], cacc[j][t][r], acc[j][t][r]);
+  }
 };
 
 template <int MT, int NW, int PF>
@@ -99,167 +133,11 @@ __global__ __launch_bounds__(256) void w8_skinny_gemm_kernel(
     const bf16* __restrict__ bias,   // [N] or null (applied when nsplits==1)
     const int m_rows, const int n_total, const int k_total,
     const int k_per_split, const int nsplits, const int64_t a_stride) {
-  constexpr int MROWS = 16 * MT;
-  constexpr int NT = 64 * NW;
-  constexpr int KC = W8_KC;
-  const int n0 = blockIdx.x * NT;
-  const int kb = blockIdx.y * k_per_split;
-  const int ke = min(k_total, kb + k_per_split);  // multiple of 128
-
-  const int tid = threadIdx.x;
-  const int wave = tid / WAVE_SIZE;
-  const int lane = tid % WAVE_SIZE;
-  const int lq = lane % 16;
-  const int la = lane / 16;
-
-  __shared__ __attribute__((aligned(16))) union {
-    bf16 a_buf[2][64][KC + W8_AP];
-    float c_buf[NT][64 + 1];
-  } lds;
-
-  f32x4 acc[NW][MT];
-#pragma unroll
-  for (int j = 0; j < NW; ++j)
-#pragma unroll
-    for (int t = 0; t < MT; ++t) acc[j][t] = {0.f, 0.f, 0.f, 0.f};
-
-  // A-fragment row of this lane in sub-tile j: n0 + 64*j + 16*wave + lq;
-  // its C-fragment rows: n0 + 64*j + 16*wave + 4*la + r.
-  const uint8_t* wrow = w8 + (int64_t)(n0 + wave * 16 + lq) * k_total + 32 * la;
-  const int nc = n0 + wave * 16 + 4 * la;
-
-  // Staging of one 128-wide chunk: the global loads of chunk c+1 issue at
-  // the top of iteration c and their ds_writes come after its MFMAs. No
-  // tails (K and the split ranges are multiples of 128), no per-item
-  // guards. Rows >= m_rows are clamped duplicates that no reader consumes.
-  constexpr int NIT = MROWS * 16 / 256;  // == MT
-  auto load_a = [&](int kc, ushort8 (&gv)[NIT]) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * 256;
-      const int row = min(i / 16, m_rows - 1);
-      gv[it] = *reinterpret_cast<const ushort8*>(
-          a + (int64_t)row * a_stride + kc + (i % 16) * 8);
-    }
-  };
-  auto store_a = [&](const ushort8 (&gv)[NIT], int buf) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * 256;
-      *reinterpret_cast<ushort8*>(&lds.a_buf[buf][i / 16][(i % 16) * 8]) =
-          gv[it];
-    }
-  };
-
-  // W ring of PF+1 chunks with COMPILE-TIME slots (the loop below is
-  // unrolled over them). Branchless: past the end of the split the address
-  // clamps to its last chunk (a re-read that nothing consumes); under a
-  // branch the compiler cannot count the loads in flight and drains the
-  // prefetch in front of the A ds_writes.
-  W8Chunk<NW> wreg[PF + 1];
-  auto load_w = [&](int kc, W8Chunk<NW>& dst) {
-    kc = min(kc, ke - KC);
-    const int64_t g = (int64_t)(kc / KC) * n_total;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-      const uint8_t* p = wrow + (int64_t)j * 64 * k_total + kc;
-      dst.q[j][0] = *reinterpret_cast<const u32x4*>(p);
-      dst.q[j][1] = *reinterpret_cast<const u32x4*>(p + 16);
-      dst.sc[j] = *reinterpret_cast<const f32x4*>(scales + g + nc + j * 64);
-    }
-  };
-
-  // A loads issue BEFORE the W prefetch (issue-ordered vmcnt: the wait in
-  // front of the A ds_writes then leaves the younger W loads in flight).
-  if (kb >= ke) return;  // uniform; the host never launches an empty split
-  {
-    ushort8 gv[NIT];
-    load_a(kb, gv);
-#pragma unroll
-    for (int p = 0; p <= PF; ++p) load_w(kb + p * KC, wreg[p]);
-    store_a(gv, 0);
-  }
-  __syncthreads();
-
-  int buf = 0;
-  for (int kc0 = kb; kc0 < ke; kc0 += (PF + 1) * KC) {
-#pragma unroll
-    for (int u = 0; u <= PF; ++u) {
-      const int kc = kc0 + u * KC;
-      if (kc >= ke) break;  // uniform
-      ushort8 gv[NIT];
-      load_a(min(kc + KC, ke - KC), gv);  // last chunk: an unused re-read
-      const W8Chunk<NW> cur = wreg[u];
-      load_w(kc + (PF + 1) * KC, wreg[u]);  // refill the slot just read
-
-      f32x4 cacc[NW][MT];
-#pragma unroll
-      for (int j = 0; j < NW; ++j)
-#pragma unroll
-        for (int t = 0; t < MT; ++t) cacc[j][t] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        bf16x8 wf[NW];
-#pragma unroll
-        for (int j = 0; j < NW; ++j)
-          wf[j] = w8_frag(cur.q[j][s / 2][2 * (s % 2)],
-                          cur.q[j][s / 2][2 * (s % 2) + 1]);
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-          ushort8 af = *reinterpret_cast<const ushort8*>(
-              &lds.a_buf[buf][t * 16 + lq][32 * la + 8 * s]);
-#pragma unroll
-          for (int j = 0; j < NW; ++j)
-            cacc[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                wf[j], *reinterpret_cast<bf16x8*>(&af), cacc[j][t], 0, 0, 0);
-        }
-      }
-      // acc += s * cacc
-#pragma unroll
-      for (int j = 0; j < NW; ++j)
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            acc[j][t][r] =
-                __builtin_fmaf(cur.sc[j][r], cacc[j][t][r], acc[j][t][r]);
-      store_a(gv, buf ^ 1);
-      __syncthreads();  // next chunk's A is staged; this slot may be reused
-      buf ^= 1;
-    }
-  }
-
-  if (nsplits > 1) {
-    // [split][m][n] f32 partials, one 16 B store per lane per tile (the
-    // layout of skinny_gemm.hip's store_partials). Rows >= m_rows hold
-    // garbage and are never read.
-    float* p = part + (int64_t)blockIdx.y * MROWS * n_total + nc;
-#pragma unroll
-    for (int j = 0; j < NW; ++j)
-#pragma unroll
-      for (int t = 0; t < MT; ++t)
-        *reinterpret_cast<f32x4*>(p + (int64_t)(t * 16 + lq) * n_total +
-                                  j * 64) = acc[j][t];
-    return;
-  }
-
-  // Direct epilogue: transpose C^T through LDS, add bias, round to bf16.
-  __syncthreads();  // all a_buf reads done before the union flips to c_buf
-#pragma unroll
-  for (int j = 0; j < NW; ++j)
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        lds.c_buf[j * 64 + wave * 16 + 4 * la + r][t * 16 + lq] = acc[j][t][r];
-  __syncthreads();
-  for (int i = tid; i < m_rows * NT; i += 256) {
-    const int m = i / NT;
-    const int n = i % NT;
-    float v = lds.c_buf[n][m];
-    if (bias != nullptr) v += bf16_bits_to_float(bias[n0 + n]);
-    out[(int64_t)m * n_total + n0 + n] = float_to_bf16_bits(v);
-  }
+  const WqLane ln(64 * NW);
+  wq_dense_gemm<MT, PF>(
+      ln, W8Weights<NW>(ln, w8, scales, n_total, k_total),
+      WqDenseRows<MT>{part, out, a, bias, m_rows, nsplits, a_stride}, n_total,
+      k_total, k_per_split);
 }
 
 // out[n][16c..16c+15] = bf16(float(w8) * s): 16 weights per thread, two 16 B
@@ -297,51 +175,21 @@ __global__ __launch_bounds__(256) void w8_dequant_kernel(
 
 using namespace arks;
 
-extern "C" void arks_skinny_combine(void* out, const void* part,
-                                    const void* bias, int m_rows, int n_total,
-                                    int nsplits, int mrows_pad,
-                                    hipStream_t stream);
-
-static int w8_mt(int m_rows) { return std::min((m_rows + 15) / 16, 4); }
-
-// Rows per split slab of the partials that arks_w8_skinny_gemm writes.
-extern "C" int arks_w8_slab_rows(int m_rows) { return 16 * w8_mt(m_rows); }
-
-// nw = 64-row N sub-tiles per workgroup (1 or 2). combine = false (nsplits > 1
-// only) leaves the f32 partials in `part` for a consumer that reduces them.
 extern "C" void arks_w8_skinny_gemm(void* part, void* out, const void* a,
                                     const void* w8, const void* scales,
                                     const void* bias, int m_rows, int n_total,
                                     int k_total, int k_per_split, int nsplits,
                                     int64_t a_stride, int nw, bool combine,
                                     hipStream_t stream) {
-  dim3 grid(n_total / (64 * nw), nsplits), block(256);
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, stream, (float*)part,
-                       (bf16*)out, (const bf16*)a, (const uint8_t*)w8,
-                       (const float*)scales, (const bf16*)bias, m_rows,
-                       n_total, k_total, k_per_split, nsplits, a_stride);
-  };
-  constexpr int PF = 1;
-  const int mt = w8_mt(m_rows);
-  if (nw == 2) {
-    switch (mt) {
-      case 1: launch(w8_skinny_gemm_kernel<1, 2, PF>); break;
-      case 2: launch(w8_skinny_gemm_kernel<2, 2, PF>); break;
-      case 3: launch(w8_skinny_gemm_kernel<3, 2, PF>); break;
-      default: launch(w8_skinny_gemm_kernel<4, 2, PF>); break;
-    }
-  } else {
-    switch (mt) {
-      case 1: launch(w8_skinny_gemm_kernel<1, 1, PF>); break;
-      case 2: launch(w8_skinny_gemm_kernel<2, 1, PF>); break;
-      case 3: launch(w8_skinny_gemm_kernel<3, 1, PF>); break;
-      default: launch(w8_skinny_gemm_kernel<4, 1, PF>); break;
-    }
-  }
-  if (nsplits > 1 && combine)
-    arks_skinny_combine(out, part, bias, m_rows, n_total, nsplits,
-                        arks_w8_slab_rows(m_rows), stream);
+  wq_launch_dense(
+      out, part, bias, m_rows, n_total, nsplits, nw, combine, stream,
+      [&](auto MT, auto NW, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((w8_skinny_gemm_kernel<MT(), NW(), 1>), grid,
+                           block, 0, stream, (float*)part, (bf16*)out,
+                           (const bf16*)a, (const uint8_t*)w8,
+                           (const float*)scales, (const bf16*)bias, m_rows,
+                           n_total, k_total, k_per_split, nsplits, a_stride);
+      });
 }
 
 extern "C" void arks_w8_dequant(void* out, const void* w8, const void* scales,

@@ -105,7 +105,7 @@ def _w4_set_storage(mod: nn.Module, name: str) -> tuple[int, int]:
         persistent=False)
     mod.w4 = True
     mod.w4_shape = (N, K)
-    ops.w4_reserve_workspace(N * K, dev)
+    ops.reserve_dequant_workspace(N * K, dev)
     return N, K
 
 
@@ -124,7 +124,7 @@ def finalize_module_w4(mod: nn.Module) -> None:
 
     dev = mod.w4_qweight.device
     if dev.type == "cuda":
-        ops.w4_reserve_workspace(mod.w4_shape[0] * mod.w4_shape[1], dev)
+        ops.reserve_dequant_workspace(mod.w4_shape[0] * mod.w4_shape[1], dev)
         return
     packed = (mod.w4_qweight, mod.w4_scales, mod.w4_zeros)
     mod.register_buffer(
@@ -200,7 +200,7 @@ def init_module_w8(mod: nn.Module, name: str = "linear") -> None:
         persistent=False)
     mod.w8 = True
     mod.w8_shape = (N, K)
-    ops.w4_reserve_workspace(N * K, dev)
+    ops.reserve_dequant_workspace(N * K, dev)
 
 
 def finalize_module_w8(mod: nn.Module) -> None:
@@ -213,7 +213,7 @@ def finalize_module_w8(mod: nn.Module) -> None:
 
     dev = mod.w8_weight.device
     if dev.type == "cuda":
-        ops.w4_reserve_workspace(mod.w8_shape[0] * mod.w8_shape[1], dev)
+        ops.reserve_dequant_workspace(mod.w8_shape[0] * mod.w8_shape[1], dev)
         return
     mod.register_buffer(
         "weight_qdq",

@@ -114,7 +114,7 @@ def main():
         w16 = [torch.randn(n, k, dtype=torch.bfloat16, device="cuda",
                            generator=gen) * 0.05 for _ in range(ncopy16)]
         w4 = [make_w4(n, k, gen) for _ in range(ncopy4)]
-        ops.w4_reserve_workspace(n * k, "cuda")
+        ops.reserve_dequant_workspace(n * k, "cuda")
         for m in map(int, args.ms.split(",")):
             x = torch.randn(m, k, dtype=torch.bfloat16, device="cuda",
                             generator=gen) * 0.5
@@ -123,10 +123,11 @@ def main():
                 "w4": (lambda w: ops.w4_linear(x, w), w4, w4_bytes(n, k)),
             }
             if m > 64:  # both routes, whichever w4_linear ships for this M
-                paths["w4_slab"] = (lambda w: ops._w4_slabs(x, w, None), w4,
+                paths["w4_slab"] = (
+                    lambda w: ops._wq_slabs(ops._W4, x, w, None), w4,
                                     w4_bytes(n, k))
                 paths["w4_deq"] = (
-                    lambda w: ops._w4_dequant_linear(x, w, None), w4,
+                    lambda w: ops._wq_dequant_linear(ops._W4, x, w, None), w4,
                     w4_bytes(n, k))
             graphs = {p: capture(fn, ws) for p, (fn, ws, _) in paths.items()}
             res = {(mode, p): [] for mode in ("eager", "graph")

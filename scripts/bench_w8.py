@@ -117,7 +117,7 @@ def main():
         w16 = [torch.randn(n, k, dtype=torch.bfloat16, device="cuda",
                            generator=gen) * 0.05 for _ in range(ncopy16)]
         w8 = [make_w8(n, k, gen) for _ in range(ncopy8)]
-        ops.w4_reserve_workspace(n * k, "cuda")
+        ops.reserve_dequant_workspace(n * k, "cuda")
         for m in map(int, args.ms.split(",")):
             x = torch.randn(m, k, dtype=torch.bfloat16, device="cuda",
                             generator=gen) * 0.5
@@ -126,10 +126,11 @@ def main():
                 "w8": (lambda w: ops.w8_linear(x, w), w8, w8_bytes(n, k)),
             }
             if m > 64:  # both routes, whichever w8_linear ships for this M
-                paths["w8_slab"] = (lambda w: ops._w8_slabs(x, w, None), w8,
+                paths["w8_slab"] = (
+                    lambda w: ops._wq_slabs(ops._W8, x, w, None), w8,
                                     w8_bytes(n, k))
                 paths["w8_deq"] = (
-                    lambda w: ops._w8_dequant_linear(x, w, None), w8,
+                    lambda w: ops._wq_dequant_linear(ops._W8, x, w, None), w8,
                     w8_bytes(n, k))
             graphs = {p: capture(fn, ws) for p, (fn, ws, _) in paths.items()}
             res = {(mode, p): [] for mode in ("eager", "graph")

@@ -114,7 +114,7 @@ def test_numerics_large_m(m):
     q, z, s = _random_w4(n, k, 11)
     wd = ref.w4_dequant(q, z, s).to(DEV)
     packed = _to_dev(ref.w4_pack(q, z, s))
-    ops.w4_reserve_workspace(n * k, DEV)
+    ops.reserve_dequant_workspace(n * k, DEV)
     torch.manual_seed(13)
     x = torch.randn(m, k, dtype=torch.bfloat16, device=DEV) * 0.5
     bias = torch.randn(n, dtype=torch.bfloat16, device=DEV)

@@ -118,7 +118,7 @@ def test_numerics_large_m(m):
     w8, scales = _random_w8(n, k, 11)
     wd = ref.w8_dequant(w8, scales).to(DEV)
     weight = _to_dev((w8, scales))
-    ops.w4_reserve_workspace(n * k, DEV)
+    ops.reserve_dequant_workspace(n * k, DEV)
     torch.manual_seed(13)
     x = torch.randn(m, k, dtype=torch.bfloat16, device=DEV) * 0.5
     bias = torch.randn(n, dtype=torch.bfloat16, device=DEV)
