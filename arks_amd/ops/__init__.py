@@ -430,6 +430,7 @@ def skinny_gemm(x, weight, bias=None, defer: bool = False):
     M, K = x.shape
     N = weight.shape[0]
     config, nsplits, k_per_split, mrows = _skinny_plan(M, N, K)
+    config = _skinny_resident_config(config, M, nsplits, k_per_split)
     part = (_skinny_ws(nsplits, N, mrows, x.device) if nsplits > 1
             else x.new_empty(0, dtype=torch.float32))
     if defer and nsplits > 1:
@@ -447,7 +448,9 @@ def _skinny_plan(M: int, N: int, K: int):
     """Routing rule of the skinny GEMM: (config, nsplits, k_per_split, mrows).
     config is the kernel the extension launches (0 = default ring with MT
     from M, 1 = tall-K, 2 = tall-K with non-temporal W loads); mrows is the
-    slab height of its split-K partials, 16 * MT."""
+    slab height of its split-K partials, 16 * MT. _skinny_resident_config
+    then moves short-K split plans of config 0 to config 3 without touching
+    the other three values."""
     ntiles = N // 64
     if K > N and ntiles < 128 and M > 48:
         # tall-K (down-proj shape): few N tiles, parallelism comes from
@@ -464,6 +467,29 @@ def _skinny_plan(M: int, N: int, K: int):
     k_per_split = -(-(-(-K // nsplits)) // 32) * 32
     nsplits = -(-K // k_per_split)
     return config, nsplits, k_per_split, 16 * mt
+
+
+# Longest K-range whose A slice the A-resident kernel keeps in LDS.
+_SKINNY_RESIDENT_KMAX = 512
+# ARKS_SKINNY_RESIDENT=0 keeps the short-K split-K GEMMs (qkv, o_proj) on
+# launch config 0 for A/B runs; the partials are bit-identical either way.
+_SKINNY_RESIDENT = os.environ.get("ARKS_SKINNY_RESIDENT", "1") == "1"
+# Smallest M that takes it (see profiles/r07_resident_a.md).
+_SKINNY_RESIDENT_MIN_M = 1
+
+
+def _skinny_resident_config(config: int, M: int, nsplits: int,
+                            k_per_split: int) -> int:
+    """Second routing step, after _skinny_plan: a config-0 plan that splits K
+    into ranges short enough for a workgroup's A slice to stay in LDS runs
+    the A-resident kernel (launch config 3) at the same nsplits, k_per_split
+    and slab height. Everything else, the tall-K plan included, is left as
+    planned."""
+    if (_SKINNY_RESIDENT and config == 0 and nsplits > 1
+            and k_per_split <= _SKINNY_RESIDENT_KMAX
+            and M >= _SKINNY_RESIDENT_MIN_M):
+        return 3
+    return config
 
 
 def _skinny_ws(nsplits: int, N: int, mrows: int, device):

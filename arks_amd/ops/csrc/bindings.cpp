@@ -83,8 +83,10 @@ void arks_silu_mul_fp8(void* out, void* inv_scale, const void* gate_up,
 void arks_skinny_gemm(void* part, void* out, const void* a, const void* w,
                       const void* bias, int m_rows, int n_total, int k_total,
                       int k_per_split, int nsplits, int64_t a_stride,
-                      int config, bool combine, hipStream_t stream);
+                      int config, bool combine, hipStream_t stream,
+                      int groups);
 int arks_skinny_slab_rows(int m_rows, int config);
+int arks_skinny_resident_kmax();
 void arks_skinny_combine(void* out, const void* part, const void* bias,
                          int m_rows, int n_total, int nsplits, int mrows_pad,
                          hipStream_t stream);
@@ -470,16 +472,23 @@ const void* check_skinny_args(const torch::Tensor& out,
 }
 
 // config selects the kernel (skinny_gemm.hip): 0 = default ring with MT from
-// M, 1 = tall-K, 2 = tall-K with non-temporal W loads.
+// M, 1 = tall-K, 2 = tall-K with non-temporal W loads, 3 = A-resident (split-K
+// with a K-range that fits in LDS; groups = workgroups per split, 0 = auto).
 void skinny_gemm_impl(torch::Tensor out, torch::Tensor part, torch::Tensor a,
                       torch::Tensor w, c10::optional<torch::Tensor> bias,
                       int64_t k_per_split, int64_t nsplits, int64_t config,
-                      bool combine) {
+                      int64_t groups, bool combine) {
   const int m = a.size(0), k = a.size(1), n = w.size(0);
   TORCH_CHECK(w.size(1) == k);
-  TORCH_CHECK(0 <= config && config <= 2, "config in 0..2");
+  TORCH_CHECK(0 <= config && config <= 3, "config in 0..3");
   TORCH_CHECK(k_per_split >= 32 && k_per_split % 32 == 0 &&
               nsplits * k_per_split >= k, "splits must cover K");
+  TORCH_CHECK(config != 3 ||
+                  (nsplits > 1 && k_per_split <= arks_skinny_resident_kmax()),
+              "config 3 needs nsplits > 1 and k_per_split <= ",
+              arks_skinny_resident_kmax());
+  TORCH_CHECK(0 <= groups && groups <= 65535, "groups in 0..65535");
+  TORCH_CHECK(nsplits <= 65535, "too many splits");
   const int mrows = arks_skinny_slab_rows(m, (int)config);
   const void* bias_ptr = check_skinny_args(out, part, a, w, bias, k, nsplits,
                                            mrows, !combine, "skinny_gemm");
@@ -487,13 +496,15 @@ void skinny_gemm_impl(torch::Tensor out, torch::Tensor part, torch::Tensor a,
                    combine ? out.data_ptr() : nullptr, a.data_ptr(),
                    w.data_ptr(), bias_ptr, m, n, k, (int)k_per_split,
                    (int)nsplits, a.stride(0), (int)config, combine,
-                   current_stream());
+                   current_stream(), (int)groups);
 }
 
 void skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
                  torch::Tensor w, c10::optional<torch::Tensor> bias,
-                 int64_t k_per_split, int64_t nsplits, int64_t config) {
-  skinny_gemm_impl(out, part, a, w, bias, k_per_split, nsplits, config, true);
+                 int64_t k_per_split, int64_t nsplits, int64_t config,
+                 int64_t groups) {
+  skinny_gemm_impl(out, part, a, w, bias, k_per_split, nsplits, config, groups,
+                   true);
 }
 
 // Partials-only launch (nsplits > 1): leaves the f32 split-K partials
@@ -503,9 +514,9 @@ void skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
 // consumer, not here.
 void skinny_gemm_partials(torch::Tensor part, torch::Tensor a, torch::Tensor w,
                           int64_t k_per_split, int64_t nsplits,
-                          int64_t config) {
+                          int64_t config, int64_t groups) {
   skinny_gemm_impl(torch::Tensor(), part, a, w, c10::nullopt, k_per_split,
-                   nsplits, config, false);
+                   nsplits, config, groups, false);
 }
 
 // Packed W4 weight (w4_gemm.hip): qweight i32 [N, K/8], scales f16 [K/128, N],
@@ -1274,10 +1285,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul_fp8", &silu_mul_fp8);
   m.def("skinny_gemm", &skinny_gemm, py::arg("out"), py::arg("part"),
         py::arg("a"), py::arg("w"), py::arg("bias"), py::arg("k_per_split"),
-        py::arg("nsplits"), py::arg("config") = 0);
+        py::arg("nsplits"), py::arg("config") = 0, py::arg("groups") = 0);
   m.def("skinny_gemm_partials", &skinny_gemm_partials, py::arg("part"),
         py::arg("a"), py::arg("w"), py::arg("k_per_split"),
-        py::arg("nsplits"), py::arg("config") = 0);
+        py::arg("nsplits"), py::arg("config") = 0, py::arg("groups") = 0);
   m.def("skinny_combine", &skinny_combine);
   m.def("w4_skinny_gemm", &w4_skinny_gemm);
   m.def("w4_skinny_gemm_partials", &w4_skinny_gemm_partials);

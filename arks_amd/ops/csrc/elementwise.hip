@@ -133,6 +133,94 @@ __global__ __launch_bounds__(256) void splitk_add_rmsnorm_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// The same op in one round of loads, for rows of at most NORM_WIDE_BLOCK
+// vectors (hidden <= 4096): one thread per 8-column vector, so every load of
+// a row — partials, residual, weight, bias — is issued before the first
+// add, and the rounded sums stay in registers for the normalisation (the
+// kernel above needs two dependent rounds at hidden 3584 and re-reads the
+// row for pass 2).
+// The bits are those of the kernel above because its summation order is
+// rebuilt exactly: there, lane t of 256 chains add_square over vector t and
+// then over vector t + 256; here the upper 256 threads publish their
+// rounded sums to LDS and lane t continues its chain over them, and
+// block_reduce_sum<NORM_BLOCK>'s order (wave shuffle tree, then the four
+// wave sums added 0..3) runs over the lower four waves only.
+// ---------------------------------------------------------------------------
+constexpr int NORM_WIDE_BLOCK = 512;
+
+__global__ __launch_bounds__(NORM_WIDE_BLOCK) void splitk_add_rmsnorm_wide_kernel(
+    bf16* __restrict__ out, const float* __restrict__ part,
+    const bf16* __restrict__ bias,  // [hidden] or null
+    bf16* __restrict__ residual, const bf16* __restrict__ weight,
+    const float eps, const int hidden, const int nsplits,
+    const int64_t split_stride) {
+  // One LDS object: a second one can cost extra waits on the first.
+  __shared__ struct {
+    ushort8 hi[NORM_WIDE_BLOCK - NORM_BLOCK];  // rounded sums of vector t+256
+    float red[NORM_BLOCK / WAVE_SIZE];
+  } lds;
+  const int row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int nvec = hidden / 8;
+  const bool live = tid < nvec;
+  // Idle threads load vector 0 (in bounds) and store nothing.
+  const int col = live ? tid * 8 : 0;
+  const float* part_row = part + (int64_t)row * hidden;
+  bf16* res = residual + (int64_t)row * hidden + col;
+
+  // Every load of the row, up front.
+  const ushort8 r = *reinterpret_cast<const ushort8*>(res);
+  const ushort8 w = *reinterpret_cast<const ushort8*>(weight + col);
+  ushort8 b = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (bias != nullptr) b = *reinterpret_cast<const ushort8*>(bias + col);
+  const float* const p[2] = {part_row + col, part_row + col + 4};
+  float4v acc[2];
+  splitk_reduce<2, 2>(p, split_stride, nsplits, acc);
+
+  ushort8 s;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float xf = acc[j / 4][j % 4];
+    if (bias != nullptr) xf += bf16_bits_to_float(b[j]);
+    const uint16_t x = float_to_bf16_bits(xf);  // the combine's rounding
+    // add_residual8's arithmetic
+    s[j] = float_to_bf16_bits(bf16_bits_to_float(x) +
+                              bf16_bits_to_float(r[j]));
+  }
+  if (live) *reinterpret_cast<ushort8*>(res) = s;
+  if (tid >= NORM_BLOCK) lds.hi[tid - NORM_BLOCK] = s;
+  __syncthreads();
+
+  if (tid < NORM_BLOCK) {  // whole waves 0..3
+    float ss = 0.f;
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss = add_square(ss, bf16_bits_to_float(s[j]));
+    }
+    if (tid + NORM_BLOCK < nvec) {
+      const ushort8 h = lds.hi[tid];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss = add_square(ss, bf16_bits_to_float(h[j]));
+    }
+    ss = wave_reduce_sum(ss);
+    if (tid % WAVE_SIZE == 0) lds.red[tid / WAVE_SIZE] = ss;
+  }
+  __syncthreads();
+  float total = 0.f;
+#pragma unroll
+  for (int wv = 0; wv < NORM_BLOCK / WAVE_SIZE; ++wv) total += lds.red[wv];
+  const float rrms = rsqrtf(total / (float)hidden + eps);
+  if (!live) return;
+  ushort8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float v = bf16_bits_to_float(s[j]) * rrms * bf16_bits_to_float(w[j]);
+    o[j] = float_to_bf16_bits(v);
+  }
+  *reinterpret_cast<ushort8*>(out + (int64_t)row * hidden + col) = o;
+}
+
+// ---------------------------------------------------------------------------
 // SiLU-mul: input [rows, 2*d] = [gate | up], output [rows, d].
 // ---------------------------------------------------------------------------
 __global__ void silu_mul_kernel(bf16* __restrict__ out,
@@ -228,11 +316,14 @@ void arks_splitk_add_rmsnorm(void* out, const void* part, const void* bias,
                              void* residual, const void* weight, float eps,
                              int rows, int hidden, int nsplits, int mrows_pad,
                              hipStream_t stream) {
-  dim3 grid(rows), block(256);
-  hipLaunchKernelGGL(splitk_add_rmsnorm_kernel, grid, block, 0, stream,
-                     (bf16*)out, (const float*)part, (const bf16*)bias,
-                     (bf16*)residual, (const bf16*)weight, eps, hidden,
-                     nsplits, (int64_t)mrows_pad * hidden);
+  // One vector per thread where the row fits; wider rows loop.
+  const bool wide = hidden <= 8 * NORM_WIDE_BLOCK;
+  dim3 grid(rows), block(wide ? NORM_WIDE_BLOCK : NORM_BLOCK);
+  hipLaunchKernelGGL(
+      wide ? splitk_add_rmsnorm_wide_kernel : splitk_add_rmsnorm_kernel, grid,
+      block, 0, stream, (bf16*)out, (const float*)part, (const bf16*)bias,
+      (bf16*)residual, (const bf16*)weight, eps, hidden, nsplits,
+      (int64_t)mrows_pad * hidden);
 }
 
 void arks_silu_mul(void* out, const void* gate_up, int64_t rows, int d,

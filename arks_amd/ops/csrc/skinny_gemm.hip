@@ -16,8 +16,13 @@
 //   against (16 x waves) x 128 of W, through the same load path, so with
 //   four waves at M = 64 half of a CU's fetches are A re-read from L2; a
 //   probe build without the A loads ran the down-proj 9 us (23 %) faster.
-//   The tall-K configs therefore run eight waves per workgroup: the same W
-//   per CU against half the A.
+//   Two answers, by K-range. The tall-K configs run eight waves per
+//   workgroup: the same W per CU against half the A. Split-K plans whose
+//   K-range is at most 512 (qkv, o_proj) run skinny_resident_kernel
+//   (config 3, below): one workgroup per CU fetches its A slice once, keeps
+//   it in LDS and streams all of the CU's slabs of W past it, 0.44 bytes of
+//   A per byte of W at the qkv shape instead of 1 (cold, per call: qkv
+//   14.9 -> 12.5 us, o_proj 11.5 -> 10.2; profiles/r07_resident_a.md).
 //   (2) The s_waitcnt pattern of the compiled loop, because vmcnt retires
 //   in issue order (ISA audits: profiles/r02_final.md and r05). On its own
 //   the pattern below did not move the measured time (the loop was fetch-
@@ -52,20 +57,24 @@
 //   splitk_reduce (common.h); skinny_combine_kernel is the fallback that
 //   materialises a bf16 [M, N].
 //
-// The file builds seven kernels: skinny_gemm_kernel<MT> for MT 1..4 (launch
+// The file builds eleven kernels: skinny_gemm_kernel<MT> for MT 1..4 (launch
 // config 0, MT from M, four waves), <4, false, 8> for the tall-K plan of
 // the down-proj shape (config 1, eight waves), <4, true, 8> with
-// non-temporal W loads (config 2), and skinny_combine_kernel. The
-// experiments that lost — global-direct A reads, wave-private barrier-free
-// staging, silu_mul fused into the A staging, shifted rings of other
-// (KC, PF) — are recorded with their numbers in profiles/r02_final.md; the
-// MLP runs silu_mul_kernel (elementwise.hip) ahead of the down-proj.
+// non-temporal W loads (config 2), skinny_resident_kernel<MT> for MT 1..4
+// (config 3: split-K with K-ranges of at most 512, A resident in LDS), and
+// skinny_combine_kernel. The experiments that lost — global-direct A reads,
+// wave-private barrier-free staging, silu_mul fused into the A staging,
+// shifted rings of other (KC, PF) — are recorded with their numbers in
+// profiles/r02_final.md, eight-wave and two-per-CU decompositions of the
+// resident kernel in profiles/r07_resident_a.md; the MLP runs
+// silu_mul_kernel (elementwise.hip) ahead of the down-proj.
 //
 // N must be a multiple of 64 and K of 32 (true for every Qwen/Llama shape;
 // the Python wrapper falls back to hipBLASLt otherwise).
 #include "common.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 #include <type_traits>
 
@@ -325,6 +334,206 @@ __global__ __launch_bounds__(64 * WAVES, 2) void skinny_gemm_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// A-resident kernel for short K-ranges (launch config 3, split-K only).
+//
+// grid = (groups, nsplits). A workgroup belongs to one split and owns a run
+// of 16-row slabs of W (wave v takes every SKR_WAVES-th of them). Its whole
+// A slice, 16*MT x K-range, is staged into LDS once (row stride
+// k_per_split + SK_AP, dynamic LDS); after that one barrier the waves run
+// on their own: no A load, no ds_write and no barrier per chunk.
+//
+// Per wave:
+//   prologue  issue the A piece (one row of the slice per wave per pass, all
+//             passes at once), then the W of the first R slabs, whole;
+//             wait for A only (a counted vmcnt: the W stays out while A
+//             is written to LDS), ds_write it, barrier. A goes first
+//             because vmcnt retires in issue order: behind the W loads,
+//             the wait for A would be a wait for all of them.
+//   slab i    MFMAs over the K-range, ascending k (W from ring slot i % R,
+//             A from LDS); store_partials; refill the slot with slab i + R
+// The ring is indexed statically and holds whole slabs: R = 2 slabs of 3-4
+// chunks or 3 of 1-2 (at most 128 VGPRs of W). The chunk count of the
+// K-range (1..4, uniform per workgroup) selects one straight-line
+// instantiation of the whole stream, and within it every possible number
+// of slabs left after the last full turn has its own path, as in the
+// kernel above, so every wait is an exact count (ISA table in
+// profiles/r07_resident_a.md; vmcnt(0) only where a wave's last slab is
+// consumed). Slots that no slab is left for are still loaded in the
+// prologue, one line, as in `issue` of the kernel above.
+// Four waves, one workgroup per CU measured fastest (eight waves, or more
+// workgroups than CUs, lost 1-4 us per call at the decode shapes).
+// An accumulator sees the MFMA sequence of skinny_gemm_kernel<MT> for the
+// same split boundaries, so the partials are bit-equal to config 0's.
+// ---------------------------------------------------------------------------
+constexpr int SKR_WAVES = 4;
+constexpr int SKR_KMAX = 512;  // longest K-range (four chunks)
+
+template <int MT>
+__global__ __launch_bounds__(64 * SKR_WAVES, 2) void skinny_resident_kernel(
+    float* __restrict__ part,   // [nsplits, 16*MT, N]
+    const bf16* __restrict__ a, // [M, K] (row stride a_stride)
+    const bf16* __restrict__ w, // [N, K] row-major
+    const int m_rows, const int n_total, const int k_total,
+    const int k_per_split, const int64_t a_stride, const int slabs_per_group) {
+  constexpr int KC = SK_KC;
+  constexpr int WAVES = SKR_WAVES;
+  constexpr int NA = 16 * MT / WAVES;  // A rows (loads) per thread
+  static_assert(NA * WAVES == 16 * MT, "A rows must divide over the waves");
+  extern __shared__ __attribute__((aligned(16))) bf16 a_lds[];
+  const int lstride = k_per_split + SK_AP;  // a_lds row stride (bf16)
+
+  const int kb = blockIdx.y * k_per_split;
+  const int ke = min(k_total, kb + k_per_split);
+  const int klen = max(ke - kb, 0);        // multiple of 32, <= SKR_KMAX
+  const int nch = (klen + KC - 1) / KC;
+
+  const int tid = threadIdx.x;
+  const int wave = tid / WAVE_SIZE;
+  const int lane = tid % WAVE_SIZE;
+  const int lq = lane % 16;
+  const int la = lane / 16;
+
+  // This workgroup's slabs [slab0, slab0 + nwg); wave v takes slab0 + v,
+  // slab0 + v + WAVES, ...: nsl of them (0 where the groups outnumber N).
+  const int slab0 = blockIdx.x * slabs_per_group;
+  const int nwg = max(min(slabs_per_group, n_total / 16 - slab0), 0);
+  const int nsl = (nwg - wave + WAVES - 1) / WAVES;
+
+  // A piece of this thread: row it * WAVES + wave, 16 B at column lcol of
+  // the K-range. Branchless: rows past m_rows are clamped to the last row,
+  // and lanes past the K-range to its last vector, which they load and
+  // write again (the same bytes to the same place). With a guard around the
+  // ds_writes the compiler sinks the loads into it, behind the W loads,
+  // and the wait for A becomes a vmcnt(0).
+  ushort8 areg[NA];
+  const int lcol = max(min(8 * lane, klen - 8), 0);
+  const int acol = min(kb + lcol, k_total - 8);
+  auto load_a = [&]() {
+#pragma unroll
+    for (int it = 0; it < NA; ++it)
+      areg[it] = *reinterpret_cast<const ushort8*>(
+          a + (int64_t)min(it * WAVES + wave, m_rows - 1) * a_stride + acol);
+    __builtin_amdgcn_sched_barrier(0);  // A enters the queue ahead of W
+  };
+  auto stage_a = [&]() {
+#pragma unroll
+    for (int it = 0; it < NA; ++it)
+      *reinterpret_cast<ushort8*>(
+          &a_lds[(it * WAVES + wave) * lstride + lcol]) = areg[it];
+    __syncthreads();
+  };
+
+  const bf16* wlane = w + 8 * la;
+  const bf16* afrag = a_lds + lq * lstride + 8 * la;
+  using std::integral_constant;
+
+  auto stream = [&](auto nch_c) {
+    constexpr int NCH = decltype(nch_c)::value;
+    constexpr int KS = NCH * (KC / 32);   // k-steps (loads) per slab
+    constexpr int R = NCH >= 3 ? 2 : 3;   // slabs in flight
+    ushort8 wreg[R][KS];
+
+    // Issue the W of the wave's slab i, whole; nothing waited for. k-steps
+    // past the K-range are clamped into the row and never consumed.
+    auto issue = [&](int i, ushort8 (&wd)[KS], bool live) {
+      const bf16* wrow =
+          wlane +
+          (int64_t)((slab0 + wave + i * WAVES) * 16 + lq) * k_total;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const bf16* src = wrow + min(kb + s * 32, k_total - 32);
+        wd[s] = *reinterpret_cast<const ushort8*>(live ? src : w);
+      }
+    };
+    // MFMAs of slab i from its ring slot, ascending k, then its partials.
+    auto consume = [&](int i, const ushort8 (&wd)[KS]) {
+      f32x4 acc[MT];
+#pragma unroll
+      for (int t = 0; t < MT; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        // only the last chunk may be short
+        if (s >= KS - KC / 32 && s * 32 >= klen) break;
+        ushort8 wv = wd[s];
+        bf16x8 wfrag = *reinterpret_cast<bf16x8*>(&wv);
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+          ushort8 af = *reinterpret_cast<const ushort8*>(
+              afrag + t * 16 * lstride + s * 32);
+          acc[t] = sk_mfma(wfrag, *reinterpret_cast<bf16x8*>(&af), acc[t]);
+        }
+      }
+      store_partials<MT>(part, acc, n_total,
+                         (slab0 + wave + i * WAVES) * 16 + 4 * la, lq);
+    };
+
+    // Every load of a path is issued inside it. The marker differs per
+    // path, which keeps the compiler from hoisting the common loads above
+    // the switch: with loads out across it, the paths after the first
+    // opened with a vmcnt(0) ahead of their W loads.
+    asm volatile("; resident path, %0 chunks" ::"n"(NCH));
+    load_a();
+#pragma unroll
+    for (int p = 0; p < R; ++p) {
+      issue(p, wreg[p], p < nsl);
+      __builtin_amdgcn_sched_barrier(0);  // slabs enter the queue in order
+    }
+    stage_a();
+    __builtin_amdgcn_sched_barrier(0);
+
+    int c = 0;  // next slab to consume; a multiple of R, so it is in slot 0
+    // One turn of the ring: R slabs from slots 0..R-1, the first `nrefill`
+    // slots refilled with slab c + R + s (which must exist).
+    auto ring_turn = [&](auto nrefill) {
+      constexpr int NR = decltype(nrefill)::value;
+#pragma unroll
+      for (int s = 0; s < R; ++s) {
+        consume(c + s, wreg[s]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s < NR) issue(c + R + s, wreg[s], true);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      c += R;
+    };
+    auto drain = [&](auto nleft) {
+      constexpr int NL = decltype(nleft)::value;
+#pragma unroll
+      for (int s = 0; s < NL; ++s) consume(c + s, wreg[s]);
+    };
+    // REM slabs left, 0 < REM < 2R: a partly refilled turn, then the rest.
+    auto tail = [&](auto rem) {
+      constexpr int REM = decltype(rem)::value;
+      if constexpr (REM >= 2 * R) {
+        // not reachable for this R
+      } else if constexpr (REM >= R) {
+        ring_turn(integral_constant<int, REM - R>{});
+        drain(integral_constant<int, REM - R>{});
+      } else {
+        drain(integral_constant<int, REM>{});
+      }
+    };
+    // Steady state: every slot refilled, no branch around a load.
+    while (c + 2 * R <= nsl) ring_turn(integral_constant<int, R>{});
+    switch (nsl - c) {
+      case 5: tail(integral_constant<int, 5>{}); break;
+      case 4: tail(integral_constant<int, 4>{}); break;
+      case 3: tail(integral_constant<int, 3>{}); break;
+      case 2: tail(integral_constant<int, 2>{}); break;
+      case 1: tail(integral_constant<int, 1>{}); break;
+      default: break;
+    }
+    static_assert(R <= 3, "the tail switch is written out for R <= 3");
+  };
+
+  switch (nch) {
+    case 4: stream(integral_constant<int, 4>{}); break;
+    case 3: stream(integral_constant<int, 3>{}); break;
+    case 2: stream(integral_constant<int, 2>{}); break;
+    default: stream(integral_constant<int, 1>{}); break;  // or empty: zeros
+  }
+}
+
 // Reduce the split partials: out[m][n] = bf16(sum_s part[s][m][n] + bias[n]).
 // Partials and output share the [m][n] orientation, so this is elementwise:
 // each thread owns four consecutive n of one row (16 B loads per split, all
@@ -369,11 +578,11 @@ extern "C" void arks_skinny_combine(void* out, const void* part,
                      n_total, nsplits, (int64_t)mrows_pad * n_total);
 }
 
-// M tiles of the kernel that `config` launches for m_rows rows: config 0
-// takes MT from M, the tall-K configs (1, 2) always run MT = 4 (64-row
+// M tiles of the kernel that `config` launches for m_rows rows: configs 0
+// and 3 take MT from M, the tall-K configs (1, 2) always run MT = 4 (64-row
 // slabs, which the tall-K plan's consumers expect).
 static int skinny_mt(int m_rows, int config) {
-  return config == 0 ? std::min((m_rows + 15) / 16, 4) : 4;
+  return config == 0 || config == 3 ? std::min((m_rows + 15) / 16, 4) : 4;
 }
 
 // Rows per split slab of the partials that arks_skinny_gemm writes.
@@ -381,15 +590,81 @@ extern "C" int arks_skinny_slab_rows(int m_rows, int config) {
   return 16 * skinny_mt(m_rows, config);
 }
 
+// Longest k_per_split config 3 takes (its A slice must fit in LDS).
+extern "C" int arks_skinny_resident_kmax() { return SKR_KMAX; }
+
+// Compute units of the current device, queried once per device.
+static int device_cu_count() {
+  constexpr int MAX_DEV = 64;
+  static std::atomic<int> cus[MAX_DEV];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) dev = 0;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess || n <= 0)
+      n = 1;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+// Config 3. groups = workgroups per split; 0 = one workgroup per compute
+// unit over all splits, so that every A slice is fetched once per CU and
+// the (slab, split) units come out even (qkv at 7B: 32 x 8 workgroups of 9
+// slabs on 256 CUs).
+template <int MT>
+static void launch_resident(float* part, const bf16* a, const bf16* w,
+                            int m_rows, int n_total, int k_total,
+                            int k_per_split, int nsplits, int64_t a_stride,
+                            int groups, hipStream_t stream) {
+  const int slabs = n_total / 16;
+  // An explicit count is taken as given: groups past the last slab exit
+  // after the barrier.
+  if (groups <= 0)
+    groups = std::min(std::max(device_cu_count() / nsplits, 1), slabs);
+  const int per_group = (slabs + groups - 1) / groups;
+  const size_t lds = (size_t)16 * MT * (k_per_split + SK_AP) * sizeof(bf16);
+  // Above 64 KB (K-range 512 at MT = 4) the size has to be opted into.
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&skinny_resident_kernel<MT>),
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        16 * MT * (SKR_KMAX + SK_AP) * (int)sizeof(bf16));
+  hipLaunchKernelGGL(skinny_resident_kernel<MT>, dim3(groups, nsplits),
+                     dim3(64 * SKR_WAVES), lds, stream, part, a, w, m_rows,
+                     n_total, k_total, k_per_split, a_stride, per_group);
+}
+
 // config 0: MT from M, four waves; 1: tall-K plan (MT=4, eight waves);
-// 2: tall-K with non-temporal W loads.
+// 2: tall-K with non-temporal W loads; 3: A-resident, split-K only
+// (nsplits > 1, k_per_split <= SKR_KMAX), `groups` workgroups per split
+// (0 = auto; the other configs ignore it).
 // combine = false (nsplits > 1 only) stops after the GEMM: the f32 partials
 // stay in `part` for a consumer kernel that reduces them itself.
 extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
                                  const void* w, const void* bias, int m_rows,
                                  int n_total, int k_total, int k_per_split,
                                  int nsplits, int64_t a_stride, int config,
-                                 bool combine, hipStream_t stream) {
+                                 bool combine, hipStream_t stream,
+                                 int groups = 0) {
+  if (config == 3) {
+    auto launch = [&](auto mt) {
+      launch_resident<decltype(mt)::value>(
+          (float*)part, (const bf16*)a, (const bf16*)w, m_rows, n_total,
+          k_total, k_per_split, nsplits, a_stride, groups, stream);
+    };
+    switch (skinny_mt(m_rows, config)) {
+      case 1: launch(std::integral_constant<int, 1>{}); break;
+      case 2: launch(std::integral_constant<int, 2>{}); break;
+      case 3: launch(std::integral_constant<int, 3>{}); break;
+      default: launch(std::integral_constant<int, 4>{}); break;
+    }
+    if (combine)
+      arks_skinny_combine(out, part, bias, m_rows, n_total, nsplits,
+                          arks_skinny_slab_rows(m_rows, config), stream);
+    return;
+  }
   // The tall-K configs run 8 waves (128 rows of W) per workgroup.
   const int waves = config == 0 ? 4 : 8;
   dim3 grid((n_total + 16 * waves - 1) / (16 * waves), nsplits);

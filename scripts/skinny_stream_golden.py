@@ -95,13 +95,15 @@ def make_inputs(case, device, unit=False):
     return a, w.to(device), bv.to(torch.bfloat16).to(device)
 
 
-def run_case(native, case, device, config=None, unit=False):
+def run_case(native, case, device, config=None, unit=False, groups=0):
     """Launch one case. Returns (out bf16 [M, N], partial rows f32
-    [nsplits, M, N] or None when the case does not split)."""
+    [nsplits, M, N] or None when the case does not split). groups is the
+    workgroups-per-split argument of config 3 (0 = auto)."""
     M, N, K, cfg, nsplits, kps, _ = case
     cfg = cfg if config is None else config
     a, w, bias = make_inputs(case, device, unit)
-    mrows = 16 * (min(-(-M // 16), 4) if cfg == 0 else 4)
+    # configs 0 and 3 (A-resident) take the slab height from M
+    mrows = 16 * (min(-(-M // 16), 4) if cfg in (0, 3) else 4)
     out = torch.empty((M, N), dtype=torch.bfloat16, device=device)
     if nsplits == 1:
         part = torch.empty(0, dtype=torch.float32, device=device)
@@ -109,9 +111,9 @@ def run_case(native, case, device, config=None, unit=False):
         return out, None
     part = torch.full((nsplits * mrows * N,), float("nan"),
                       dtype=torch.float32, device=device)
-    native.skinny_gemm_partials(part, a, w, kps, nsplits, cfg)
+    native.skinny_gemm_partials(part, a, w, kps, nsplits, cfg, groups)
     rows = part.view(nsplits, mrows, N)[:, :M, :].clone()
-    native.skinny_gemm(out, part, a, w, bias, kps, nsplits, cfg)
+    native.skinny_gemm(out, part, a, w, bias, kps, nsplits, cfg, groups)
     return out, rows
 
 
