@@ -113,20 +113,40 @@ def rope_and_cache(positions, q, k, v, k_cache, v_cache, slot_mapping,
     return q2, k2
 
 
+# ARKS_ROPE_SPLITK_GROUPS=1 keeps the RoPE + cache consumer of the split-K
+# qkv GEMM at one workgroup per token for A/B runs (0 = spread the tokens
+# over the compute units); the results are bit-identical either way.
+_ROPE_SPLITK_GROUPS = int(os.environ.get("ARKS_ROPE_SPLITK_GROUPS", "0"))
+
+
+def _rope_splitk_groups(tokens: int, cus: int) -> int:
+    """Workgroups per token of the split-K RoPE + cache consumer: enough to
+    put work on every compute unit when the tokens alone do not (decode: 64
+    tokens on 256 CUs run as 4 groups each). The launcher keeps a group at
+    64 items or more."""
+    if _ROPE_SPLITK_GROUPS > 0:
+        return _ROPE_SPLITK_GROUPS
+    return max(1, -(-cus // max(tokens, 1)))
+
+
 def rope_and_cache_splitk(positions, qkv, k_cache, v_cache, slot_mapping,
-                          cos_sin, head_dim: int, num_q_heads: int):
+                          cos_sin, head_dim: int, num_q_heads: int,
+                          groups: int | None = None):
     """rope_and_cache for a qkv projection that is still a SplitKPending
     handle: reduces the split-K partials, rotates, writes rotated k and v
     into the paged cache and returns rotated q [T, Hq*D]. k and v are not
-    materialised (the decode attention kernel reads them from the cache)."""
+    materialised (the decode attention kernel reads them from the cache).
+    groups = workgroups per token (default: _rope_splitk_groups)."""
     qkv.check_live()
     if qkv.shape[1] != (num_q_heads + 2 * k_cache.shape[1]) * head_dim:
         raise ValueError(f"qkv width {qkv.shape[1]} does not match the heads")
     q = torch.empty((qkv.shape[0], num_q_heads * head_dim),
                     dtype=torch.bfloat16, device=qkv.ws.device)
+    if groups is None:
+        groups = _rope_splitk_groups(qkv.shape[0], _cu_count(qkv.ws.device))
     _native().splitk_rope_and_cache(positions, qkv.ws, qkv.bias, q, k_cache,
                                     v_cache, slot_mapping, cos_sin, head_dim,
-                                    qkv.nsplits, qkv.mrows)
+                                    qkv.nsplits, qkv.mrows, groups)
     return q
 
 
@@ -431,6 +451,9 @@ def skinny_gemm(x, weight, bias=None, defer: bool = False):
     N = weight.shape[0]
     config, nsplits, k_per_split, mrows = _skinny_plan(M, N, K)
     config = _skinny_resident_config(config, M, nsplits, k_per_split)
+    if config == 1:  # the only plan the step moves; the rest need no device
+        config = _skinny_tallk7_config(config, N, nsplits,
+                                       _cu_count(x.device))
     part = (_skinny_ws(nsplits, N, mrows, x.device) if nsplits > 1
             else x.new_empty(0, dtype=torch.float32))
     if defer and nsplits > 1:
@@ -449,8 +472,9 @@ def _skinny_plan(M: int, N: int, K: int):
     config is the kernel the extension launches (0 = default ring with MT
     from M, 1 = tall-K, 2 = tall-K with non-temporal W loads); mrows is the
     slab height of its split-K partials, 16 * MT. _skinny_resident_config
-    then moves short-K split plans of config 0 to config 3 without touching
-    the other three values."""
+    then moves short-K split plans of config 0 to config 3, and
+    _skinny_tallk7_config tall-K plans to config 4, without touching the
+    other three values."""
     ntiles = N // 64
     if K > N and ntiles < 128 and M > 48:
         # tall-K (down-proj shape): few N tiles, parallelism comes from
@@ -489,6 +513,32 @@ def _skinny_resident_config(config: int, M: int, nsplits: int,
             and k_per_split <= _SKINNY_RESIDENT_KMAX
             and M >= _SKINNY_RESIDENT_MIN_M):
         return 3
+    return config
+
+
+# ARKS_SKINNY_TALLK_WAVES=8 keeps the tall-K plan on 128-row tiles (launch
+# config 1) for A/B runs; the partials are bit-identical either way.
+_TALLK_WAVES = os.environ.get("ARKS_SKINNY_TALLK_WAVES", "7").strip()
+if _TALLK_WAVES not in ("7", "8"):
+    raise ValueError(
+        f"ARKS_SKINNY_TALLK_WAVES={_TALLK_WAVES!r}: accepted values are 7 "
+        "(112-row tiles where they fill more CUs) and 8 (128-row tiles)"
+    )
+
+
+def _skinny_tallk7_config(config: int, N: int, nsplits: int, cus: int) -> int:
+    """Third routing step: a tall-K plan (config 1) runs on 112-row tiles
+    (launch config 4, seven waves) when those put workgroups on more of the
+    device's `cus` compute units than 128-row tiles do without exceeding one
+    per CU: N a multiple of 112, N/112 * nsplits <= cus, and that more than
+    ceil(N/128) * nsplits. The down-proj of a 7B model (N = 3584, 8 splits)
+    goes from 224 workgroups to 256. nsplits, k_per_split and the slab height
+    are untouched; config 2 (non-temporal) stays as it is."""
+    if _TALLK_WAVES != "7" or config != 1 or N % 112 != 0:
+        return config
+    wgs = N // 112 * nsplits
+    if wgs <= cus and wgs > -(-N // 128) * nsplits:
+        return 4
     return config
 
 
@@ -977,20 +1027,61 @@ def moe_mix_rows(y, weights, rows):
     return ref.moe_mix_rows(y, weights, rows)
 
 
-def sample_tokens(logits, temperatures, uniform):
-    """Gumbel-max categorical sampling; rows with temperature 0 are greedy."""
+_CU_COUNT: dict = {}
+
+
+def _cu_count(device) -> int:
+    """Compute units of a GPU, queried once per device."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    n = _CU_COUNT.get(idx)
+    if n is None:
+        n = _CU_COUNT[idx] = torch.cuda.get_device_properties(idx).multi_processor_count
+    return n
+
+
+# Shortest vocabulary chunk a sampling workgroup is given (one trip of its
+# 256 threads x 8 tokens), and the workgroups per CU the chunking aims for.
+_SAMPLE_MIN_CHUNK = 2048
+_SAMPLE_WGS_PER_CU = 4
+
+
+def _sample_chunks(rows: int, vocab: int, cus: int) -> int:
+    """Workgroups per row of the unmasked samplers. The kernels scan a row
+    with one workgroup; below one row per CU most of the chip would idle
+    (decode: 64 rows of 152k logits on 256 CUs), so a row is cut into chunks,
+    about _SAMPLE_WGS_PER_CU workgroups per CU in all, none shorter than
+    _SAMPLE_MIN_CHUNK. The ids do not depend on the count."""
+    if rows >= cus:
+        return 1
+    want = -(-_SAMPLE_WGS_PER_CU * cus // max(rows, 1))
+    return max(1, min(want, vocab // _SAMPLE_MIN_CHUNK))
+
+
+def _sample_launch(fn, logits, args, chunks):
+    rows, vocab = logits.shape
+    if chunks is None:
+        chunks = _sample_chunks(rows, vocab, _cu_count(logits.device))
+    out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    pairs = (torch.empty((rows, chunks, 2), dtype=torch.int32,
+                         device=logits.device) if chunks > 1 else None)
+    fn(out, logits, *args, pairs, chunks)
+    return out
+
+
+def sample_tokens(logits, temperatures, uniform, chunks=None):
+    """Gumbel-max categorical sampling; rows with temperature 0 are greedy.
+    chunks forces the workgroups per row (default: _sample_chunks)."""
     if logits.is_cuda:
-        out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
-        _native().gumbel_sample(out, logits, temperatures, uniform)
-        return out
+        return _sample_launch(_native().gumbel_sample, logits,
+                              (temperatures, uniform), chunks)
     return ref.gumbel_sample(logits, temperatures, uniform)
 
 
-def greedy_sample(logits):
+def greedy_sample(logits, chunks=None):
+    """Argmax per row, lowest index on ties. chunks forces the workgroups
+    per row (default: _sample_chunks)."""
     if logits.is_cuda:
-        out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
-        _native().greedy_sample(out, logits)
-        return out
+        return _sample_launch(_native().greedy_sample, logits, (), chunks)
     return ref.greedy_sample(logits)
 
 

@@ -100,12 +100,13 @@ void arks_splitk_rope_and_cache(const void* positions, const void* part,
                                 const void* cos_sin, int num_tokens,
                                 int head_dim, int num_q_heads,
                                 int num_kv_heads, int block_size, int nsplits,
-                                int mrows_pad, int kv_fp8, hipStream_t stream);
-void arks_greedy_sample(void* out, const void* logits, int rows, int vocab,
-                        hipStream_t stream);
-void arks_gumbel_sample(void* out, const void* logits, const void* temperatures,
-                        const void* uniform, int rows, int vocab,
-                        hipStream_t stream);
+                                int mrows_pad, int kv_fp8, int groups,
+                                hipStream_t stream);
+void arks_greedy_sample(void* out, void* pairs, const void* logits, int rows,
+                        int vocab, int chunks, hipStream_t stream);
+void arks_gumbel_sample(void* out, void* pairs, const void* logits,
+                        const void* temperatures, const void* uniform,
+                        int rows, int vocab, int chunks, hipStream_t stream);
 void arks_greedy_sample_masked(void* out, const void* logits,
                                const void* masks, const void* mask_row,
                                int rows, int vocab, int slots,
@@ -444,12 +445,14 @@ const void* check_skinny_args(const torch::Tensor& out,
                               const torch::Tensor& a, const torch::Tensor& w,
                               const c10::optional<torch::Tensor>& bias,
                               int64_t k, int64_t nsplits, int64_t mrows,
-                              bool partials_only, const char* what) {
+                              int64_t n_mult, bool partials_only,
+                              const char* what) {
   check_bf16_rowstrided(a, "a");
   check_bf16_contig(w, "w");
   const int64_t m = a.size(0), n = w.size(0);
   TORCH_CHECK(m >= 1 && m <= 64, what, " needs 1 <= M <= 64");
-  TORCH_CHECK(n % 64 == 0 && k % 32 == 0, "N%64==0 and K%32==0 required");
+  TORCH_CHECK(n % n_mult == 0 && k % 32 == 0, "N%", n_mult,
+              "==0 and K%32==0 required");
   if (partials_only) {
     TORCH_CHECK(nsplits > 1, what, ": partials-only needs nsplits > 1");
   } else {
@@ -473,14 +476,17 @@ const void* check_skinny_args(const torch::Tensor& out,
 
 // config selects the kernel (skinny_gemm.hip): 0 = default ring with MT from
 // M, 1 = tall-K, 2 = tall-K with non-temporal W loads, 3 = A-resident (split-K
-// with a K-range that fits in LDS; groups = workgroups per split, 0 = auto).
+// with a K-range that fits in LDS; groups = workgroups per split, 0 = auto),
+// 4 = tall-K on 112-row tiles. The tall-K configs (1, 2, 4) take any N that
+// is a multiple of 16 (a tile may hang over N by whole waves); 0 and 3 need
+// a multiple of 64.
 void skinny_gemm_impl(torch::Tensor out, torch::Tensor part, torch::Tensor a,
                       torch::Tensor w, c10::optional<torch::Tensor> bias,
                       int64_t k_per_split, int64_t nsplits, int64_t config,
                       int64_t groups, bool combine) {
   const int m = a.size(0), k = a.size(1), n = w.size(0);
   TORCH_CHECK(w.size(1) == k);
-  TORCH_CHECK(0 <= config && config <= 3, "config in 0..3");
+  TORCH_CHECK(0 <= config && config <= 4, "config in 0..4");
   TORCH_CHECK(k_per_split >= 32 && k_per_split % 32 == 0 &&
               nsplits * k_per_split >= k, "splits must cover K");
   TORCH_CHECK(config != 3 ||
@@ -490,8 +496,10 @@ void skinny_gemm_impl(torch::Tensor out, torch::Tensor part, torch::Tensor a,
   TORCH_CHECK(0 <= groups && groups <= 65535, "groups in 0..65535");
   TORCH_CHECK(nsplits <= 65535, "too many splits");
   const int mrows = arks_skinny_slab_rows(m, (int)config);
-  const void* bias_ptr = check_skinny_args(out, part, a, w, bias, k, nsplits,
-                                           mrows, !combine, "skinny_gemm");
+  const void* bias_ptr =
+      check_skinny_args(out, part, a, w, bias, k, nsplits, mrows,
+                        config == 0 || config == 3 ? 64 : 16, !combine,
+                        "skinny_gemm");
   arks_skinny_gemm(nsplits > 1 ? part.data_ptr() : nullptr,
                    combine ? out.data_ptr() : nullptr, a.data_ptr(),
                    w.data_ptr(), bias_ptr, m, n, k, (int)k_per_split,
@@ -825,12 +833,14 @@ void splitk_add_rmsnorm(torch::Tensor out, torch::Tensor part,
 
 // rope_and_cache whose q/k/v input is the split-K partials of the fused qkv
 // skinny GEMM. Writes rotated q to q_out [T, Hq*D]; k/v only to the cache.
+// groups = workgroups per token (1 = the whole token in one workgroup).
 void splitk_rope_and_cache(torch::Tensor positions, torch::Tensor part,
                            c10::optional<torch::Tensor> bias,
                            torch::Tensor q_out, torch::Tensor k_cache,
                            torch::Tensor v_cache, torch::Tensor slot_mapping,
                            torch::Tensor cos_sin, int64_t head_dim,
-                           int64_t nsplits, int64_t mrows) {
+                           int64_t nsplits, int64_t mrows, int64_t groups) {
+  TORCH_CHECK(1 <= groups && groups <= 65535, "groups in 1..65535");
   TORCH_CHECK(positions.scalar_type() == torch::kInt64 &&
               positions.is_contiguous());
   TORCH_CHECK(slot_mapping.scalar_type() == torch::kInt64 &&
@@ -855,7 +865,7 @@ void splitk_rope_and_cache(torch::Tensor positions, torch::Tensor part,
                              v_cache.data_ptr(), slot_mapping.data_ptr(),
                              cos_sin.data_ptr(), T, (int)head_dim, nq, nkv,
                              block_size, (int)nsplits, (int)mrows,
-                             kv_fp8 ? 1 : 0, current_stream());
+                             kv_fp8 ? 1 : 0, (int)groups, current_stream());
 }
 
 void rmsnorm_fp8(torch::Tensor out, torch::Tensor inv_scale,
@@ -902,21 +912,42 @@ void quant_fp8_rows(torch::Tensor out, torch::Tensor inv_scale,
                       x.size(0), x.size(1), current_stream());
 }
 
-void greedy_sample(torch::Tensor out, torch::Tensor logits) {
+// chunks = workgroups per row. Above 1, `pairs` is the workspace the chunk
+// winners go through: int32 [rows, chunks, 2] (value bits, index).
+static void* check_sample_pairs(const torch::Tensor& out,
+                                const torch::Tensor& logits,
+                                const c10::optional<torch::Tensor>& pairs,
+                                int64_t chunks) {
   check_bf16_contig(logits, "logits");
-  TORCH_CHECK(out.scalar_type() == torch::kInt64);
-  arks_greedy_sample(out.data_ptr(), logits.data_ptr(), logits.size(0),
-                     logits.size(1), current_stream());
+  TORCH_CHECK(logits.dim() == 2);
+  TORCH_CHECK(out.scalar_type() == torch::kInt64 && out.is_contiguous() &&
+              out.numel() >= logits.size(0));
+  TORCH_CHECK(1 <= chunks && chunks <= 65535, "chunks in 1..65535");
+  if (chunks == 1) return nullptr;
+  TORCH_CHECK(pairs.has_value() && pairs->is_cuda() &&
+                  pairs->scalar_type() == torch::kInt32 &&
+                  pairs->is_contiguous() &&
+                  pairs->numel() >= logits.size(0) * chunks * 2,
+              "chunks > 1 needs an int32 workspace of rows * chunks * 2");
+  return pairs->data_ptr();
+}
+
+void greedy_sample(torch::Tensor out, torch::Tensor logits,
+                   c10::optional<torch::Tensor> pairs, int64_t chunks) {
+  void* ws = check_sample_pairs(out, logits, pairs, chunks);
+  arks_greedy_sample(out.data_ptr(), ws, logits.data_ptr(), logits.size(0),
+                     logits.size(1), (int)chunks, current_stream());
 }
 
 void gumbel_sample(torch::Tensor out, torch::Tensor logits,
-                   torch::Tensor temperatures, torch::Tensor uniform) {
-  check_bf16_contig(logits, "logits");
-  TORCH_CHECK(out.scalar_type() == torch::kInt64);
+                   torch::Tensor temperatures, torch::Tensor uniform,
+                   c10::optional<torch::Tensor> pairs, int64_t chunks) {
+  void* ws = check_sample_pairs(out, logits, pairs, chunks);
   TORCH_CHECK(temperatures.scalar_type() == torch::kFloat32);
   TORCH_CHECK(uniform.scalar_type() == torch::kFloat32);
-  arks_gumbel_sample(out.data_ptr(), logits.data_ptr(), temperatures.data_ptr(),
-                     uniform.data_ptr(), logits.size(0), logits.size(1),
+  arks_gumbel_sample(out.data_ptr(), ws, logits.data_ptr(),
+                     temperatures.data_ptr(), uniform.data_ptr(),
+                     logits.size(0), logits.size(1), (int)chunks,
                      current_stream());
 }
 
@@ -1298,9 +1329,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w8_skinny_gemm_partials", &w8_skinny_gemm_partials);
   m.def("w8_dequant", &w8_dequant);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
-  m.def("splitk_rope_and_cache", &splitk_rope_and_cache);
-  m.def("greedy_sample", &greedy_sample);
-  m.def("gumbel_sample", &gumbel_sample);
+  m.def("splitk_rope_and_cache", &splitk_rope_and_cache, py::arg("positions"),
+        py::arg("part"), py::arg("bias"), py::arg("q_out"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("slot_mapping"), py::arg("cos_sin"),
+        py::arg("head_dim"), py::arg("nsplits"), py::arg("mrows"),
+        py::arg("groups") = 1);
+  m.def("greedy_sample", &greedy_sample, py::arg("out"), py::arg("logits"),
+        py::arg("pairs") = py::none(), py::arg("chunks") = 1);
+  m.def("gumbel_sample", &gumbel_sample, py::arg("out"), py::arg("logits"),
+        py::arg("temperatures"), py::arg("uniform"),
+        py::arg("pairs") = py::none(), py::arg("chunks") = 1);
   m.def("greedy_sample_masked", &greedy_sample_masked);
   m.def("gumbel_sample_masked", &gumbel_sample_masked);
   m.def("apply_token_bitmask", &apply_token_bitmask);

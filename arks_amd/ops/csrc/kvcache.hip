@@ -112,12 +112,15 @@ __global__ void rope_cache_kernel(
 // cached with rope_cache_kernel's arithmetic — bit-identical outputs without
 // the combine launch or the bf16 qkv round trip. Rotated q goes to a dense
 // [T, Hq*D] buffer; k and v go ONLY to the paged cache (the decode attention
-// kernel reads them from there). One workgroup per token as before, but the
-// kernel is bound by the latency of the partial reads (nsplits x 18 KB per
-// token at Qwen2.5-7B), so (a) a thread covers four rotary pairs, making the
-// loads 16 B, and (b) rotation items and v items share one index space that
-// the launcher covers with up to 1024 threads: every thread then makes one
-// memory round trip instead of three dependent ones.
+// kernel reads them from there). The kernel is bound by the latency of the
+// partial reads (nsplits x 18 KB per token at Qwen2.5-7B), so (a) a thread
+// covers four rotary pairs, making the loads 16 B, and (b) rotation items and
+// v items share one index space that the launcher covers with up to 1024
+// threads per token: every thread then makes one memory round trip instead
+// of three dependent ones. grid = (tokens, groups): the groups of a token
+// share its index space (no item needs another, so any grouping gives the
+// same bits), which spreads a decode batch of fewer tokens than compute
+// units over the chip instead of pulling a token's partials through one CU.
 // ---------------------------------------------------------------------------
 template <bool FP8>
 __global__ __launch_bounds__(1024) void splitk_rope_cache_kernel(
@@ -148,7 +151,8 @@ __global__ __launch_bounds__(1024) void splitk_rope_cache_kernel(
   const int nrot = pg.valid ? nrot_q + num_kv_heads * quads : nrot_q;
   const int nvec = pg.valid ? num_kv_heads * head_dim / 8 : 0;
   const int v_col0 = (num_q_heads + num_kv_heads) * head_dim;
-  for (int idx = threadIdx.x; idx < nrot + nvec; idx += blockDim.x) {
+  for (int idx = blockIdx.y * blockDim.x + threadIdx.x; idx < nrot + nvec;
+       idx += blockDim.x * gridDim.y) {
     if (idx < nrot) {
       const int h = idx / quads;
       const int p4 = (idx % quads) * 4;
@@ -239,12 +243,16 @@ extern "C" void arks_splitk_rope_and_cache(
     void* k_cache, void* v_cache, const void* slot_mapping,
     const void* cos_sin, int num_tokens, int head_dim, int num_q_heads,
     int num_kv_heads, int block_size, int nsplits, int mrows_pad, int kv_fp8,
-    hipStream_t stream) {
+    int groups, hipStream_t stream) {
   if (num_tokens == 0) return;
-  // one item per thread where the token's work fits (see the kernel comment)
+  // one item per thread where the token's work fits (see the kernel
+  // comment), over `groups` workgroups per token
   const int items = (num_q_heads + num_kv_heads) * (head_dim / 8) +
                     num_kv_heads * head_dim / 8;
-  dim3 grid(num_tokens), block(std::min(1024, (items + 63) / 64 * 64));
+  groups = std::max(1, std::min(groups, (items + 63) / 64));
+  const int per_group = (items + groups - 1) / groups;
+  dim3 grid(num_tokens, groups);
+  dim3 block(std::min(1024, (per_group + 63) / 64 * 64));
   const int64_t split_stride =
       (int64_t)mrows_pad * (num_q_heads + 2 * num_kv_heads) * head_dim;
   dispatch_kv_fp8(kv_fp8, [&](auto fp8) {

@@ -4,8 +4,9 @@
 // tuned algos reach only 1.3-2.9 TB/s on the decode shapes
 // (profiles/r01_p2, profiles/data/dec_top r2).
 //
-//   grid = (N/64, nsplits), or (N/128, nsplits) for the tall-K configs: a
-//   workgroup owns an N-tile of 16 rows per wave and a K-range.
+//   grid = (N/64, nsplits), or (N/128, nsplits) and (N/112, nsplits) for the
+//   tall-K configs: a workgroup owns an N-tile of 16 rows per wave and a
+//   K-range.
 //   W is read exactly once, 16 B/lane (guide G13), into a register ring of
 //   SK_D = 4 chunks of 128 k per wave (16 KB of W per wave in flight).
 //   A (the activations, tiny, L2-hot) rides in the same ring, one chunk
@@ -17,7 +18,11 @@
 //   four waves at M = 64 half of a CU's fetches are A re-read from L2; a
 //   probe build without the A loads ran the down-proj 9 us (23 %) faster.
 //   Two answers, by K-range. The tall-K configs run eight waves per
-//   workgroup: the same W per CU against half the A. Split-K plans whose
+//   workgroup: the same W per CU against half the A (seven where 112-row
+//   tiles put a workgroup on every CU and 128-row tiles do not: the 7B
+//   down-proj, 32 x 8 = 256 workgroups against 224, 8 % less W through each
+//   CU's load path; in the graph 34.8 -> 32.9 us,
+//   profiles/r08_all_cus.md). Split-K plans whose
 //   K-range is at most 512 (qkv, o_proj) run skinny_resident_kernel
 //   (config 3, below): one workgroup per CU fetches its A slice once, keeps
 //   it in LDS and streams all of the CU's slabs of W past it, 0.44 bytes of
@@ -57,20 +62,26 @@
 //   splitk_reduce (common.h); skinny_combine_kernel is the fallback that
 //   materialises a bf16 [M, N].
 //
-// The file builds eleven kernels: skinny_gemm_kernel<MT> for MT 1..4 (launch
+// The file builds twelve kernels: skinny_gemm_kernel<MT> for MT 1..4 (launch
 // config 0, MT from M, four waves), <4, false, 8> for the tall-K plan of
 // the down-proj shape (config 1, eight waves), <4, true, 8> with
-// non-temporal W loads (config 2), skinny_resident_kernel<MT> for MT 1..4
-// (config 3: split-K with K-ranges of at most 512, A resident in LDS), and
-// skinny_combine_kernel. The experiments that lost — global-direct A reads,
+// non-temporal W loads (config 2), <4, false, 7> for tall-K plans that fill
+// more CUs on 112-row tiles (config 4, seven waves),
+// skinny_resident_kernel<MT> for MT 1..4 (config 3: split-K with K-ranges of
+// at most 512, A resident in LDS), and skinny_combine_kernel. The
+// experiments that lost — global-direct A reads,
 // wave-private barrier-free staging, silu_mul fused into the A staging,
 // shifted rings of other (KC, PF) — are recorded with their numbers in
 // profiles/r02_final.md, eight-wave and two-per-CU decompositions of the
-// resident kernel in profiles/r07_resident_a.md; the MLP runs
-// silu_mul_kernel (elementwise.hip) ahead of the down-proj.
+// resident kernel in profiles/r07_resident_a.md, a flat grid with the split
+// fastest (split = id % nsplits, so that an XCD's L2 sees one K-slice of A)
+// in profiles/r08_all_cus.md: qkv 12.5 -> 12.8 us in the graph, the
+// down-proj +0.3 to +1.5 us cold. The MLP runs silu_mul_kernel
+// (elementwise.hip) ahead of the down-proj.
 //
-// N must be a multiple of 64 and K of 32 (true for every Qwen/Llama shape;
-// the Python wrapper falls back to hipBLASLt otherwise).
+// N must be a multiple of 64 (of 16 for the tall-K configs, whose last tile
+// may hang over N by whole waves) and K of 32 (true for every Qwen/Llama
+// shape; the Python wrapper falls back to hipBLASLt otherwise).
 #include "common.h"
 
 #include <algorithm>
@@ -133,8 +144,11 @@ constexpr int SK_D = 4;     // chunks a wave keeps in flight (register ring)
 // chunk a workgroup stages is as many bytes as the W chunk of four waves,
 // and it comes through the same per-CU load path (from L2), so at WAVES = 4
 // half of what a CU fetches is A. The tall-K configs run WAVES = 8, one
-// 128-row workgroup per CU: the same W per CU against half the A. A wave's
-// MFMA sequence does not depend on WAVES.
+// 128-row workgroup per CU: the same W per CU against half the A; or
+// WAVES = 7 where that occupies more CUs. There the 448 threads stage 28
+// rows of A per pass, three passes for 64 rows: 48 + 64 VGPRs of ring
+// against 32 + 64, 238 in all, no scratch. A wave's MFMA sequence does not
+// depend on WAVES.
 template <int MT, bool NT = false, int WAVES = 4>
 __global__ __launch_bounds__(64 * WAVES, 2) void skinny_gemm_kernel(
     float* __restrict__ part,   // [nsplits, 16*MT, N] (nsplits > 1)
@@ -151,9 +165,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void skinny_gemm_kernel(
   constexpr int THREADS = 64 * WAVES;
   constexpr int NTW = 16 * WAVES;        // N rows per workgroup
   constexpr int RPP = THREADS / CPT;     // A rows staged per pass
-  constexpr int NIT = 16 * MT / RPP;     // A loads per thread per chunk
+  // A loads per thread per chunk. Seven waves stage 28 rows per pass, which
+  // does not divide 64: the third pass runs past row 63 (see arow, write_a).
+  constexpr int NIT = (16 * MT + RPP - 1) / RPP;
   static_assert(D % 2 == 0, "LDS slot parity follows the ring slot");
-  static_assert(NIT * RPP == 16 * MT, "A chunk must divide over the threads");
   const int n0 = blockIdx.x * NTW;
   const int kb = blockIdx.y * k_per_split;
   const int ke = min(k_total, kb + k_per_split);
@@ -177,8 +192,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void skinny_gemm_kernel(
 #pragma unroll
   for (int t = 0; t < MT; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
 
-  // The last workgroup of a WAVES = 8 launch may hang over N (N % 128 = 64):
-  // its upper waves stream the last row again and store nothing.
+  // The last workgroup of a WAVES = 7 or 8 launch may hang over N (N is a
+  // multiple of 16, not of the tile): its upper waves stream the last row
+  // again and store nothing.
   const bool wave_live = n0 + wave * 16 < n_total;
   const bf16* wrow =
       w + (int64_t)min(n0 + wave * 16 + lq, n_total - 1) * k_total + 8 * la;
@@ -187,6 +203,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void skinny_gemm_kernel(
   // COMPILE-TIME chunk width (a runtime divisor costs a ~30-op division per
   // index, PMC r2). Branchless: rows past m_rows and columns past k_total
   // are clamped to real in-bounds values that the MFMAs never consume.
+  // Where the passes overshoot the 16*MT rows (WAVES = 7), the threads past
+  // the last row load it again (m_rows - 1 <= 16*MT - 1 is their clamp too)
+  // and write_a puts the same bytes in the same place a second time: no
+  // guard around a load or a ds_write, and the counts stay exact.
   const int acol = (tid % CPT) * 8;
   const bf16* arow[NIT];
 #pragma unroll
@@ -224,9 +244,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void skinny_gemm_kernel(
   };
   auto write_a = [&](const ushort8 (&ad)[NIT], int buf) {
 #pragma unroll
-    for (int it = 0; it < NIT; ++it)
-      *reinterpret_cast<ushort8*>(
-          &lds.a_buf[buf][tid / CPT + it * RPP][acol]) = ad[it];
+    for (int it = 0; it < NIT; ++it) {
+      int row = tid / CPT + it * RPP;
+      if constexpr (NIT * RPP != 16 * MT) row = min(row, 16 * MT - 1);
+      *reinterpret_cast<ushort8*>(&lds.a_buf[buf][row][acol]) = ad[it];
+    }
   };
   // MFMAs of one chunk, ascending k; kw = valid width (multiple of 32).
   auto mfma_chunk = [&](const ushort8 (&wd)[KSTEPS], int buf, int kw) {
@@ -323,7 +345,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void skinny_gemm_kernel(
     }
   }
   __syncthreads();
-  const int nvalid = min(NTW, n_total - n0);  // 64 or NTW
+  const int nvalid = min(NTW, n_total - n0);
   for (int i = tid; i < m_rows * NTW; i += THREADS) {
     const int m = i / NTW;
     const int n = i % NTW;
@@ -579,8 +601,8 @@ extern "C" void arks_skinny_combine(void* out, const void* part,
 }
 
 // M tiles of the kernel that `config` launches for m_rows rows: configs 0
-// and 3 take MT from M, the tall-K configs (1, 2) always run MT = 4 (64-row
-// slabs, which the tall-K plan's consumers expect).
+// and 3 take MT from M, the tall-K configs (1, 2, 4) always run MT = 4
+// (64-row slabs, which the tall-K plan's consumers expect).
 static int skinny_mt(int m_rows, int config) {
   return config == 0 || config == 3 ? std::min((m_rows + 15) / 16, 4) : 4;
 }
@@ -639,7 +661,9 @@ static void launch_resident(float* part, const bf16* a, const bf16* w,
 // config 0: MT from M, four waves; 1: tall-K plan (MT=4, eight waves);
 // 2: tall-K with non-temporal W loads; 3: A-resident, split-K only
 // (nsplits > 1, k_per_split <= SKR_KMAX), `groups` workgroups per split
-// (0 = auto; the other configs ignore it).
+// (0 = auto; the other configs ignore it); 4: tall-K on seven waves
+// (112-row tiles: 3584 / 112 x 8 splits is one workgroup on each of 256
+// CUs, where 128-row tiles leave 32 idle; N a multiple of 16).
 // combine = false (nsplits > 1 only) stops after the GEMM: the f32 partials
 // stay in `part` for a consumer kernel that reduces them itself.
 extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
@@ -665,8 +689,9 @@ extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
                           arks_skinny_slab_rows(m_rows, config), stream);
     return;
   }
-  // The tall-K configs run 8 waves (128 rows of W) per workgroup.
-  const int waves = config == 0 ? 4 : 8;
+  // The tall-K configs run 8 or 7 waves (128 or 112 rows of W) per
+  // workgroup.
+  const int waves = config == 0 ? 4 : config == 4 ? 7 : 8;
   dim3 grid((n_total + 16 * waves - 1) / (16 * waves), nsplits);
   dim3 block(64 * waves);
   auto launch = [&](auto kernel) {
@@ -675,7 +700,9 @@ extern "C" void arks_skinny_gemm(void* part, void* out, const void* a,
                        (const bf16*)bias, m_rows, n_total, k_total,
                        k_per_split, nsplits, a_stride);
   };
-  if (config == 2) {
+  if (config == 4) {
+    launch(skinny_gemm_kernel<4, false, 7>);
+  } else if (config == 2) {
     launch(skinny_gemm_kernel<4, true, 8>);
   } else if (config == 1) {
     launch(skinny_gemm_kernel<4, false, 8>);

@@ -5,15 +5,17 @@ step, where 15 GB of other weights pass between two calls.
 
     PYTHONPATH=. python scripts/bench_skinny_cold.py [LABEL] [--config C]
         [--groups G[,G...]] [--shapes NAME[,NAME...]]
+        [--down-config C[,C...]]
 
 --config overrides the launch config of the split-K qkv/o shapes (0 = the
 chunk-ring kernel, 3 = the A-resident kernel; default: what ops.skinny_gemm
 routes to). --groups times config 3 once per value (workgroups per split,
-0 = auto).
+0 = auto). --down-config times the down-proj shape once per value (1 =
+128-row tiles, 4 = 112-row tiles; default: what ops.skinny_gemm routes to).
 
 Companion of scripts/bench_membw_cold.hip (the raw-read floor of the same
 pattern and grid); results in profiles/r05_skinny_stream.md and
-profiles/r07_resident_a.md.
+profiles/r07_resident_a.md and profiles/r08_all_cus.md.
 """
 import argparse
 
@@ -26,6 +28,7 @@ ap.add_argument("label", nargs="?", default="build")
 ap.add_argument("--config", type=int, default=None)
 ap.add_argument("--groups", default="0")
 ap.add_argument("--shapes", default=None)
+ap.add_argument("--down-config", default=None)
 args = ap.parse_args()
 label = args.label
 native = ops._native()
@@ -40,6 +43,8 @@ if args.shapes:
 for name, M, N, K in shapes:
     config, nsplits, kps, mrows = ops._skinny_plan(M, N, K)
     config = ops._skinny_resident_config(config, M, nsplits, kps)
+    config = ops._skinny_tallk7_config(config, N, nsplits, ops._cu_count(
+        torch.device(dev, torch.cuda.current_device())))
     if name == "down_nt":
         config = 2
     elif args.config is not None and not name.startswith("down"):
@@ -49,8 +54,12 @@ for name, M, N, K in shapes:
     ws = [torch.randn(N, K, dtype=torch.bfloat16, device=dev) * 0.05 for _ in range(nbuf)]
     a = torch.randn(M, K, dtype=torch.bfloat16, device=dev) * 0.5
     part = torch.empty(nsplits * mrows * N, dtype=torch.float32, device=dev)
-    for groups in ([int(g) for g in args.groups.split(",")]
-                   if config == 3 else [0]):
+    configs = ([int(c) for c in args.down_config.split(",")]
+               if name == "down" and args.down_config else [config])
+    runs = [(c, g) for c in configs
+            for g in ([int(g) for g in args.groups.split(",")]
+                      if c == 3 else [0])]
+    for config, groups in runs:
         def rot(n):
             for _ in range(n):
                 for w in ws:
