@@ -385,10 +385,178 @@ class MoEMLP(nn.Module):
             rows = ref._unpack_nibbles(t).t().contiguous()  # [N, K]
             qw[le, r0:r0 + N].copy_(ref._pack_nibbles(rows))
 
-    def _forward_w4(self, x):
-        """GPU forward over W4 experts, the same for every T: route once,
-        then two routed grouped GEMMs that stream only the experts the batch
-        selected. Up to DENSE_TOKENS the launch shapes depend on T alone (no
+    # ---- W8 experts (block-scaled FP8 checkpoints, quantize_w8) ----
+    # The checkpoint's e4m3 bytes stacked per local expert, ops/ref.py's W8
+    # format with a leading expert dimension: w13_w8 [E, 2I, H] is
+    # [gate | up] along N with scales [E, H/128, 2I]; w2_w8 [E, H, I] with
+    # scales [E, I/128, H]. The bf16 w13 / w2 parameters are dropped. On CPU
+    # the W4 convention holds: bf16 [E, in, out] buffers named w13 / w2
+    # (dequantized in f32, rounded once) stand in and the bf16 forward runs
+    # on them; on GPU a W8 block has no bf16 copy of its experts.
+    w8 = False
+
+    _W8_PROJS = {"gate": ("gate_proj", "w1"), "up": ("up_proj", "w3"),
+                 "down": ("down_proj", "w2")}
+
+    def w8_supported(self) -> bool:
+        """What w8_moe_gemm_kernel needs of both expert GEMMs: K a multiple
+        of the 128 scale block (N = 2I and H are then multiples of 64)."""
+        return self.hidden % 128 == 0 and self.inter % 128 == 0
+
+    def w8_check_shapes(self, name: str) -> None:
+        if not self.w8_supported():
+            raise ValueError(
+                f"{name}: MoE expert width {self.inter} is not supported: W8 "
+                f"experts need hidden and expert widths that are multiples "
+                f"of the scale block 128, got hidden={self.hidden}, expert "
+                f"width={self.inter}"
+            )
+
+    def w8_weight(self, which: str):
+        return (getattr(self, f"{which}_w8"),
+                getattr(self, f"{which}_w8_scales"))
+
+    def init_w8(self, name: str = "moe") -> None:
+        """Switch to (empty) W8 storage; the bf16 parameters are dropped, so
+        a block switched before its weights stream in never holds them."""
+        from ..ops import ref
+
+        self.w8_check_shapes(name)
+        dev = self.w13.device
+        E, H, I = self.local_experts, self.hidden, self.inter
+        del self._parameters["w13"]
+        del self._parameters["w2"]
+        for which, (N, K) in (("w13", (2 * I, H)), ("w2", (H, I))):
+            self.register_buffer(
+                f"{which}_w8",
+                torch.zeros(E, N, K, dtype=torch.float8_e4m3fn, device=dev),
+                persistent=False)
+            self.register_buffer(
+                f"{which}_w8_scales",
+                torch.zeros(E, K // ref.W8_BLOCK, N, dtype=torch.float32,
+                            device=dev),
+                persistent=False)
+        self.w8 = True
+        self._w8_got = set()    # (local expert, projection, kind) arrived
+        self._w8_names = {}     # projection -> (checkpoint prefix, leaf)
+
+    def load_fp8_expert(self, name: str, le: int, proj: str, kind: str,
+                        t: torch.Tensor) -> None:
+        """One FP8 tensor (kind: weight / weight_scale_inv) of local expert
+        le's gate / up / down projection into the stacked buffers: gate
+        fills rows [0, I) of w13, up rows [I, 2I). The weight is stored as it
+        is; the block scales are expanded to one row per output channel, cut
+        to N and transposed. Each tensor lands on its own."""
+        from ..ops import ref
+
+        if not self.w8:
+            raise ValueError(
+                f"{name}: FP8 expert tensor in the checkpoint but the block "
+                "was not prepared for FP8 (config.json lacks "
+                "quantization_config, or the experts are on its skip list?)"
+            )
+        H, I, B = self.hidden, self.inter, ref.W8_BLOCK
+        which, r0, N, K = {"gate": ("w13", 0, I, H), "up": ("w13", I, I, H),
+                           "down": ("w2", 0, H, I)}[proj]
+        w8, sc = self.w8_weight(which)
+        if kind == "weight":
+            if t.dtype != torch.float8_e4m3fn:
+                raise ValueError(
+                    f"{name}: plain {t.dtype} weight of an MoE expert, but "
+                    "the block was prepared for FP8 (mixed-precision expert "
+                    "checkpoints are not supported)")
+            want = (N, K)
+        elif kind == "weight_scale_inv":
+            want = (-(-N // B), K // B)
+        else:
+            raise ValueError(f"{name}: unexpected tensor kind {kind!r} for "
+                             "an FP8 expert")
+        if tuple(t.shape) != want:
+            raise ValueError(
+                f"{name}: shape {tuple(t.shape)}, expected {want} for a "
+                f"{N}x{K} projection at block size {B}"
+            )
+        if kind == "weight":
+            # byte copy: no conversion may touch the checkpoint's codes
+            w8[le, r0:r0 + N].view(torch.uint8).copy_(t.view(torch.uint8))
+        else:
+            rows = t.float().repeat_interleave(B, dim=0)[:N]     # [N, K/128]
+            sc[le, :, r0:r0 + N].copy_(rows.t())
+        self._w8_got.add((le, proj, kind))
+        head, sep, _ = name.rpartition(".experts.")
+        if sep and proj not in self._w8_names:
+            self._w8_names[proj] = (head, name.split(".")[-2])
+
+    def finalize_w8(self, name: str = "moe") -> None:
+        """After loading: every (local expert, projection, kind) must have
+        arrived. On CPU keep the bf16 dequantized experts that the bf16
+        forward runs on."""
+        from ..ops import ref
+
+        got = getattr(self, "_w8_got", None)
+        if got is not None:
+            style = 0
+            if self._w8_names:
+                style = 1 if next(iter(self._w8_names.values()))[1] in (
+                    "w1", "w2", "w3") else 0
+            for le in range(self.local_experts):
+                for proj, leaves in self._W8_PROJS.items():
+                    for kind in ("weight", "weight_scale_inv"):
+                        if (le, proj, kind) in got:
+                            continue
+                        head, leaf = self._w8_names.get(
+                            proj, (f"{name}", leaves[style]))
+                        raise ValueError(
+                            f"{head}.experts.{self.expert_base + le}.{leaf}."
+                            f"{kind}: missing from the checkpoint for the "
+                            f"FP8 experts of {name}")
+            self._w8_got = None
+        if self.w13_w8.is_cuda:
+            return
+        for which in ("w13", "w2"):
+            w8, sc = self.w8_weight(which)
+            deq = torch.stack([
+                ref.w8_dequant(w8[e], sc[e]).to(torch.bfloat16).t()
+                for e in range(self.local_experts)
+            ]).contiguous()
+            if which in self._buffers:
+                del self._buffers[which]
+            self.register_buffer(which, deq, persistent=False)
+
+    def quantize_w8(self, name: str = "moe") -> None:
+        """Block-scaled W8 of loaded bf16 experts, one expert at a time
+        (ops.ref.w8_quantize), so the transient memory is one expert's."""
+        from ..ops import ref
+
+        self.w8_check_shapes(name)
+        bf16 = {"w13": self.w13.data, "w2": self.w2.data}
+        self.init_w8(name)
+        self._w8_got = None     # filled here, nothing streams in
+        I = self.inter
+        for which, w in bf16.items():
+            w8, sc = self.w8_weight(which)
+            for e in range(self.local_experts):
+                # stored [in, out]; the quantizer takes [N, K] = [out, in].
+                # gate and up are separate tensors in a checkpoint, each
+                # with its own blocks along N.
+                full = w[e].t()
+                parts = ((0, full[:I]), (I, full[I:])) if which == "w13" \
+                    else ((0, full),)
+                for r0, part in parts:
+                    q, blocks = ref.w8_quantize(part)
+                    n = part.shape[0]
+                    w8[e, r0:r0 + n].view(torch.uint8).copy_(
+                        q.view(torch.uint8))
+                    sc[e, :, r0:r0 + n].copy_(
+                        ref.w8_expand_scales(blocks, n))
+        del bf16
+        self.finalize_w8(name)
+
+    def _forward_routed(self, x, gemm, w13, w2):
+        """GPU forward over quantized experts (gemm = ops.w4_moe_gemm on the
+        packed W4 triples, ops.w8_moe_gemm on the W8 pairs), the same for
+        every T: route once, then two routed grouped GEMMs that stream only
+        the experts the batch selected. Up to DENSE_TOKENS the launch shapes depend on T alone (no
         host sync; the decode graphs capture it); above it one sync per layer
         fetches the longest expert list to size the grid."""
         from ..parallel.comm import tp_all_reduce
@@ -400,15 +568,13 @@ class MoEMLP(nn.Module):
                                       self.local_experts)
         max_rows = (T if T <= self.DENSE_TOKENS
                     else max(1, int(counts.max().item())))
-        gu = ops.w4_moe_gemm(x, self.w4_packed("w13"), counts, pairs, k,
-                             max_rows)                     # [T*k, 2I]
+        gu = gemm(x, w13, counts, pairs, k, max_rows)      # [T*k, 2I]
         h = ops.silu_mul(gu)                               # [T*k, I]
         # y row 0 is a zero row: the pairs of experts other ranks own are
         # never written, and the mix multiplies whatever it reads (0 * NaN
         # is NaN), so their slots read row 0 at weight 0.
         y = x.new_empty(T * k + 1, self.hidden)
-        ops.w4_moe_gemm(h, self.w4_packed("w2"), counts, pairs, 1, max_rows,
-                        out=y[1:])
+        gemm(h, w2, counts, pairs, 1, max_rows, out=y[1:])
         rows = torch.arange(1, T * k + 1, dtype=torch.int32,
                             device=x.device).view(T, k)
         if self.local_experts != self.num_experts:
@@ -429,7 +595,13 @@ class MoEMLP(nn.Module):
         from ..parallel.comm import tp_all_reduce
 
         if self.w4 and x.is_cuda:
-            return self._forward_w4(x)
+            return self._forward_routed(x, ops.w4_moe_gemm,
+                                        self.w4_packed("w13"),
+                                        self.w4_packed("w2"))
+        if self.w8 and x.is_cuda:
+            return self._forward_routed(x, ops.w8_moe_gemm,
+                                        self.w8_weight("w13"),
+                                        self.w8_weight("w2"))
         T = x.shape[0]
         router_logits = torch.nn.functional.linear(x, self.gate).float()
         # fused softmax+topk+renorm routing kernel (ops.moe_topk) replaces
@@ -713,8 +885,10 @@ class LlamaFamilyForCausalLM(nn.Module):
     # ---- block-scaled FP8 checkpoints (W8A16; format in ops/ref.py) ----
     # X.weight e4m3fn [N, K] + X.weight_scale_inv f32 [ceil(N/128),
     # ceil(K/128)] per quantized projection. The candidate layers are
-    # _w4_targets(experts=True); the routed experts have no grouped W8 kernel
-    # and are dequantized to bf16 at load, as is a quantized lm_head.
+    # _w4_targets(experts=True) plus the routed experts of every MoE block,
+    # which keep their e4m3 bytes stacked for the grouped W8 kernel (MoEMLP
+    # init_w8). A block whose widths that kernel cannot take is dequantized
+    # to bf16 at load, as is a quantized lm_head.
     _W8_KINDS = ("weight", "weight_scale_inv")
 
     @staticmethod
@@ -736,22 +910,47 @@ class LlamaFamilyForCausalLM(nn.Module):
                 return True
         return False
 
-    def quantize_w8(self) -> None:
+    def quantize_w8(self, experts: bool = False) -> None:
         """Block-scaled W8A16 of a loaded bf16 model in memory
-        (quantize_module_w8 over the layers an FP8 checkpoint quantizes; the
-        routed experts stay bf16). For tests and benchmarks: serving reads
-        the format from a checkpoint, there is no --quantization value."""
+        (quantize_module_w8 over the linear layers an FP8 checkpoint
+        quantizes; with experts=True the routed experts of every MoE block
+        too, otherwise they stay bf16). For tests and benchmarks: serving
+        reads the format from a checkpoint, there is no --quantization
+        value."""
         from ..parallel.layers import quantize_module_w8
 
+        if experts:
+            if self.cfg.num_local_experts == 0:
+                raise ValueError(
+                    "experts=True needs an MoE model, "
+                    f"{self.cfg.architecture} has no experts")
+            for name, moe in self._moe_blocks():
+                moe.w8_check_shapes(name)
         for name, mod in self._w4_targets(experts=True):
             quantize_module_w8(mod, name)
+        if experts:
+            for name, moe in self._moe_blocks():
+                moe.quantize_w8(name)
+
+    def _w8_expert_hf_names(self, name: str, moe) -> list[str]:
+        """HF module names of every routed expert projection of a block
+        (all ranks' experts, so that every rank decides alike)."""
+        if self.cfg.architecture.startswith("MixtralFor"):
+            sub, leaves = "block_sparse_moe", ("w1", "w3", "w2")
+        else:
+            sub, leaves = "mlp", ("gate_proj", "up_proj", "down_proj")
+        pre = name.rpartition(".")[0]
+        return [f"model.{pre}.{sub}.experts.{e}.{p}"
+                for e in range(moe.num_experts) for p in leaves]
 
     def prepare_fp8_checkpoint(self) -> None:
         """Switch the quantized layers to (empty) W8 storage BEFORE a
         block-scaled FP8 checkpoint streams in, so their bf16 weights are
         never allocated on the device; finalize_w8() completes the switch
         after loading. The parts of a fused projection must all be quantized
-        or all be on the checkpoint's skip list."""
+        or all be on the checkpoint's skip list, and so must the routed
+        experts of an MoE block; a block whose widths the grouped kernel
+        cannot take stays bf16 and is dequantized as its tensors arrive."""
         from ..parallel.layers import init_module_w8
 
         self._w8_pending = {}
@@ -768,6 +967,20 @@ class LlamaFamilyForCausalLM(nn.Module):
                     "left in bf16); they must all be FP8 or all plain")
             init_module_w8(mod, name)
             mod._w8_got = set()
+        for name, moe in self._moe_blocks():
+            names = self._w8_expert_hf_names(name, moe)
+            skipped = [self._w8_skipped(p) for p in names]
+            if all(skipped):
+                continue
+            if any(skipped):
+                plain = [p for p, s in zip(names, skipped) if s]
+                raise ValueError(
+                    f"{name}: the checkpoint quantizes only some parts of "
+                    f"this block's routed experts ({len(plain)} of "
+                    f"{len(names)} projections left in bf16, the first "
+                    f"{plain[0]}); they must all be FP8 or all plain")
+            if moe.w8_supported():
+                moe.init_w8(name)
 
     def finalize_w8(self) -> None:
         from ..parallel.layers import finalize_module_w8
@@ -797,13 +1010,35 @@ class LlamaFamilyForCausalLM(nn.Module):
                     f"{name}: the checkpoint has no {sorted(missing)} for "
                     "this FP8 layer")
             finalize_module_w8(mod)
+        dropped = False
+        for name, moe in self._moe_blocks():
+            if not moe.w8:
+                continue
+            moe.finalize_w8(name)
+            dropped = True
+            if (not moe.w13_w8.is_cuda
+                    and not getattr(self, "_w8_experts_logged", False)):
+                import logging
+
+                self._w8_experts_logged = True
+                logging.getLogger(__name__).warning(
+                    "FP8 routed experts are dequantized to bf16 on this "
+                    "device (the grouped W8 kernel runs on the GPU only): "
+                    "the model holds its experts at bf16 size")
+        if dropped and torch.cuda.is_available() and any(
+                moe.w13_w8.is_cuda for _, moe in self._moe_blocks()
+                if moe.w8):
+            # the dropped bf16 experts sit in the caching allocator; hand
+            # them back so profile_num_blocks sees them as free
+            torch.cuda.empty_cache()
 
     def _w8_target(self, stem: str):
         """(module, our name, fused HF partner stems or None, how) of the HF
         module `stem` (no "model." prefix) for an FP8 tensor; how is "col"
         (column-parallel, maybe fused), "row", "dequant" (dequantize to bf16
-        and load as a plain weight) or "skip" (another rank's expert). None
-        for a module that never holds FP8."""
+        and load as a plain weight), "expert" (a local routed expert of a W8
+        MoE block: module is the block) or "skip" (another rank's expert).
+        None for a module that never holds FP8."""
         if stem == "lm_head":
             return None, "lm_head", None, "dequant"
         parts = stem.split(".")
@@ -828,8 +1063,12 @@ class LlamaFamilyForCausalLM(nn.Module):
             if not isinstance(layer.mlp, MoEMLP) or len(parts) != 6:
                 return None
             le = int(parts[4]) - layer.mlp.expert_base
-            local = 0 <= le < layer.mlp.local_experts
-            return None, stem, None, "dequant" if local else "skip"
+            if not 0 <= le < layer.mlp.local_experts:
+                return None, stem, None, "skip"
+            if layer.mlp.w8 and parts[5] in (
+                    "gate_proj", "up_proj", "down_proj", "w1", "w3", "w2"):
+                return layer.mlp, stem, None, "expert"
+            return None, stem, None, "dequant"
         if sub.startswith("mlp.shared_expert."):
             if not isinstance(layer.mlp, MoEMLP) or layer.mlp.shared is None:
                 return None
@@ -885,6 +1124,13 @@ class LlamaFamilyForCausalLM(nn.Module):
                 "quantization_config?)")
         if how == "dequant":
             self._w8_dequant_load(full_name, stem, kind, w)
+            return True
+        if how == "expert":
+            parts = stem.split(".")
+            proj = {"gate_proj": "gate", "up_proj": "up", "down_proj": "down",
+                    "w1": "gate", "w3": "up", "w2": "down"}[parts[5]]
+            mod.load_fp8_expert(full_name, int(parts[4]) - mod.expert_base,
+                                proj, kind, w)
             return True
         if not getattr(mod, "w8", False):
             raise ValueError(
@@ -972,10 +1218,14 @@ class LlamaFamilyForCausalLM(nn.Module):
         del self._w8_pending[("dequant", stem)]
         if stem != "lm_head" and not self._w8_experts_logged:
             self._w8_experts_logged = True
+            mlp = self.layers[int(stem.split(".")[1])].mlp
+            why = ("the block was not prepared for FP8 experts"
+                   if mlp.w8_supported() else
+                   f"hidden={mlp.hidden}, expert width={mlp.inter}: the "
+                   "grouped W8 kernel needs multiples of 128")
             logging.getLogger(__name__).warning(
-                "FP8 routed experts are dequantized to bf16 at load (no "
-                "grouped W8 kernel): the model holds its experts at bf16 "
-                "size")
+                "FP8 routed experts are dequantized to bf16 at load (%s): "
+                "the model holds these experts at bf16 size", why)
         dev = self.embed_tokens.weight.device
         w8 = pair["weight"].to(dev)
         scales = ref.w8_expand_scales(pair["weight_scale_inv"].to(dev),

@@ -873,6 +873,30 @@ def w4_moe_gemm(a, packed, counts, pairs, src_div: int, max_rows: int,
     return out
 
 
+def w8_moe_gemm(a, weight, counts, pairs, src_div: int, max_rows: int,
+                out=None):
+    """Routed grouped W8A16 GEMM over the stacked local experts of an MoE
+    block (w8_moe_gemm_kernel): w4_moe_gemm for weight = (w8 e4m3fn
+    [E, N, K], scales f32 [E, K/128, N]), the checkpoint's bytes and its
+    block scales expanded per output row:
+    out[p] = a[p // src_div] @ (float(w8[e]) * scales[e])^T for every local
+    expert e and p in pairs[e][:counts[e]]. Same arguments, same capture
+    rules, and no eager fallback on GPU either."""
+    if not a.is_cuda:
+        return ref.w8_moe_gemm(a, weight, counts, pairs, src_div, out=out)
+    w8, scales = weight
+    T = pairs.shape[1] if pairs.dim() == 2 else 0
+    top_k = a.shape[0] * src_div // max(T, 1)
+    if out is None:
+        out = torch.empty((T * top_k, w8.shape[1]), dtype=a.dtype,
+                          device=a.device)
+    if not a.is_contiguous() or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    _native().w8_moe_gemm(out, a, w8, scales, counts, pairs, top_k, src_div,
+                          max_rows)
+    return out
+
+
 def rmsnorm_fp8(x, weight, eps: float = 1e-6):
     """Fused RMSNorm -> per-token fp8 e4m3: (out8, inv_scale). GPU-only
     fast path (hidden <= 8192); otherwise compose the unfused ops."""

@@ -159,6 +159,11 @@ void arks_w8_skinny_gemm(void* part, void* out, const void* a, const void* w8,
                          hipStream_t stream);
 void arks_w8_dequant(void* out, const void* w8, const void* scales,
                      int n_total, int k_total, hipStream_t stream);
+void arks_w8_moe_gemm(void* out, const void* a, const void* w8,
+                      const void* scales, const void* counts,
+                      const void* pairs, int n_experts, int t_cols,
+                      int n_pairs, int src_div, int slabs, int n_total,
+                      int k_total, int nw, hipStream_t stream);
 void arks_moe_route(void* counts, void* pairs, const void* ids, int n_pairs,
                     int T, int expert_base, int n_local, hipStream_t stream);
 void arks_mfma_probe(void* d, const void* a, const void* b, hipStream_t stream);
@@ -782,6 +787,64 @@ void w4_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor qw,
                    current_stream());
 }
 
+// The same over stacked W8 experts (w8_moe_gemm_kernel): w8 e4m3fn [E, N, K]
+// (the checkpoint's bytes), scales f32 [E, K/128, N].
+void w8_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w8,
+                 torch::Tensor scales, torch::Tensor counts,
+                 torch::Tensor pairs, int64_t top_k, int64_t src_div,
+                 int64_t max_rows) {
+  TORCH_CHECK(w8.is_cuda() && w8.scalar_type() == at::kFloat8_e4m3fn &&
+              w8.dim() == 3 && w8.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(w8.data_ptr()) % 16 == 0,
+              "w8 weight must be contiguous float8_e4m3fn [E, N, K] on GPU");
+  const int64_t ne = w8.size(0), n = w8.size(1), k = w8.size(2);
+  TORCH_CHECK(ne >= 1 && ne <= 65535, "need 1 <= E_local <= 65535");
+  TORCH_CHECK(k >= 128 && k % 128 == 0, "W8 needs K % 128 == 0, got K=", k);
+  TORCH_CHECK(n >= 64 && n % 64 == 0, "W8 needs N % 64 == 0, got N=", n);
+  TORCH_CHECK(n * k < ((int64_t)1 << 31), "expert weight too large");
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kFloat32 &&
+              scales.is_contiguous() && scales.dim() == 3 &&
+              scales.size(0) == ne && scales.size(1) == k / 128 &&
+              scales.size(2) == n &&
+              reinterpret_cast<uintptr_t>(scales.data_ptr()) % 16 == 0,
+              "scales must be contiguous f32 [E, K/128, N] on GPU");
+  check_bf16_contig(a, "a");
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(a.dim() == 2 && a.size(1) == k, "a must be [rows, K]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "a rows must be 16-byte aligned");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == torch::kInt32 &&
+              counts.is_contiguous() && counts.dim() == 1 &&
+              counts.size(0) == ne, "counts must be int32 [E_local] on GPU");
+  TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt32 &&
+              pairs.is_contiguous() && pairs.dim() == 2 &&
+              pairs.size(0) == ne && pairs.size(1) >= 1,
+              "pairs must be int32 [E_local, T] on GPU, got ", pairs.sizes());
+  const int64_t t_cols = pairs.size(1);
+  TORCH_CHECK(top_k >= 1, "top_k must be >= 1");
+  const int64_t n_pairs = t_cols * top_k;
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == n && out.size(0) == n_pairs,
+              "out must be [T*k, N] = [", n_pairs, ", ", n, "], got ",
+              out.sizes());
+  TORCH_CHECK(n_pairs < ((int64_t)1 << 31) / 2);
+  TORCH_CHECK(src_div >= 1 && a.size(0) * src_div >= n_pairs,
+              "a has ", a.size(0), " rows, too few for ", n_pairs,
+              " pairs at src_div=", src_div);
+  TORCH_CHECK(max_rows >= 1 && max_rows <= t_cols,
+              "need 1 <= max_rows <= T, got ", max_rows);
+  const auto dev = w8.device();
+  TORCH_CHECK(scales.device() == dev && a.device() == dev &&
+              out.device() == dev && counts.device() == dev &&
+              pairs.device() == dev);
+  const int64_t slabs = (max_rows + 63) / 64;
+  TORCH_CHECK(slabs <= 65535, "max_rows too large");
+  const int nw = (max_rows > 32 && n % 128 == 0) ? 2 : 1;  // as w4_moe_gemm
+  arks_w8_moe_gemm(out.data_ptr(), a.data_ptr(), w8.data_ptr(),
+                   scales.data_ptr(), counts.data_ptr(), pairs.data_ptr(),
+                   (int)ne, (int)t_cols, (int)n_pairs, (int)src_div,
+                   (int)slabs, (int)n, (int)k, nw, current_stream());
+}
+
 // Checks shared by the consumers of split-K partials [nsplits, mrows, n].
 const void* check_partials(const torch::Tensor& part,
                            const c10::optional<torch::Tensor>& bias,
@@ -1328,6 +1391,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w8_skinny_gemm", &w8_skinny_gemm);
   m.def("w8_skinny_gemm_partials", &w8_skinny_gemm_partials);
   m.def("w8_dequant", &w8_dequant);
+  m.def("w8_moe_gemm", &w8_moe_gemm);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache, py::arg("positions"),
         py::arg("part"), py::arg("bias"), py::arg("q_out"), py::arg("k_cache"),

@@ -29,6 +29,11 @@
 //   No zero-point, hence no activation sums (the W4 format's asum) and no
 //   LDS for them.
 //
+// w8_moe_gemm_kernel is the same chunk loop over the stacked experts of an
+// MoE block ([E, N, K] / [E, K/128, N]), its rows gathered and scattered
+// through the routing table that moe_route_kernel (moe.hip) writes; comment
+// at the kernel.
+//
 // w8_dequant_kernel expands the weight to bf16 [N, K] for the library GEMM
 // (M above the slab limit).
 #include "wq_stream.h"
@@ -140,6 +145,59 @@ __global__ __launch_bounds__(256) void w8_skinny_gemm_kernel(
       k_total, k_per_split);
 }
 
+// Routed grouped W8A16 GEMM over the local experts of an MoE block:
+//   for e < E_local, i < counts[e], p = pairs[e][i]:
+//     out[p, :] = a[p / src_div, :] @ (float(w8[e]) * scales[e])^T
+// w4_moe_gemm_kernel (w4_gemm.hip, read the notes there) with W8Weights: the
+// same grid = (N/(64*NW), E_local, slabs), a function of (N, E_local,
+// max_rows) only; the same uniform early return for a list shorter than the
+// slab, the same prow table and clamps, the same MT = 1..4 bodies picked once
+// by ceil(rows / 16). The expert's weight and scales are reached by 64-bit
+// offsets (e * N * K bytes, e * (K/128) * N floats); inside an expert the
+// dense format's addressing is unchanged. No zero-point, so no activation
+// sums in LDS.
+template <int NW, int PF>
+__global__ __launch_bounds__(256) void w8_moe_gemm_kernel(
+    bf16* __restrict__ out,             // [n_pairs, N]
+    const bf16* __restrict__ a,         // [>= ceil(n_pairs / src_div), K]
+    const uint8_t* __restrict__ w8,     // [E, N, K] e4m3fn
+    const float* __restrict__ scales,   // [E, K/128, N]
+    const int* __restrict__ counts,     // [E]
+    const int* __restrict__ pairs,      // [E, t_cols]
+    const int t_cols, const int n_pairs, const int src_div,
+    const int n_total, const int k_total) {
+  const int e = blockIdx.y;
+  const int cnt = min(max(counts[e], 0), t_cols);
+  const int r0 = blockIdx.z * 64;
+  if (r0 >= cnt) return;  // uniform
+  const int rows = min(cnt - r0, 64);
+
+  __shared__ __attribute__((aligned(16))) WqLds<NW, false> lds;
+  __shared__ int prow[64];
+  if (threadIdx.x < 64) {
+    const int p = pairs[(int64_t)e * t_cols + r0 + min((int)threadIdx.x,
+                                                       rows - 1)];
+    prow[threadIdx.x] = min(max(p, 0), n_pairs - 1);
+  }
+  __syncthreads();
+
+  const int64_t ww = (int64_t)e * n_total * k_total;
+  const int64_t wg = (int64_t)e * (k_total / WQ_KC) * n_total;
+  const WqLane ln(64 * NW);
+#define ARKS_W8_MOE_SLAB(MT)                                              \
+  wq_stream<MT, PF>(                                                      \
+      lds, ln, W8Weights<NW>(ln, w8 + ww, scales + wg, n_total, k_total), \
+      WqRoutedRows<MT>(out, a, prow, rows, src_div, k_total), 0, k_total, \
+      n_total)
+  switch ((rows + 15) / 16) {
+    case 1: ARKS_W8_MOE_SLAB(1); break;
+    case 2: ARKS_W8_MOE_SLAB(2); break;
+    case 3: ARKS_W8_MOE_SLAB(3); break;
+    default: ARKS_W8_MOE_SLAB(4); break;
+  }
+#undef ARKS_W8_MOE_SLAB
+}
+
 // out[n][16c..16c+15] = bf16(float(w8) * s): 16 weights per thread, two 16 B
 // stores. One f32 multiply and one round-to-nearest-even per weight.
 __global__ __launch_bounds__(256) void w8_dequant_kernel(
@@ -190,6 +248,27 @@ extern "C" void arks_w8_skinny_gemm(void* part, void* out, const void* a,
                            (const float*)scales, (const bf16*)bias, m_rows,
                            n_total, k_total, k_per_split, nsplits, a_stride);
       });
+}
+
+// nw = 64-row N sub-tiles per workgroup (1 or 2); slabs = ceil(max_rows/64).
+extern "C" void arks_w8_moe_gemm(void* out, const void* a, const void* w8,
+                                 const void* scales, const void* counts,
+                                 const void* pairs, int n_experts, int t_cols,
+                                 int n_pairs, int src_div, int slabs,
+                                 int n_total, int k_total, int nw,
+                                 hipStream_t stream) {
+  dim3 grid(n_total / (64 * nw), n_experts, slabs), block(256);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, (bf16*)out,
+                       (const bf16*)a, (const uint8_t*)w8,
+                       (const float*)scales, (const int*)counts,
+                       (const int*)pairs, t_cols, n_pairs, src_div, n_total,
+                       k_total);
+  };
+  if (nw == 2)
+    launch(w8_moe_gemm_kernel<2, 1>);
+  else
+    launch(w8_moe_gemm_kernel<1, 1>);
 }
 
 extern "C" void arks_w8_dequant(void* out, const void* w8, const void* scales,

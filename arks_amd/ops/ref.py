@@ -626,6 +626,30 @@ def w8_linear(x: torch.Tensor, w8: torch.Tensor, scales: torch.Tensor,
         x, w8_dequant(w8, scales).to(x.dtype), bias)
 
 
+def w8_moe_gemm(a: torch.Tensor, weight, counts: torch.Tensor,
+                pairs: torch.Tensor, src_div: int, out=None) -> torch.Tensor:
+    """out[p] = a[p // src_div] @ (float(w8[e]) * scales[e])^T for every
+    local expert e and p in pairs[e][:counts[e]]: a plain loop over experts
+    on w8_dequant (f32 accumulate, one rounding to a's dtype). weight is the
+    stacked pair (w8 e4m3fn [E, N, K], scales f32 [E, K/128, N]). Rows of
+    `out` that no local expert owns are left as they are (zeros when out is
+    None)."""
+    w8, scales = weight
+    E, N = w8.shape[0], w8.shape[1]
+    T = pairs.shape[1]
+    n_pairs = T * (a.shape[0] * src_div // T)
+    if out is None:
+        out = torch.zeros(n_pairs, N, dtype=a.dtype, device=a.device)
+    for e in range(E):
+        p = pairs[e, :int(counts[e])].long()
+        if p.numel() == 0:
+            continue
+        w = w8_dequant(w8[e], scales[e])
+        src = torch.div(p, src_div, rounding_mode="floor")
+        out[p] = (a[src].float() @ w.t()).to(out.dtype)
+    return out
+
+
 POOL_LAST, POOL_MEAN, POOL_CLS = 0, 1, 2
 
 
