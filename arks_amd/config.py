@@ -59,10 +59,13 @@ class ModelConfig:
     torch_dtype: str = "bfloat16"
     # "awq" when the checkpoint's quantization_config declares 4-bit AWQ,
     # "fp8_block" when it declares block-scaled FP8 (e4m3, 128x128 blocks,
-    # f32 scales, dynamic activations); None for plain checkpoints
+    # f32 scales, dynamic activations), "mxfp4" when it declares a Quark
+    # MXFP4 export (e2m1 weights, e8m0 scale per 32); None for plain
+    # checkpoints
     quant_method: str | None = None
     # fp8_block: module-name fragments the checkpoint left unquantized
-    # (modules_to_not_convert / ignored_layers)
+    # (modules_to_not_convert / ignored_layers); mxfp4: the export's
+    # `exclude` list (module names, fnmatch patterns allowed)
     quant_skip_modules: tuple = ()
 
     def __post_init__(self):
@@ -111,6 +114,8 @@ class ModelConfig:
             return None
         if str(qc.get("quant_method")).lower() == "fp8":
             return ModelConfig._check_fp8_config(qc)
+        if str(qc.get("quant_method")).lower() == "quark":
+            return ModelConfig._check_quark_config(qc)
         want = {"quant_method": "awq", "bits": 4, "group_size": 128,
                 "zero_point": True, "version": "gemm"}
         for field, ok in want.items():
@@ -157,8 +162,74 @@ class ModelConfig:
         return "fp8_block"
 
     @staticmethod
+    def _check_quark_config(qc: dict) -> str:
+        """Accepts exactly the MXFP4 weight-only reading of a Quark export
+        (the amd/*-MXFP4 checkpoints): global_quant_config.weight is static
+        fp4, per group of 32 with e8m0 scales, stored real_quantized; no
+        per-layer overrides, no quantized outputs, bias or KV cache; anything
+        else raises naming the offending field. input_tensors may be null or
+        a DYNAMIC spec, which is accepted and ignored: the activations stay
+        bf16 here, more precise than the checkpoint asks for. Static input
+        scales are refused (they would be tensors the engine never reads)."""
+        tail = ("the engine reads Quark MXFP4 with static fp4 weights, "
+                "per_group scales of group size 32 in e8m0, weights only")
+
+        def bad(field, got, ok):
+            return ValueError(
+                f"unsupported quantization_config: {field}={got!r} (only "
+                f"{field}={ok} is supported; {tail})")
+
+        glob = qc.get("global_quant_config")
+        if not isinstance(glob, dict):
+            raise bad("global_quant_config", glob, "{weight: ...}")
+        weight = glob.get("weight")
+        if not isinstance(weight, dict):
+            raise bad("global_quant_config.weight", weight, "an fp4 spec")
+        want = {"dtype": "fp4", "qscheme": "per_group", "group_size": 32,
+                "scale_format": "e8m0", "is_dynamic": False}
+        for field, ok in want.items():
+            got = weight.get(field)
+            if isinstance(got, str):
+                got = got.lower()
+            if got != ok or isinstance(got, bool) != isinstance(ok, bool):
+                raise bad(f"global_quant_config.weight.{field}",
+                          weight.get(field), repr(ok))
+        inp = glob.get("input_tensors")
+        if inp is not None:
+            if not isinstance(inp, dict) or inp.get("is_dynamic") is not True:
+                raise bad("global_quant_config.input_tensors", inp,
+                          "null or a dynamic spec (is_dynamic=true)")
+        for field in ("output_tensors", "bias"):
+            if glob.get(field) is not None:
+                raise bad(f"global_quant_config.{field}", glob.get(field),
+                          "null")
+        for field in ("layer_quant_config", "layer_type_quant_config"):
+            if qc.get(field):
+                raise bad(field, qc.get(field), "{}")
+        export = qc.get("export") or {}
+        if not isinstance(export, dict):
+            raise bad("export", export, "{...}")
+        if export.get("kv_cache_group"):
+            raise bad("export.kv_cache_group", export.get("kv_cache_group"),
+                      "[]")
+        wf = export.get("weight_format", "real_quantized")
+        if str(wf).lower() != "real_quantized":
+            raise bad("export.weight_format", wf, "'real_quantized'")
+        return "mxfp4"
+
+    @staticmethod
     def _fp8_skip_modules(qc: dict | None) -> tuple:
-        """modules_to_not_convert and its alias ignored_layers, merged."""
+        """modules_to_not_convert and its alias ignored_layers, merged; for
+        a Quark MXFP4 checkpoint its `exclude` list (module names, fnmatch
+        patterns allowed)."""
+        if qc and str(qc.get("quant_method")).lower() == "quark":
+            val = qc.get("exclude") or []
+            if isinstance(val, str) or not all(isinstance(v, str)
+                                               for v in val):
+                raise ValueError(
+                    f"unsupported quantization_config: exclude={val!r} "
+                    "(expected a list of module names)")
+            return tuple(dict.fromkeys(val))
         if not qc or str(qc.get("quant_method")).lower() != "fp8":
             return ()
         out: list[str] = []
@@ -590,6 +661,11 @@ class EngineConfig:
     # bf16; MoE experts stay bf16 unless quantize_experts is set)
     # "awq": a 4-bit AWQ checkpoint, dense or MoE (auto-detected from its
     # config.json; giving it for any other checkpoint is an error)
+    # "mxfp4": OCP MXFP4 weights (e2m1, one e8m0 scale per 32 along K), W4A16
+    # for the dense qkv/o/gate_up/down GEMMs: a Quark MXFP4 checkpoint
+    # (auto-detected, excludes every other mode) or, on a bf16 checkpoint,
+    # the OCP conversion at load (the counterpart of "int4"; MoE experts
+    # stay bf16)
     quantization: str | None = None
     # with quantization="int4" on an MoE model: also quantize the routed
     # experts and the shared expert at load (routed grouped W4 GEMM)
@@ -630,10 +706,10 @@ class EngineConfig:
     embedding_normalize: str = "auto"
 
     def __post_init__(self):
-        if self.quantization not in (None, "fp8", "int4", "awq"):
+        if self.quantization not in (None, "fp8", "int4", "awq", "mxfp4"):
             raise ValueError(
                 f"unknown quantization {self.quantization!r}: expected "
-                "None, 'fp8', 'int4' or 'awq'"
+                "None, 'fp8', 'int4' or 'awq', or 'mxfp4'"
             )
         if self.quantize_experts and self.quantization != "int4":
             raise ValueError(
@@ -677,7 +753,9 @@ class EngineConfig:
         own and excludes every other mode; "awq" needs such a checkpoint. A
         block-scaled FP8 checkpoint selects "fp8_block" on its own; "fp8"
         on it is accepted and means the same, on any other checkpoint it is
-        the W8A8 path."""
+        the W8A8 path. An MXFP4 checkpoint selects "mxfp4" on its own and
+        excludes every other mode; on a bf16 checkpoint "mxfp4" quantizes
+        the dense layers at load."""
         if self.quantize_experts and model_cfg.num_local_experts == 0:
             raise ValueError(
                 "quantize_experts needs an MoE model, "
@@ -693,6 +771,14 @@ class EngineConfig:
                     "already e4m3 (leave quantization unset or give 'fp8')"
                 )
             return "fp8_block"
+        if model_cfg.quant_method == "mxfp4":
+            if self.quantization not in (None, "mxfp4"):
+                raise ValueError(
+                    f"quantization={self.quantization!r} cannot be applied "
+                    "to an MXFP4 checkpoint: its weights are already 4-bit "
+                    "(leave quantization unset or give 'mxfp4')"
+                )
+            return "mxfp4"
         if model_cfg.quant_method == "awq":
             if self.quantization not in (None, "awq"):
                 raise ValueError(

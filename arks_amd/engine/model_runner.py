@@ -107,6 +107,13 @@ class ModelRunner:
             # likewise for a block-scaled FP8 checkpoint: the e4m3 bytes
             # stream straight into the layers' W8 buffers
             self.model.prepare_fp8_checkpoint()
+        # "mxfp4" is either the checkpoint's own format (its nibbles and
+        # scale bytes stream straight into the layers' MX4 buffers) or, on a
+        # bf16 checkpoint, the load-time quantization that int4 is for W4
+        mx4_ckpt = (self.quantization == "mxfp4"
+                    and self.model_cfg.quant_method == "mxfp4")
+        if mx4_ckpt:
+            self.model.prepare_mxfp4_checkpoint()
         if self.cfg.model_path:
             from ..loader.safetensors_loader import load_model_weights
 
@@ -131,6 +138,12 @@ class ModelRunner:
             self.model.finalize_w4()
         elif self.quantization == "fp8_block":
             self.model.finalize_w8()
+        elif mx4_ckpt:
+            self.model.finalize_mx4()
+        elif self.quantization == "mxfp4":
+            self.model.quantize_mx4()
+            if self.device.type == "cuda":
+                torch.cuda.empty_cache()  # as for int4
         elif self.quantization is not None:
             raise ValueError(f"unknown quantization {self.quantization!r}")
         # serving past max_position_embeddings: the rope table must cover

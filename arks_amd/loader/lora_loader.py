@@ -53,6 +53,8 @@ def _local_shape(mod) -> tuple[int, int]:
     """(N, K) of a linear layer's local weight, W4/W8-quantized or not."""
     if getattr(mod, "w8", False):
         return mod.w8_shape
+    if getattr(mod, "mx4", False):
+        return mod.mx4_shape
     return mod.w4_shape if getattr(mod, "w4", False) else tuple(mod.weight.shape)
 
 

@@ -348,6 +348,73 @@ def save_fp8_checkpoint(cfg, out_dir: str, seed: int = 0,
         _write_checkpoint(cfg, dequantized_dir, plain)
 
 
+_MX4_CONFIG = {
+    "quant_method": "quark",
+    "global_quant_config": {
+        "weight": {"dtype": "fp4", "qscheme": "per_group", "group_size": 32,
+                   "scale_format": "e8m0", "is_dynamic": False,
+                   "ch_axis": -1},
+        "input_tensors": None, "output_tensors": None, "bias": None,
+    },
+    "layer_quant_config": {}, "layer_type_quant_config": {},
+    "export": {"kv_cache_group": [], "weight_format": "real_quantized"},
+}
+
+
+def save_mx4_checkpoint(cfg, out_dir: str, seed: int = 0,
+                        dequantized_dir: str | None = None,
+                        skip: tuple = ()) -> None:
+    """Write a random-init checkpoint in the MXFP4 layout of a Quark export:
+    every q/k/v/o/gate/up/down projection (of a dense MLP, of each routed MoE
+    expert under its Qwen-MoE or Mixtral w1/w3/w2 name, and of the shared
+    expert) is quantized by the OCP MX rule (ops.ref.mx4_quantize) and stored
+    as .weight u8 [N, K/2] (two e2m1 nibbles per byte, low nibble first)
+    plus .weight_scale u8 [N, K/32] (e8m0); everything else is bf16.
+    config.json carries the quark quantization_config.
+    skip: module names or fnmatch patterns (e.g. "*.down_proj") left in bf16
+    and listed under `exclude` together with lm_head.
+    dequantized_dir: also write a plain bf16 checkpoint holding the
+    dequantized weights, which bf16 holds exactly (the model an MXFP4 engine
+    must reproduce)."""
+    import copy
+    import fnmatch
+
+    from ..ops import ref
+
+    projs = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj",
+             "down_proj", "w1", "w2", "w3")
+
+    def skipped(stem: str) -> bool:
+        comps = stem.split(".")
+        for entry in skip:
+            e = entry.split(".")
+            if fnmatch.fnmatchcase(stem, entry) or any(
+                    comps[i:i + len(e)] == e
+                    for i in range(len(comps) - len(e) + 1)):
+                return True
+        return False
+
+    mx4: dict[str, torch.Tensor] = {}
+    plain: dict[str, torch.Tensor] = {}
+    for name, t in _random_hf_tensors(cfg, seed).items():
+        stem, _, param = name.rpartition(".")
+        if (param == "weight" and stem.rsplit(".", 1)[-1] in projs
+                and not skipped(stem)):
+            packed, scales = ref.mx4_quantize(t)
+            mx4[name] = packed
+            mx4[f"{stem}.weight_scale"] = scales
+            plain[name] = ref.mx4_dequant(packed, scales).to(torch.bfloat16)
+        else:
+            mx4[name] = t.to(torch.bfloat16)
+            plain[name] = t.to(torch.bfloat16)
+    qc = copy.deepcopy(_MX4_CONFIG)
+    qc["exclude"] = ["lm_head", *skip]
+    _write_checkpoint(cfg, out_dir, mx4,
+                      extra_config={"quantization_config": qc})
+    if dequantized_dir is not None:
+        _write_checkpoint(cfg, dequantized_dir, plain)
+
+
 def _random_hf_tensors(cfg, seed: int) -> dict[str, torch.Tensor]:
     """HF-layout tensors of a random-init model (fused weights split back
     apart)."""

@@ -1234,6 +1234,218 @@ class LlamaFamilyForCausalLM(nn.Module):
         pre = "" if stem == "lm_head" else "model."
         self.load_hf_state_dict({f"{pre}{stem}.weight": plain})
 
+    # ---- MXFP4 checkpoints (MX4, W4A16; format in ops/ref.py) ----
+    # X.weight u8 [N, K/2] + X.weight_scale u8 [N, K/32] per quantized
+    # projection, as a Quark MXFP4 export stores them. The candidate layers
+    # are _w4_targets(experts=True); routed experts (no grouped MX4 kernel)
+    # and a quantized lm_head are dequantized to bf16 at load.
+    _MX4_KINDS = ("weight", "weight_scale")
+
+    def _mx4_skipped(self, hf_name: str) -> bool:
+        """The export's `exclude` list: an entry names a module by its full
+        name, by an fnmatch pattern over it, or (as for FP8 checkpoints) by
+        dotted components that occur in a row in it."""
+        import fnmatch
+
+        return (self._w8_skipped(hf_name)
+                or any(fnmatch.fnmatchcase(hf_name, e)
+                       or fnmatch.fnmatchcase(hf_name.removeprefix("model."),
+                                              e)
+                       for e in self.cfg.quant_skip_modules))
+
+    def quantize_mx4(self) -> None:
+        """MX4 of a loaded bf16 model in memory by the OCP conversion rule
+        (quantize_module_mx4 over the dense qkv/o/gate_up/down projections;
+        lm_head, embeddings, router gates and every MoE expert stay bf16):
+        --quantization mxfp4 on a bf16 checkpoint."""
+        from ..parallel.layers import quantize_module_mx4
+
+        for name, mod in self._w4_targets():
+            quantize_module_mx4(mod, name)
+
+    def prepare_mxfp4_checkpoint(self) -> None:
+        """Switch the quantized layers to (empty) MX4 storage BEFORE an MXFP4
+        checkpoint streams in, so their bf16 weights are never allocated on
+        the device; finalize_mx4() completes the switch after loading. The
+        parts of a fused projection must all be quantized or all be on the
+        checkpoint's exclude list."""
+        from ..parallel.layers import init_module_mx4
+
+        self._mx4_pending = {}
+        self._mx4_experts_logged = False
+        for name, mod in self._w4_targets(experts=True):
+            parts = self._w8_hf_parts(name)
+            skipped = [self._mx4_skipped(p) for p in parts]
+            if all(skipped):
+                continue
+            if any(skipped):
+                raise ValueError(
+                    f"{name}: the checkpoint quantizes only some parts of "
+                    "this fused projection "
+                    f"({dict(zip(parts, skipped))}: True = excluded, left "
+                    "in bf16); they must all be MXFP4 or all excluded")
+            init_module_mx4(mod, name)
+            mod._mx4_got = set()
+
+    def finalize_mx4(self) -> None:
+        from ..parallel.layers import finalize_module_mx4
+
+        for key, held in getattr(self, "_mx4_pending", {}).items():
+            for stem, kinds in held.items():
+                if key[0] != "dequant":
+                    raise ValueError(
+                        f"{stem}.{key[1]}: the fused partners of this MXFP4 "
+                        f"tensor ({key[0]}) are missing from the checkpoint")
+                if "weight" not in kinds:
+                    raise ValueError(
+                        f"{stem}.weight_scale: a scale without its weight "
+                        "in the checkpoint")
+                raise ValueError(
+                    f"{stem}.weight: an MXFP4 weight without its "
+                    "weight_scale in the checkpoint")
+        for name, mod in self._w4_targets(experts=True):
+            if not getattr(mod, "mx4", False):
+                continue
+            missing = set(self._MX4_KINDS) - mod._mx4_got
+            if missing:
+                raise ValueError(
+                    f"{name}: the checkpoint has no {sorted(missing)} for "
+                    "this MXFP4 layer")
+            finalize_module_mx4(mod)
+
+    def _route_mx4(self, full_name: str, w: torch.Tensor) -> bool:
+        """Takes the tensors of an MXFP4 checkpoint (uint8 weights and their
+        weight_scale) out of load_hf_state_dict's stream; True when the
+        tensor was consumed here."""
+        from ..ops import ref
+
+        name = full_name.removeprefix("model.")
+        stem, _, kind = name.rpartition(".")
+        is_mx4 = w.dtype == torch.uint8 and kind == "weight"
+        if not is_mx4 and kind != "weight_scale":
+            if kind == "weight":
+                tgt = self._w8_target(stem)
+                if (tgt is not None and tgt[0] is not None
+                        and getattr(tgt[0], "mx4", False)):
+                    raise ValueError(
+                        f"{full_name}: plain {w.dtype} weight, but "
+                        f"{tgt[1]} was prepared for MXFP4 (the checkpoint's "
+                        "quantization_config does not list it under "
+                        "exclude)")
+            return False
+        tgt = self._w8_target(stem)
+        if tgt is None:
+            raise ValueError(
+                f"{full_name}: MXFP4 tensor for a module that is never "
+                "quantized (embeddings, norms and router gates are read "
+                "in bf16)")
+        mod, modname, group, how = tgt
+        if how == "skip":
+            return True
+        if not hasattr(self, "_mx4_pending"):
+            raise ValueError(
+                f"{full_name}: MXFP4 tensor in the checkpoint but the model "
+                "was not prepared for MXFP4 (config.json lacks "
+                "quantization_config?)")
+        if w.dtype != torch.uint8 or w.dim() != 2:
+            raise ValueError(
+                f"{full_name}: expected a 2-D uint8 tensor, got "
+                f"{tuple(w.shape)} {w.dtype}")
+        if kind == "weight_scale":
+            # on the host, before anything is uploaded: outside this range a
+            # scaled e2m1 value is not a normal finite bf16 (255 is NaN)
+            lo, hi = int(w.min()), int(w.max())
+            if lo < ref.MX4_SCALE_MIN or hi > ref.MX4_SCALE_MAX:
+                raise ValueError(
+                    f"{full_name}: e8m0 scale bytes span [{lo}, {hi}], "
+                    f"outside the supported [{ref.MX4_SCALE_MIN}, "
+                    f"{ref.MX4_SCALE_MAX}] (0.5 * 2^(s-127) must be a normal "
+                    "bf16 and 6 * 2^(s-127) finite; 255 is NaN)")
+        if how in ("dequant", "expert"):
+            self._mx4_dequant_load(full_name, stem, kind, w)
+            return True
+        if not getattr(mod, "mx4", False):
+            raise ValueError(
+                f"{full_name}: MXFP4 tensor in the checkpoint but {modname} "
+                "was not prepared for MXFP4 (it is on the checkpoint's "
+                "exclude list)")
+        if group is None:
+            self._load_mx4(mod, modname, kind, [w], how)
+            return True
+        held = self._mx4_pending.setdefault((modname, kind), {})
+        held[stem] = {kind: w}
+        if all(g in held for g in group):
+            fulls = [held[g][kind] for g in group]
+            del self._mx4_pending[(modname, kind)]
+            self._load_mx4(mod, modname, kind, fulls, how)
+        return True
+
+    def _load_mx4(self, mod, name: str, kind: str, fulls, how: str) -> None:
+        """One tensor kind (weight / weight_scale) of a projection, or of
+        the fused partners `fulls`, into the module's MX4 buffers, sharded on
+        the host slice. Both kinds have one row per output channel, so a
+        column-parallel shard slices rows of both and fused parts concatenate
+        along N; a row-parallel shard slices K as K/2 bytes of nibbles and
+        K/32 scale bytes. The two kinds are independent, so they may arrive
+        in different chunks."""
+        from ..ops import ref
+
+        div = 2 if kind == "weight" else ref.MX4_BLOCK
+        r = get_tp_rank()
+        N, K = mod.mx4_shape
+        if how == "row":
+            per = mod.in_per_rank // div
+            parts = [fulls[0][:, r * per:(r + 1) * per]]
+        elif len(fulls) == 3:
+            parts = mod.shard_qkv_parts(*fulls)
+        elif len(fulls) == 2:
+            parts = mod.shard_merged_parts(*fulls)
+        else:
+            parts = [mod.shard(fulls[0])]
+        dst = mod.mx4_weight if kind == "weight" else mod.mx4_scales
+        off = 0
+        for part in parts:
+            n = part.shape[0]
+            if part.shape[1] != K // div or off + n > N:
+                raise ValueError(
+                    f"{name}: MXFP4 {kind} part {tuple(part.shape)} does "
+                    f"not fit the layer's {N}x{K} ([N, K/{div}] bytes)")
+            dst[off:off + n].copy_(part)
+            off += n
+        if off != N:
+            raise ValueError(f"{name}: MXFP4 {kind} covers {off} of {N} rows")
+        mod._mx4_got.add(kind)
+
+    def _mx4_dequant_load(self, full_name: str, stem: str, kind: str,
+                          w: torch.Tensor) -> None:
+        """A routed expert or lm_head that arrives in MXFP4: hold the tensor
+        until its partner is here, then dequantize to bf16 (exact) on the
+        model's device and load it as the plain weight it replaces. One
+        projection at a time, so the transient memory is one expert's."""
+        import logging
+
+        from ..ops import ref
+
+        held = self._mx4_pending.setdefault(("dequant", stem), {})
+        pair = held.setdefault(stem, {})
+        # the partner may come with a later chunk, after the staging buffer
+        # this view points into has been recycled
+        pair[kind] = w.clone()
+        if len(pair) < 2:
+            return
+        del self._mx4_pending[("dequant", stem)]
+        if stem != "lm_head" and not self._mx4_experts_logged:
+            self._mx4_experts_logged = True
+            logging.getLogger(__name__).warning(
+                "MXFP4 routed experts are dequantized to bf16 at load (no "
+                "grouped MX4 kernel): the model holds its experts at bf16 "
+                "size")
+        dev = self.embed_tokens.weight.device
+        plain = ref.mx4_dequant(pair["weight"].to(dev),
+                                pair["weight_scale"].to(dev)).to(self.dtype)
+        pre = "" if stem == "lm_head" else "model."
+        self.load_hf_state_dict({f"{pre}{stem}.weight": plain})
+
     def _load_awq(self, mod, name: str, kind: str, fulls, shard_parts) -> None:
         """One AWQ tensor kind (qweight / qzeros / scales) of a projection,
         or of the fused partners `fulls`: unpack on the host to row form
@@ -1352,7 +1564,7 @@ class LlamaFamilyForCausalLM(nn.Module):
             assert off == p.shape[0], (name, off, p.shape)
 
         for name, w in tensors.items():
-            if self._route_w8(name, w):
+            if self._route_w8(name, w) or self._route_mx4(name, w):
                 continue
             name = name.removeprefix("model.")
             if name == "embed_tokens.weight":

@@ -611,7 +611,10 @@ def linear_bf16(x, weight, bias=None, defer: bool = False):
 # Quantized weights, group / block size 128 along K (formats in ops/ref.py):
 #   W4A16  4-bit AWQ-style, packed (qweight, scales, zeros)
 #   W8A16  block-scaled e4m3fn, (w8_weight [N, K], w8_scales f32 [K/128, N])
-# Both run the streaming chunk loop of csrc/wq_stream.h, so one path serves
+#   MX4    OCP MXFP4 (W4A16): e2m1 nibbles with one e8m0 scale per 32 k,
+#          (mx4_weight u8 [N, K/2], mx4_scales u8 [N, K/32]); a 128-wide
+#          chunk holds four of its blocks, one per lane group
+# All run the streaming chunk loop of csrc/wq_stream.h, so one path serves
 # them, driven by a format descriptor.
 # ---------------------------------------------------------------------------
 # Rows one launch of the shared skinny kernel takes (MT <= 4 tiles of 16).
@@ -623,6 +626,9 @@ W4_SKINNY_MAX_M = W8_SKINNY_MAX_M = _WQ_SKINNY_MAX_M = 64
 # profiles/w8_gemm.md).
 W4_SLAB_MAX_M = 128
 W8_SLAB_MAX_M = 128
+# MX4 starts from the W8 value: it moves only on a measurement recorded in
+# profiles/mx4_gemm.md.
+MX4_SLAB_MAX_M = W8_SLAB_MAX_M
 # bf16 [N*K] scratch per device for the path above the slab limit
 # (dequantize, then the library GEMM): a model is W4 or W8, never both at
 # once, and either way the scratch is one bf16 [N*K] of its largest layer.
@@ -663,6 +669,10 @@ _W8 = _WqFormat(
     "w8", lambda w: tuple(w[0].shape),
     lambda x, w, bias: ref.w8_linear(x, *w, bias),
     lambda w: ref.w8_dequant(*w), W8_SLAB_MAX_M)
+_MX4 = _WqFormat(
+    "mx4", lambda w: (w[0].shape[0], w[0].shape[1] * 2),
+    lambda x, w, bias: ref.mx4_linear(x, *w, bias),
+    lambda w: ref.mx4_dequant(*w), MX4_SLAB_MAX_M)
 
 
 def _wq_plan(M: int, N: int, K: int):
@@ -705,7 +715,7 @@ def _wq_plan(M: int, N: int, K: int):
     return nw, nsplits, k_per_split, 16 * min(-(-M // 16), 4)
 
 
-_w4_plan = _w8_plan = _wq_plan
+_w4_plan = _w8_plan = _mx4_plan = _wq_plan
 
 
 def _wq_dequant(fmt: _WqFormat, weight, out=None):
@@ -728,6 +738,13 @@ def w8_dequant(weight, out=None):
     """bf16 [N, K] from a W8 weight (w8_weight, w8_scales), via
     w8_dequant_kernel on GPU."""
     return _wq_dequant(_W8, weight, out)
+
+
+def mx4_dequant(weight, out=None):
+    """bf16 [N, K] from an MX4 weight (mx4_weight, mx4_scales), via
+    mx4_dequant_kernel on GPU. Exact: every e2m1 value times a power of two
+    is a bf16 for the scale bytes a layer accepts."""
+    return _wq_dequant(_MX4, weight, out)
 
 
 def _wq_skinny(fmt: _WqFormat, x, weight, bias, defer: bool, plan, out=None):
@@ -841,6 +858,35 @@ def w8_linear(x, weight, bias=None, defer: bool = False, plan=None):
     faster than either route on qkv/o/gate_up (23 / 23 / 70 us at 128); down
     stays faster in W8 up to 128 rows."""
     return _wq_linear(_W8, x, weight, bias, defer, plan)
+
+
+def mx4_linear(x, weight, bias=None, defer: bool = False, plan=None):
+    """y = x @ dequant(weight)^T + bias for an MX4 weight (mx4_weight u8
+    [N, K/2] of e2m1 nibble pairs, mx4_scales u8 [N, K/32] e8m0; the
+    tensors of an MXFP4 checkpoint). On GPU: the MX4 streaming kernel for
+    M <= 64 (defer=True returns a SplitKPending when it splits K, as
+    skinny_gemm does); M up to MX4_SLAB_MAX_M runs that kernel per 64-row
+    slab; above it the weight is expanded to bf16 in the preallocated
+    workspace and the library GEMM runs on it. No eager fallback: a shape the
+    kernels cannot take (N % 64, K % 128) raises. On CPU: the reference
+    emulation.
+    plan overrides _mx4_plan for M <= 64 (tests force a split count with it).
+
+    _mx4_plan is _wq_plan: the kernel shares the W4 and W8 kernels' staging,
+    grid and partial layout, so it takes their rule; the plan was not swept
+    again for MX4. MEASURED as a whole on an MI355X with scripts/bench_mx4.py
+    (in-graph us, weights cycled past the LLC; profiles/mx4_gemm.md): with
+    this plan every M <= 64 row of the Qwen2.5-7B shapes beats bf16 (qkv
+    8.9-15.3 vs 11.2-16.8, o 8.6-13.7 vs 10.6-15.1, gate_up 28.8-47.8 vs
+    55.8-63.0, down 21.0-27.9 vs 34.3-111); against w4_linear in the same
+    session it is within 4% on qkv / o, 4-9% faster at M = 64, and 10-23%
+    SLOWER on gate_up / down at M <= 32 (cause not established).
+    M > 64: slabs vs dequant+library at M=128: qkv 29.8 vs 37.9, o 26.7 vs
+    36.6, gate_up 85.2 vs 165.5, down 52.1 vs 118.9 — slabs win everywhere;
+    M=256: qkv 59.0 vs 49.1, o 53.1 vs 33.7 — the library wins; gate_up 160.6
+    vs 172.5, down 101.1 vs 148.4 — slabs win. MX4_SLAB_MAX_M stays at the W8
+    value, the last measured size where slabs win on every shape."""
+    return _wq_linear(_MX4, x, weight, bias, defer, plan)
 
 
 def w4_moe_gemm(a, packed, counts, pairs, src_div: int, max_rows: int,

@@ -164,6 +164,13 @@ void arks_w8_moe_gemm(void* out, const void* a, const void* w8,
                       const void* pairs, int n_experts, int t_cols,
                       int n_pairs, int src_div, int slabs, int n_total,
                       int k_total, int nw, hipStream_t stream);
+void arks_mx4_skinny_gemm(void* part, void* out, const void* a, const void* w,
+                          const void* scales, const void* bias, int m_rows,
+                          int n_total, int k_total, int k_per_split,
+                          int nsplits, int64_t a_stride, int nw, bool combine,
+                          hipStream_t stream);
+void arks_mx4_dequant(void* out, const void* w, const void* scales,
+                      int n_total, int k_total, hipStream_t stream);
 void arks_moe_route(void* counts, void* pairs, const void* ids, int n_pairs,
                     int T, int expert_base, int n_local, hipStream_t stream);
 void arks_mfma_probe(void* d, const void* a, const void* b, hipStream_t stream);
@@ -716,6 +723,69 @@ void w8_dequant(torch::Tensor out, torch::Tensor w8, torch::Tensor scales) {
   TORCH_CHECK(n * (k / 16) < (int64_t)1 << 39);
   arks_w8_dequant(out.data_ptr(), w8.data_ptr(), scales.data_ptr(), (int)n,
                   (int)k, current_stream());
+}
+
+// MX4 weight (mx4_gemm.hip): the checkpoint's tensors, u8 [N, K/2] with two
+// e2m1 nibbles per byte and u8 [N, K/32] e8m0 scales. Returns (n, k).
+std::pair<int64_t, int64_t> check_mx4_weight(const torch::Tensor& w,
+                                             const torch::Tensor& scales) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kUInt8 &&
+              w.dim() == 2 && w.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "mx4 weight must be contiguous uint8 [N, K/2] on GPU");
+  const int64_t n = w.size(0), k = w.size(1) * 2;
+  TORCH_CHECK(k >= 128 && k % 128 == 0, "MX4 needs K % 128 == 0, got K=", k);
+  TORCH_CHECK(n % 64 == 0, "MX4 needs N % 64 == 0, got N=", n);
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kUInt8 &&
+              scales.is_contiguous() && scales.dim() == 2 &&
+              scales.size(0) == n && scales.size(1) == k / 32 &&
+              reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0,
+              "scales must be contiguous uint8 [N, K/32] on GPU");
+  TORCH_CHECK(scales.device() == w.device());
+  return {n, k};
+}
+
+void mx4_skinny_gemm_impl(torch::Tensor out, torch::Tensor part,
+                          torch::Tensor a, torch::Tensor w,
+                          torch::Tensor scales,
+                          c10::optional<torch::Tensor> bias,
+                          int64_t k_per_split, int64_t nsplits, int64_t nw,
+                          bool combine) {
+  const auto [n, k] = check_mx4_weight(w, scales);
+  const auto p = check_wq_skinny(out, part, a, bias, n, k, w.device(),
+                                 k_per_split, nsplits, nw, combine);
+  arks_mx4_skinny_gemm(p.part, p.out, a.data_ptr(), w.data_ptr(),
+                       scales.data_ptr(), p.bias, (int)a.size(0), (int)n,
+                       (int)k, (int)k_per_split, (int)nsplits, a.stride(0),
+                       (int)nw, combine, current_stream());
+}
+
+void mx4_skinny_gemm(torch::Tensor out, torch::Tensor part, torch::Tensor a,
+                     torch::Tensor w, torch::Tensor scales,
+                     c10::optional<torch::Tensor> bias, int64_t k_per_split,
+                     int64_t nsplits, int64_t nw) {
+  mx4_skinny_gemm_impl(out, part, a, w, scales, bias, k_per_split, nsplits,
+                       nw, true);
+}
+
+void mx4_skinny_gemm_partials(torch::Tensor part, torch::Tensor a,
+                              torch::Tensor w, torch::Tensor scales,
+                              int64_t k_per_split, int64_t nsplits,
+                              int64_t nw) {
+  mx4_skinny_gemm_impl(torch::Tensor(), part, a, w, scales, c10::nullopt,
+                       k_per_split, nsplits, nw, false);
+}
+
+// out bf16 [>= N*K elements] receives the dequantized [N, K] weight.
+void mx4_dequant(torch::Tensor out, torch::Tensor w, torch::Tensor scales) {
+  const auto [n, k] = check_mx4_weight(w, scales);
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(out.numel() >= n * k && out.device() == w.device() &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "mx4_dequant output too small");
+  TORCH_CHECK(n * (k / 32) < (int64_t)1 << 39);
+  arks_mx4_dequant(out.data_ptr(), w.data_ptr(), scales.data_ptr(), (int)n,
+                   (int)k, current_stream());
 }
 
 // Routed grouped GEMM over stacked experts (w4_moe_gemm_kernel):
@@ -1392,6 +1462,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w8_skinny_gemm_partials", &w8_skinny_gemm_partials);
   m.def("w8_dequant", &w8_dequant);
   m.def("w8_moe_gemm", &w8_moe_gemm);
+  m.def("mx4_skinny_gemm", &mx4_skinny_gemm);
+  m.def("mx4_skinny_gemm_partials", &mx4_skinny_gemm_partials);
+  m.def("mx4_dequant", &mx4_dequant);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache, py::arg("positions"),
         py::arg("part"), py::arg("bias"), py::arg("q_out"), py::arg("k_cache"),

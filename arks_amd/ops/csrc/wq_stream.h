@@ -1,10 +1,12 @@
 // The streaming chunk loop of the quantized skinny GEMMs (M <= 64 rows per
 // launch or per routed slab): C[M,N] = A[M,K] @ dequant(W)[N,K]^T for weights
 // quantized in groups of 128 along K. One body, wq_stream, parametrised by
-//   a weight format  (w4_gemm.hip W4Weights, w8_gemm.hip W8Weights): what a
-//       lane's chunk of W is, how it is loaded, how eight weights become a
-//       bf16 fragment, and how a chunk's f32 fragment is scaled into the
-//       accumulator (with or without the sums of the activations);
+//   a weight format  (w4_gemm.hip W4Weights, w8_gemm.hip W8Weights,
+//       mx4_gemm.hip Mx4Weights, whose groups of 32 are one lane's share of
+//       a chunk): what a lane's chunk of W is, how it is loaded, how eight
+//       weights become a bf16 fragment, and how a chunk's f32 fragment is
+//       scaled into the accumulator (with or without the sums of the
+//       activations);
 //   a row source     (WqDenseRows, WqRoutedRows below): where the A rows come
 //       from, which K-range is summed and where the result rows go.
 // MT (live 16-row M tiles), NW (64-row N sub-tiles per workgroup, 1 or 2) and

@@ -650,6 +650,81 @@ def w8_moe_gemm(a: torch.Tensor, weight, counts: torch.Tensor,
     return out
 
 
+# ---------------------------------------------------------------------------
+# MX4 (W4A16): OCP microscaling FP4 (MXFP4). e2m1 elements, one shared e8m0
+# scale per block of 32 along K:
+#   w[n, k] = e2m1(code[n, k]) * 2^(scales[n, k // 32] - 127)
+# On disk and in a layer alike: weight u8 [N, K/2], byte b of a row holding
+# k = 2b in its low nibble and k = 2b+1 in its high nibble, and scales u8
+# [N, K/32]. A code is a sign (bit 3) and an index into MX4_VALUES.
+# ---------------------------------------------------------------------------
+MX4_BLOCK = 32
+MX4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# Scale bytes a layer accepts: 0.5 * 2^(s-127) must be a normal bf16 and
+# 6 * 2^(s-127) finite, so that scaling before the MFMA is exact. 255 is NaN.
+MX4_SCALE_MIN, MX4_SCALE_MAX = 2, 252
+
+
+def mx4_quantize(w: torch.Tensor):
+    """The OCP MX conversion rule: per block of 32 along K the shared
+    exponent is floor(log2(amax)) - 2 (2 = the exponent of e2m1's largest
+    value), the elements are divided by it, rounded to the nearest e2m1 value
+    (ties to the even code) and saturated at +-6. Returns (packed u8
+    [N, K/2], scales u8 [N, K/32]). An all-zero block gets scale byte 127;
+    the byte is kept inside [MX4_SCALE_MIN, MX4_SCALE_MAX], the range a
+    layer accepts (elements of a block below it round towards zero, above it
+    they saturate)."""
+    N, K = w.shape
+    if K % MX4_BLOCK != 0:
+        raise ValueError(f"mx4_quantize needs K % {MX4_BLOCK} == 0, got K={K}")
+    blocks = w.float().view(N, K // MX4_BLOCK, MX4_BLOCK)
+    amax = blocks.abs().amax(dim=2)
+    # amax = m * 2^ex with m in [0.5, 1): floor(log2(amax)) = ex - 1, exactly
+    _, ex = torch.frexp(amax)
+    s = torch.where(amax > 0, ex.to(torch.int32) - 3 + 127,
+                    torch.full_like(ex, 127, dtype=torch.int32))
+    s = s.clamp(MX4_SCALE_MIN, MX4_SCALE_MAX)
+    q = torch.ldexp(blocks, (127 - s)[:, :, None])
+    a = q.abs().clamp(max=6.0)
+    step = torch.where(a < 2.0, 0.5, torch.where(a < 4.0, 1.0, 2.0))
+    v = torch.round(a / step) * step  # half to even = ties to the even code
+    table = torch.tensor(MX4_VALUES, dtype=torch.float32, device=w.device)
+    code = torch.searchsorted(table, v.contiguous()).to(torch.uint8)
+    code = code | (((q < 0) & (v > 0)).to(torch.uint8) << 3)
+    code = code.view(N, K)
+    packed = code[:, 0::2] | (code[:, 1::2] << 4)
+    return packed.contiguous(), s.to(torch.uint8)
+
+
+def mx4_dequant(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """f32 [N, K] = e2m1(code) * 2^(scales[n, k // 32] - 127), exactly (a
+    scale byte of 255 is NaN)."""
+    N, K = packed.shape[0], packed.shape[1] * 2
+    if (packed.dtype != torch.uint8 or scales.dtype != torch.uint8
+            or K % MX4_BLOCK != 0
+            or tuple(scales.shape) != (N, K // MX4_BLOCK)):
+        raise ValueError(
+            f"mx4 weight {tuple(packed.shape)} {packed.dtype} / scales "
+            f"{tuple(scales.shape)} {scales.dtype}: expected uint8 [N, K/2] "
+            f"and uint8 [N, K/{MX4_BLOCK}]")
+    mags = torch.tensor(MX4_VALUES, dtype=torch.float32, device=packed.device)
+    lut = torch.cat([mags, -mags])
+    code = torch.stack([packed & 0xF, packed >> 4], dim=2).view(N, K)
+    vals = lut[code.long()]
+    s = scales.to(torch.int32)
+    p2 = torch.ldexp(torch.ones_like(s, dtype=torch.float32), s - 127)
+    p2 = torch.where(s == 255, torch.full_like(p2, float("nan")), p2)
+    return vals * p2.repeat_interleave(MX4_BLOCK, dim=1)
+
+
+def mx4_linear(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor,
+               bias=None) -> torch.Tensor:
+    """The CPU emulation of an MX4 layer: a GEMM on the dequantized weight
+    rounded to the activation dtype (exact for bf16 and wider)."""
+    return torch.nn.functional.linear(
+        x, mx4_dequant(packed, scales).to(x.dtype), bias)
+
+
 POOL_LAST, POOL_MEAN, POOL_CLS = 0, 1, 2
 
 

@@ -244,6 +244,91 @@ def _w8_linear(mod: nn.Module, x, bias, defer: bool):
     return ops.w8_linear(x, (mod.w8_weight, mod.w8_scales), bias, defer=defer)
 
 
+def _mx4_check_shape(mod: nn.Module, name: str) -> tuple[int, int]:
+    N, K = mod.weight.shape
+    if K % 128 != 0:
+        raise ValueError(
+            f"{name}: mxfp4 needs the per-rank input width to be a multiple "
+            f"of 128 (four MX blocks, one chunk of the kernel), got K={K} at "
+            f"TP={get_tp_world_size()}"
+        )
+    if N % 64 != 0:
+        raise ValueError(
+            f"{name}: mxfp4 needs the per-rank output width to be a multiple "
+            f"of 64, got N={N} at TP={get_tp_world_size()}"
+        )
+    return N, K
+
+
+def init_module_mx4(mod: nn.Module, name: str = "linear") -> None:
+    """Switch a linear layer to (empty) MX4 storage: mx4_weight u8 [N, K/2]
+    and mx4_scales u8 [N, K/32] exactly as an MXFP4 checkpoint stores them
+    (format in ops/ref.py). The bf16 parameter is dropped, so a model
+    switched before its weights stream in never holds it."""
+    from .. import ops
+    from ..ops import ref
+
+    N, K = _mx4_check_shape(mod, name)
+    dev = mod.weight.device
+    mod.mx4_dtype = mod.weight.dtype
+    del mod._parameters["weight"]
+    mod.weight = None
+    mod.register_buffer(
+        "mx4_weight", torch.zeros(N, K // 2, dtype=torch.uint8, device=dev),
+        persistent=False)
+    mod.register_buffer(
+        "mx4_scales",
+        torch.full((N, K // ref.MX4_BLOCK), 127, dtype=torch.uint8,
+                   device=dev),
+        persistent=False)
+    mod.mx4 = True
+    mod.mx4_shape = (N, K)
+    ops.reserve_dequant_workspace(N * K, dev)
+
+
+def finalize_module_mx4(mod: nn.Module) -> None:
+    """After the MX4 buffers are filled: reserve the device's dequant
+    workspace (the module may have moved since it was switched) and, on CPU,
+    keep the dequantized weight in the layer's dtype so that the CPU path is
+    F.linear on it."""
+    from .. import ops
+    from ..ops import ref
+
+    dev = mod.mx4_weight.device
+    if dev.type == "cuda":
+        ops.reserve_dequant_workspace(mod.mx4_shape[0] * mod.mx4_shape[1],
+                                      dev)
+        return
+    mod.register_buffer(
+        "weight_qdq",
+        ref.mx4_dequant(mod.mx4_weight, mod.mx4_scales).to(mod.mx4_dtype),
+        persistent=False,
+    )
+
+
+def quantize_module_mx4(mod: nn.Module, name: str = "linear") -> None:
+    """Switch a loaded linear layer to MX4 in memory by the OCP MX conversion
+    rule (ops.ref.mx4_quantize): what --quantization mxfp4 does to a bf16
+    checkpoint."""
+    from ..ops import ref
+
+    _mx4_check_shape(mod, name)
+    packed, scales = ref.mx4_quantize(mod.weight.data)
+    init_module_mx4(mod, name)
+    mod.mx4_weight.copy_(packed)
+    mod.mx4_scales.copy_(scales)
+    finalize_module_mx4(mod)
+
+
+def _mx4_linear(mod: nn.Module, x, bias, defer: bool):
+    if not x.is_cuda:
+        return F.linear(x, mod.weight_qdq, bias)
+    from .. import ops
+
+    return ops.mx4_linear(x, (mod.mx4_weight, mod.mx4_scales), bias,
+                          defer=defer)
+
+
 class LoRAState:
     """Per-layer multi-LoRA slot tensors (arks_amd/loader/lora_loader.py):
     A [max_loras, S*R, K] and B [max_loras, N, R] bf16 over the layer's LOCAL
@@ -298,12 +383,13 @@ class ColumnParallelLinear(nn.Module):
     fp8 = False
     w4 = False
     w8 = False  # block-scaled e4m3 weights (init_module_w8)
+    mx4 = False  # MXFP4 weights (init_module_mx4)
     lora: LoRAState | None = None  # set when the engine runs enable_lora
 
     def forward(self, x, lora_tiles=None, defer: bool = False):
         """defer=True: the caller can consume an ops.SplitKPending in place
         of the tensor (see ops.skinny_gemm). Granted only where the fused
-        consumers are valid: bf16, W4 or W8 GEMM, TP world size 1, no LoRA
+        consumers are valid: bf16, W4, W8 or MX4 GEMM, TP world size 1, no LoRA
         delta."""
         if isinstance(x, tuple):  # pre-quantized by the producing kernel
             return _fp8_linear_prequant(self, *x)
@@ -317,6 +403,8 @@ class ColumnParallelLinear(nn.Module):
             y = _w4_linear(self, x, self.bias, defer)
         elif self.w8:
             y = _w8_linear(self, x, self.bias, defer)
+        elif self.mx4:
+            y = _mx4_linear(self, x, self.bias, defer)
         else:
             y = ops.linear_bf16(x, self.weight, self.bias, defer=defer)
         if use_lora:
@@ -411,6 +499,7 @@ class RowParallelLinear(nn.Module):
     fp8 = False
     w4 = False
     w8 = False  # block-scaled e4m3 weights (init_module_w8)
+    mx4 = False  # MXFP4 weights (init_module_mx4)
     lora: LoRAState | None = None  # set when the engine runs enable_lora
 
     def forward(self, x, lora_tiles=None, defer: bool = False):
@@ -435,6 +524,8 @@ class RowParallelLinear(nn.Module):
                 y = _w4_linear(self, x, None, defer)
             elif self.w8:
                 y = _w8_linear(self, x, None, defer)
+            elif self.mx4:
+                y = _mx4_linear(self, x, None, defer)
             else:
                 y = ops.linear_bf16(x, self.weight, defer=defer)
             if isinstance(y, ops.SplitKPending):

@@ -34,12 +34,15 @@ def parse_args(argv=None):
     p.add_argument("--enforce-eager", action="store_true")
     p.add_argument("--disaggregation-mode", choices=["prefill", "decode"],
                    default=None)
-    p.add_argument("--quantization", choices=["fp8", "int4", "awq"],
+    p.add_argument("--quantization",
+                   choices=["fp8", "int4", "awq", "mxfp4"],
                    default=None,
                    help="fp8: W8A8 at load (on a block-scaled FP8 checkpoint, "
                         "which is also auto-detected: its own W8A16 format); "
                         "int4: 4-bit round-to-nearest at load; "
-                        "awq: a 4-bit AWQ checkpoint (also auto-detected)")
+                        "awq: a 4-bit AWQ checkpoint (also auto-detected); "
+                        "mxfp4: OCP MXFP4 weights, an MXFP4 checkpoint (also "
+                        "auto-detected) or converted at load from bf16")
     p.add_argument("--quantize-experts", action="store_true",
                    help="with --quantization int4 on an MoE model: also "
                         "quantize the routed and shared experts")
