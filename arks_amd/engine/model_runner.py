@@ -709,9 +709,17 @@ class ModelRunner:
         for i in rej:
             seq, d = sb.seqs[i], drafts[i]
             qn = cu[i + 1] - cu[i]
-            rows = logits[cu[i]:cu[i + 1]].float()
+            rows = logits[cu[i]:cu[i + 1]]
             sp = seq.sampling
-            if sp.top_p < 1.0 or sp.top_k > 0 or sp.min_p > 0.0:
+            filtered = sp.top_p < 1.0 or sp.top_k > 0 or sp.min_p > 0.0
+            if filtered and rows.is_cuda:
+                rows = rows.contiguous().clone()
+                temps = torch.full((qn,), sp.temperature, dtype=torch.float32,
+                                   device=rows.device)
+                ops.apply_sample_cutoff(rows, *ops.sample_cutoff(
+                    rows, temps, *self._filter_tensors([sp] * qn, rows.device)))
+            rows = rows.float()
+            if filtered and not rows.is_cuda:
                 rows = self._apply_top_p_top_k(rows, [seq] * qn)
             probs = torch.softmax(rows / sp.temperature, dim=-1)
             u = torch.rand(2, qn, device=logits.device).tolist()
@@ -776,6 +784,7 @@ class ModelRunner:
         if any(s.sampling.has_penalties for s in seqs):
             logits = self._apply_penalties(logits, seqs)
         temps = [s.sampling.temperature for s in seqs]
+        cutoff = None
         if all(t == 0.0 for t in temps):
             if masks is not None:
                 ids = ops.greedy_sample_masked(logits.contiguous(), masks,
@@ -783,8 +792,20 @@ class ModelRunner:
             else:
                 ids = ops.greedy_sample(logits.contiguous())
         else:
-            logits = self._apply_top_p_top_k(logits, seqs)
             t = torch.tensor(temps, dtype=torch.float32, device=logits.device)
+            if not logits.is_cuda:
+                logits = self._apply_top_p_top_k(logits, seqs)
+            elif any(
+                sp.temperature > 0.0
+                and (sp.top_p < 1.0 or sp.top_k > 0 or sp.min_p > 0.0)
+                for sp in (s.sampling for s in seqs)
+            ):
+                # one cutoff pair per row over the whole batch (topk_topp.hip),
+                # consumed inside the sampler; a structured row with a
+                # nucleus had its bitmask applied above, so masks is None
+                logits = logits.contiguous()
+                cutoff = ops.sample_cutoff(logits, t, *self._filter_tensors(
+                    [s.sampling for s in seqs], logits.device))
             u = torch.rand(
                 logits.shape, dtype=torch.float32, device=logits.device
             )
@@ -804,15 +825,29 @@ class ModelRunner:
                 ids = ops.sample_tokens_masked(logits.contiguous(), t, u,
                                                masks, mask_row)
             else:
-                ids = ops.sample_tokens(logits.contiguous(), t, u)
+                ids = ops.sample_tokens(logits.contiguous(), t, u,
+                                        cutoff=cutoff)
         out = ids.tolist()
         if mask_row is not None:
             # a state with no allowed token at all (only possible when the
             # request's stop_token_ids ban every one) ends the sequence
             eos = self.model_cfg.eos_token_id
             out = [eos if t < 0 else t for t in out]
+        if cutoff is not None and any(
+                s.sampling.logprobs is not None for s in seqs):
+            # reported logprobs are those of the filtered distribution
+            logits = ops.apply_sample_cutoff(logits.clone(), *cutoff)
         self._last_logprobs = self._gather_logprobs(logits, seqs, out)
         return out
+
+    @staticmethod
+    def _filter_tensors(sps, device):
+        """(top_k int32, top_p float32, min_p float32), one entry per row."""
+        top_k = torch.tensor([min(max(sp.top_k, 0), 2**31 - 1) for sp in sps],
+                             dtype=torch.int32).to(device)
+        pm = torch.tensor([[sp.top_p for sp in sps], [sp.min_p for sp in sps]],
+                          dtype=torch.float32).to(device)
+        return top_k, pm[0], pm[1]
 
     # device-resident pool of packed allowed-token masks, keyed by
     # (grammar uid, DFA state): decode steps that revisit a state upload one

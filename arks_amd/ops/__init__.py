@@ -10,6 +10,7 @@ are unit-testable without a GPU.
 
 from __future__ import annotations
 
+import functools
 import os
 from typing import Callable, NamedTuple
 
@@ -1138,13 +1139,46 @@ def _sample_launch(fn, logits, args, chunks):
     return out
 
 
-def sample_tokens(logits, temperatures, uniform, chunks=None):
+def sample_tokens(logits, temperatures, uniform, chunks=None, cutoff=None):
     """Gumbel-max categorical sampling; rows with temperature 0 are greedy.
-    chunks forces the workgroups per row (default: _sample_chunks)."""
+    chunks forces the workgroups per row (default: _sample_chunks). cutoff =
+    the (cut_val, cut_idx) of sample_cutoff: tokens past it are never drawn."""
     if logits.is_cuda:
-        return _sample_launch(_native().gumbel_sample, logits,
-                              (temperatures, uniform), chunks)
+        if cutoff is None:
+            return _sample_launch(_native().gumbel_sample, logits,
+                                  (temperatures, uniform), chunks)
+        fn = functools.partial(_native().gumbel_sample, cut_val=cutoff[0],
+                               cut_idx=cutoff[1])
+        return _sample_launch(fn, logits, (temperatures, uniform), chunks)
+    if cutoff is not None:
+        logits = ref.apply_sample_cutoff(logits.clone(), *cutoff)
     return ref.gumbel_sample(logits, temperatures, uniform)
+
+
+def sample_cutoff(logits, temperatures, top_k, top_p, min_p):
+    """The top-k / top-p / min-p kept set of every row of bf16 logits as one
+    (cut_val float32 [rows], cut_idx int32 [rows]) pair: token i is kept iff
+    v_i > cut_val or (v_i == cut_val and i <= cut_idx). temperatures, top_p,
+    min_p are float32 [rows], top_k int32 [rows]; rows with temperature 0 or
+    no filter get the keep-all pair (-inf, INT32_MAX). Definition:
+    ref.sample_cutoff; kernel: topk_topp.hip."""
+    if logits.is_cuda:
+        rows = logits.shape[0]
+        cut_val = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        cut_idx = torch.empty(rows, dtype=torch.int32, device=logits.device)
+        _native().sample_cutoff(cut_val, cut_idx, logits, temperatures,
+                                top_k, top_p, min_p)
+        return cut_val, cut_idx
+    return ref.sample_cutoff(logits, temperatures, top_k, top_p, min_p)
+
+
+def apply_sample_cutoff(logits, cut_val, cut_idx):
+    """In place: -inf at every token past its row's cutoff pair; keep-all
+    rows are left alone."""
+    if logits.is_cuda:
+        _native().apply_sample_cutoff(logits, cut_val, cut_idx)
+        return logits
+    return ref.apply_sample_cutoff(logits, cut_val, cut_idx)
 
 
 def greedy_sample(logits, chunks=None):

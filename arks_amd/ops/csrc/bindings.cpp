@@ -106,7 +106,15 @@ void arks_greedy_sample(void* out, void* pairs, const void* logits, int rows,
                         int vocab, int chunks, hipStream_t stream);
 void arks_gumbel_sample(void* out, void* pairs, const void* logits,
                         const void* temperatures, const void* uniform,
-                        int rows, int vocab, int chunks, hipStream_t stream);
+                        const void* cut_val, const void* cut_idx, int rows,
+                        int vocab, int chunks, hipStream_t stream);
+void arks_sample_cutoff(void* cut_val, void* cut_idx, const void* logits,
+                        const void* temperatures, const void* top_k,
+                        const void* top_p, const void* min_p, int rows,
+                        int vocab, hipStream_t stream);
+void arks_apply_sample_cutoff(void* logits, const void* cut_val,
+                              const void* cut_idx, int rows, int vocab,
+                              hipStream_t stream);
 void arks_greedy_sample_masked(void* out, const void* logits,
                                const void* masks, const void* mask_row,
                                int rows, int vocab, int slots,
@@ -1072,16 +1080,72 @@ void greedy_sample(torch::Tensor out, torch::Tensor logits,
                      logits.size(1), (int)chunks, current_stream());
 }
 
+// One cutoff pair per row (topk_topp.hip): cut_val float32, cut_idx int32.
+static void check_cutoff(const torch::Tensor& logits,
+                         const torch::Tensor& cut_val,
+                         const torch::Tensor& cut_idx) {
+  TORCH_CHECK(cut_val.is_cuda() && cut_idx.is_cuda());
+  TORCH_CHECK(cut_val.scalar_type() == torch::kFloat32 &&
+              cut_val.is_contiguous() && cut_val.numel() == logits.size(0),
+              "cut_val must be float32 [rows]");
+  TORCH_CHECK(cut_idx.scalar_type() == torch::kInt32 &&
+              cut_idx.is_contiguous() && cut_idx.numel() == logits.size(0),
+              "cut_idx must be int32 [rows]");
+}
+
 void gumbel_sample(torch::Tensor out, torch::Tensor logits,
                    torch::Tensor temperatures, torch::Tensor uniform,
-                   c10::optional<torch::Tensor> pairs, int64_t chunks) {
+                   c10::optional<torch::Tensor> pairs, int64_t chunks,
+                   c10::optional<torch::Tensor> cut_val,
+                   c10::optional<torch::Tensor> cut_idx) {
   void* ws = check_sample_pairs(out, logits, pairs, chunks);
   TORCH_CHECK(temperatures.scalar_type() == torch::kFloat32);
   TORCH_CHECK(uniform.scalar_type() == torch::kFloat32);
+  TORCH_CHECK(cut_val.has_value() == cut_idx.has_value(),
+              "cut_val and cut_idx come together");
+  if (cut_val.has_value()) check_cutoff(logits, *cut_val, *cut_idx);
   arks_gumbel_sample(out.data_ptr(), ws, logits.data_ptr(),
                      temperatures.data_ptr(), uniform.data_ptr(),
+                     cut_val.has_value() ? cut_val->data_ptr() : nullptr,
+                     cut_idx.has_value() ? cut_idx->data_ptr() : nullptr,
                      logits.size(0), logits.size(1), (int)chunks,
                      current_stream());
+}
+
+// top_k int32, temperatures / top_p / min_p float32, one per row
+void sample_cutoff(torch::Tensor cut_val, torch::Tensor cut_idx,
+                   torch::Tensor logits, torch::Tensor temperatures,
+                   torch::Tensor top_k, torch::Tensor top_p,
+                   torch::Tensor min_p) {
+  check_bf16_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1 &&
+              logits.size(1) < INT32_MAX);
+  check_cutoff(logits, cut_val, cut_idx);
+  const int64_t rows = logits.size(0);
+  for (const torch::Tensor* p : {&temperatures, &top_p, &min_p})
+    TORCH_CHECK(p->is_cuda() && p->scalar_type() == torch::kFloat32 &&
+                    p->is_contiguous() && p->numel() == rows,
+                "temperatures, top_p, min_p must be float32 [rows]");
+  TORCH_CHECK(top_k.is_cuda() && top_k.scalar_type() == torch::kInt32 &&
+                  top_k.is_contiguous() && top_k.numel() == rows,
+              "top_k must be int32 [rows]");
+  if (rows == 0) return;
+  arks_sample_cutoff(cut_val.data_ptr(), cut_idx.data_ptr(),
+                     logits.data_ptr(), temperatures.data_ptr(),
+                     top_k.data_ptr(), top_p.data_ptr(), min_p.data_ptr(),
+                     rows, logits.size(1), current_stream());
+}
+
+void apply_sample_cutoff(torch::Tensor logits, torch::Tensor cut_val,
+                         torch::Tensor cut_idx) {
+  check_bf16_contig(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2);
+  check_cutoff(logits, cut_val, cut_idx);
+  if (logits.numel() == 0) return;
+  TORCH_CHECK((logits.size(1) + 2047) / 2048 <= 65535, "vocab too large");
+  arks_apply_sample_cutoff(logits.data_ptr(), cut_val.data_ptr(),
+                           cut_idx.data_ptr(), logits.size(0), logits.size(1),
+                           current_stream());
 }
 
 // masks [slots, ceil(vocab/32)] int32, mask_row [rows] int32 (-1 = none)
@@ -1475,7 +1539,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pairs") = py::none(), py::arg("chunks") = 1);
   m.def("gumbel_sample", &gumbel_sample, py::arg("out"), py::arg("logits"),
         py::arg("temperatures"), py::arg("uniform"),
-        py::arg("pairs") = py::none(), py::arg("chunks") = 1);
+        py::arg("pairs") = py::none(), py::arg("chunks") = 1,
+        py::arg("cut_val") = py::none(), py::arg("cut_idx") = py::none());
+  m.def("sample_cutoff", &sample_cutoff);
+  m.def("apply_sample_cutoff", &apply_sample_cutoff);
   m.def("greedy_sample_masked", &greedy_sample_masked);
   m.def("gumbel_sample_masked", &gumbel_sample_masked);
   m.def("apply_token_bitmask", &apply_token_bitmask);

@@ -32,12 +32,16 @@ __device__ __forceinline__ void sample_take(float v, int idx, float& best,
 // left (neither end nor the row stride need be a multiple of 8: the tail is
 // handled scalar), then wave shuffles + LDS. Starts from (-FLT_MAX, 0), so
 // a slice where nothing is taken (all NaN, all -inf, ...) reports index 0.
-template <bool GUMBEL>
+// With CUT, a token past the row's cutoff pair (topk_topp.hip: kept iff
+// v > cut_val, or v == cut_val at an index <= cut_idx, on the raw logit) is
+// skipped before its noise is even loaded.
+template <bool GUMBEL, bool CUT>
 __device__ __forceinline__ bool sample_scan(const bf16* __restrict__ lrow,
                                             const float* __restrict__ urow,
                                             const bool greedy,
                                             const float inv_t, const int begin,
-                                            const int end, float& best,
+                                            const int end, const float cut_val,
+                                            const int cut_idx, float& best,
                                             int& best_idx) {
   constexpr int BLOCK = SAMPLE_BLOCK;
   best = -FLT_MAX;
@@ -49,6 +53,9 @@ __device__ __forceinline__ bool sample_scan(const bf16* __restrict__ lrow,
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float v = bf16_bits_to_float(x[j]);
+      if constexpr (CUT) {
+        if (!(v > cut_val || (v == cut_val && i * 8 + j <= cut_idx))) continue;
+      }
       if constexpr (GUMBEL) {
         if (!greedy) {
           float u = urow[i * 8 + j];
@@ -61,6 +68,9 @@ __device__ __forceinline__ bool sample_scan(const bf16* __restrict__ lrow,
   }
   for (int idx = nvec * 8 + threadIdx.x; idx < end; idx += BLOCK) {
     float v = bf16_bits_to_float(lrow[idx]);
+    if constexpr (CUT) {
+      if (!(v > cut_val || (v == cut_val && idx <= cut_idx))) continue;
+    }
     if constexpr (GUMBEL) {
       if (!greedy) {
         float u = fmaxf(urow[idx], 1e-20f);
@@ -99,13 +109,15 @@ __device__ __forceinline__ bool sample_scan(const bf16* __restrict__ lrow,
 // pairs[row][c] and sample_merge_kernel picks the row's winner. One
 // workgroup per row leaves most of the chip idle at decode batch sizes
 // (64 rows of 304 KB on 256 CUs); rows x chunks covers it.
-template <bool GUMBEL>
+template <bool GUMBEL, bool CUT>
 __global__ __launch_bounds__(SAMPLE_BLOCK) void sample_kernel(
     int64_t* __restrict__ out,
     int2* __restrict__ pairs,  // [rows, chunks] (chunks > 1)
     const bf16* __restrict__ logits,  // [rows, vocab]
     const float* __restrict__ temperatures,  // null if !GUMBEL
     const float* __restrict__ uniform,  // [rows, vocab]
+    const float* __restrict__ cut_val,  // [rows], CUT only
+    const int* __restrict__ cut_idx,  // [rows], CUT only
     const int vocab, const int chunk_len) {
   const int row = blockIdx.x;
   const bf16* lrow = logits + (int64_t)row * vocab;
@@ -123,10 +135,16 @@ __global__ __launch_bounds__(SAMPLE_BLOCK) void sample_kernel(
   const int begin =
       (int)std::min<int64_t>((int64_t)blockIdx.y * chunk_len, vocab);
   const int end = (int)std::min<int64_t>((int64_t)begin + chunk_len, vocab);
+  float cv = 0.f;
+  int ci = 0;
+  if constexpr (CUT) {
+    cv = cut_val[row];
+    ci = cut_idx[row];
+  }
   float best;
   int best_idx;
-  if (!sample_scan<GUMBEL>(lrow, urow, greedy, inv_t, begin, end, best,
-                           best_idx))
+  if (!sample_scan<GUMBEL, CUT>(lrow, urow, greedy, inv_t, begin, end, cv, ci,
+                                best, best_idx))
     return;
   if (gridDim.y == 1)
     out[row] = best_idx;
@@ -334,20 +352,22 @@ __global__ void apply_bitmask_kernel(T* __restrict__ logits,
 using namespace arks;
 
 // chunks = workgroups per row (>= 1); pairs = workspace of rows * chunks
-// (value, index) pairs, 8 bytes each, unused when chunks == 1.
-template <bool GUMBEL>
+// (value, index) pairs, 8 bytes each, unused when chunks == 1. cut_val /
+// cut_idx = the rows' cutoff pairs, or both null for no filter.
+template <bool GUMBEL, bool CUT>
 static void launch_sample(void* out, void* pairs, const void* logits,
                           const void* temperatures, const void* uniform,
-                          int rows, int vocab, int chunks,
-                          hipStream_t stream) {
+                          const void* cut_val, const void* cut_idx, int rows,
+                          int vocab, int chunks, hipStream_t stream) {
   chunks = std::max(chunks, 1);
   // a multiple of 8, so that every chunk starts on a vector of its row
   const int chunk_len =
       chunks == 1 ? vocab : ((vocab + chunks - 1) / chunks + 7) / 8 * 8;
-  hipLaunchKernelGGL((sample_kernel<GUMBEL>), dim3(rows, chunks),
+  hipLaunchKernelGGL((sample_kernel<GUMBEL, CUT>), dim3(rows, chunks),
                      dim3(SAMPLE_BLOCK), 0, stream, (int64_t*)out,
                      (int2*)pairs, (const bf16*)logits,
-                     (const float*)temperatures, (const float*)uniform, vocab,
+                     (const float*)temperatures, (const float*)uniform,
+                     (const float*)cut_val, (const int*)cut_idx, vocab,
                      chunk_len);
   if (chunks > 1)
     hipLaunchKernelGGL(sample_merge_kernel, dim3((rows + 63) / 64), dim3(64),
@@ -399,15 +419,20 @@ void arks_apply_token_bitmask(void* logits, int is_fp32, const void* masks,
 
 void arks_greedy_sample(void* out, void* pairs, const void* logits, int rows,
                         int vocab, int chunks, hipStream_t stream) {
-  launch_sample<false>(out, pairs, logits, nullptr, nullptr, rows, vocab,
-                       chunks, stream);
+  launch_sample<false, false>(out, pairs, logits, nullptr, nullptr, nullptr,
+                              nullptr, rows, vocab, chunks, stream);
 }
 
 void arks_gumbel_sample(void* out, void* pairs, const void* logits,
                         const void* temperatures, const void* uniform,
-                        int rows, int vocab, int chunks, hipStream_t stream) {
-  launch_sample<true>(out, pairs, logits, temperatures, uniform, rows, vocab,
-                      chunks, stream);
+                        const void* cut_val, const void* cut_idx, int rows,
+                        int vocab, int chunks, hipStream_t stream) {
+  if (cut_val != nullptr && cut_idx != nullptr)
+    launch_sample<true, true>(out, pairs, logits, temperatures, uniform,
+                              cut_val, cut_idx, rows, vocab, chunks, stream);
+  else
+    launch_sample<true, false>(out, pairs, logits, temperatures, uniform,
+                               nullptr, nullptr, rows, vocab, chunks, stream);
 }
 
 }  // extern "C"

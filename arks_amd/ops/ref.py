@@ -349,6 +349,83 @@ def gumbel_sample(
     return scaled.argmax(dim=-1)
 
 
+INT32_MAX = 2**31 - 1
+
+
+def sample_cutoff(
+    logits: torch.Tensor,  # [rows, vocab]
+    temperatures: torch.Tensor,  # [rows] float
+    top_k: torch.Tensor,  # [rows] int; <= 0 or >= vocab: off
+    top_p: torch.Tensor,  # [rows] float; >= 1: off
+    min_p: torch.Tensor,  # [rows] float; <= 0: off
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """The top-k / top-p / min-p kept set of every row, as one pair per row.
+
+    Tokens are ordered by (value descending, index ascending), NaN last and
+    never kept; p = softmax(logits / T) over the others. The kept set is the
+    first n = max(1, min(n_k, n_p, n_m)) tokens of that order: n_k = top_k,
+    n_p = the tokens whose exclusive cumulative p is < top_p, n_m = the
+    tokens with p >= min_p * p_max. Being a prefix of a strict order it is
+    described by (cut_val float32, cut_idx int32): token i is kept iff
+    v_i > cut_val or (v_i == cut_val and i <= cut_idx); cut_idx is INT32_MAX
+    when every token of value cut_val is kept. Rows with T <= 0, no active
+    filter or nothing but NaN get the keep-all pair (-inf, INT32_MAX)."""
+    rows, vocab = logits.shape
+    cut_val = torch.full((rows,), float("-inf"), dtype=torch.float32,
+                         device=logits.device)
+    cut_idx = torch.full((rows,), INT32_MAX, dtype=torch.int32,
+                         device=logits.device)
+    for r in range(rows):
+        t, k = float(temperatures[r]), int(top_k[r])
+        p, m = float(top_p[r]), float(min_p[r])
+        k_on, p_on, m_on = 0 < k < vocab, p < 1.0, m > 0.0
+        if not t > 0.0 or not (k_on or p_on or m_on):
+            continue
+        v = logits[r].double()
+        nan = v.isnan()
+        count = int((~nan).sum())
+        if count == 0:
+            continue
+        # two stable sorts: by value, then NaN to the back
+        order = torch.sort(v.masked_fill(nan, float("-inf")), descending=True,
+                           stable=True).indices
+        order = order[torch.sort(nan[order].int(), stable=True).indices]
+        sv = v[order[:count]]
+        # a token equal to the maximum weighs 1, also where that is +-inf
+        w = torch.where(sv == sv[0], 1.0, torch.exp((sv - sv[0]) / t))
+        prob = w / w.sum()
+        n = count
+        if k_on:
+            n = min(n, k)
+        if p_on:
+            n = min(n, int(((prob.cumsum(0) - prob) < p).sum()))
+        if m_on:
+            n = min(n, int((prob >= m * prob[0]).sum()))
+        n = max(n, 1)
+        cut_val[r] = sv[n - 1]
+        if n < count and sv[n] == sv[n - 1]:
+            cut_idx[r] = order[n - 1]
+    return cut_val, cut_idx
+
+
+def cutoff_keep(logits: torch.Tensor, cut_val: torch.Tensor,
+                cut_idx: torch.Tensor) -> torch.Tensor:
+    """[rows, vocab] bool: the tokens a cutoff pair keeps."""
+    v = logits.double()
+    cv = cut_val.double().unsqueeze(1)
+    idx = torch.arange(logits.shape[1], device=logits.device).unsqueeze(0)
+    return (v > cv) | ((v == cv) & (idx <= cut_idx.long().unsqueeze(1)))
+
+
+def apply_sample_cutoff(logits: torch.Tensor, cut_val: torch.Tensor,
+                        cut_idx: torch.Tensor) -> torch.Tensor:
+    """In place: -inf past the cutoff; keep-all rows are left alone."""
+    keep_all = (cut_val == float("-inf")) & (cut_idx == INT32_MAX)
+    drop = ~cutoff_keep(logits, cut_val, cut_idx) & ~keep_all.unsqueeze(1)
+    logits.masked_fill_(drop, float("-inf"))
+    return logits
+
+
 def bitmask_allowed(masks: torch.Tensor, mask_row: torch.Tensor,
                     vocab: int) -> torch.Tensor:
     """[rows, vocab] bool from packed masks: bit (t % 32) of int32 word
