@@ -255,14 +255,41 @@ class MoEMLP(nn.Module):
                 requires_grad=False,
             )
 
-    # Below this many tokens the dense path wins: every expert's weights
-    # are streamed from HBM regardless (tokens scatter over all experts),
-    # so decode is weight-bandwidth-bound and the extra MFMA work of
-    # computing all tokens per expert stays at or under the HBM floor up
-    # to ~256 tokens (E*T*3*I*H*2 flops vs E*3*I*H*2 bytes: the crossover
-    # at ~1.5 PF effective and ~6 TB/s is T ~ 250). Data-independent
-    # shapes make every decode batch size hipGraph-capturable.
+    # Up to this many tokens every launch shape of the block depends on T
+    # alone (no host sync), so every decode batch size is hipGraph-capturable.
+    # It bounds two things:
+    #  - the library path of bf16 experts (_forward_bmm, below it;
+    #    _forward_sparse above): the dense bmm streams EVERY expert's weights
+    #    whatever the router picked, and its extra MFMA work stays at or
+    #    under the HBM floor up to ~256 tokens (E*T*3*I*H*2 flops vs
+    #    E*3*I*H*2 bytes: the crossover at ~1.5 PF effective and ~6 TB/s is
+    #    T ~ 250). It now serves only the expert shapes the routed bf16
+    #    kernel does not take, and T above ROUTED_BF16_TOKENS;
+    #  - _forward_routed (W4, W8 and bf16 experts): max_rows = T up to here,
+    #    one sync per layer for the longest list above.
     DENSE_TOKENS = 256
+
+    # bf16 experts on the GPU run _forward_routed over ops.moe_bf16_gemm
+    # (moe_gemm.hip: only the selected experts' weights are read) up to this
+    # many tokens when both expert GEMMs pass ops.moe_bf16_supported; above
+    # it, and for other shapes, the library paths above.
+    # MEASURED with scripts/bench_moe_bf16.py on an MI355X (whole block,
+    # in-graph us, routed vs library; profiles/moe_bf16.md): qwen3-30b-a3b
+    # T=1 75 vs 232, T=8 144 vs 246, T=64 255 vs 281, T=256 276 vs 400;
+    # mixtral-8x7b T=1 247 vs 600, T=8 524 vs 605, T=64 557 vs 579, T=256
+    # 832 vs 899: routed is faster at every measured decode T on both shapes.
+    # At T=2048 (eager) it loses on both (800 vs 694, 4708 vs 1873: every
+    # 64-row slab re-reads its expert), so the value is DENSE_TOKENS, the
+    # largest measured T where routed wins on both; 257..2047 not measured.
+    ROUTED_BF16_TOKENS = DENSE_TOKENS
+    routed_bf16_calls = 0   # forwards that took the routed bf16 path
+
+    def bf16_routed_supported(self) -> bool:
+        """What moe_bf16_gemm_kernel needs of both expert GEMMs (w13: K = H,
+        N = 2I; w2: K = I, N = H)."""
+        return (not self.w4 and not self.w8
+                and ops.moe_bf16_supported(self.hidden, 2 * self.inter)
+                and ops.moe_bf16_supported(self.inter, self.hidden))
 
     # ---- W4 experts (int4 + quantize_experts, AWQ checkpoints) ----
     # Stacked packed buffers per local expert, ops.ref.w4_pack's format with
@@ -553,9 +580,9 @@ class MoEMLP(nn.Module):
         self.finalize_w8(name)
 
     def _forward_routed(self, x, gemm, w13, w2):
-        """GPU forward over quantized experts (gemm = ops.w4_moe_gemm on the
-        packed W4 triples, ops.w8_moe_gemm on the W8 pairs), the same for
-        every T: route once, then two routed grouped GEMMs that stream only
+        """GPU forward over routed experts (gemm = ops.w4_moe_gemm on the
+        packed W4 triples, ops.w8_moe_gemm on the W8 pairs, ops.moe_bf16_gemm
+        on the bf16 parameters themselves), the same for every T: route once, then two routed grouped GEMMs that stream only
         the experts the batch selected. Up to DENSE_TOKENS the launch shapes depend on T alone (no
         host sync; the decode graphs capture it); above it one sync per layer
         fetches the longest expert list to size the grid."""
@@ -592,8 +619,6 @@ class MoEMLP(nn.Module):
         return out
 
     def forward(self, x):
-        from ..parallel.comm import tp_all_reduce
-
         if self.w4 and x.is_cuda:
             return self._forward_routed(x, ops.w4_moe_gemm,
                                         self.w4_packed("w13"),
@@ -603,30 +628,50 @@ class MoEMLP(nn.Module):
                                         self.w8_weight("w13"),
                                         self.w8_weight("w2"))
         T = x.shape[0]
+        if (x.is_cuda and T <= self.ROUTED_BF16_TOKENS
+                and self.bf16_routed_supported()):
+            self.routed_bf16_calls += 1
+            return self._forward_routed(x, ops.moe_bf16_gemm, self.w13,
+                                        self.w2)
         router_logits = torch.nn.functional.linear(x, self.gate).float()
         # fused softmax+topk+renorm routing kernel (ops.moe_topk) replaces
         # a 5-kernel torch chain per layer
         weights, selected = ops.moe_topk(router_logits, self.top_k,
                                          self.norm_topk)
-        out = torch.zeros_like(x)
         if T <= self.DENSE_TOKENS:
-            # Batched over experts: two strided-batch GEMMs (bmm) instead of
-            # a per-expert loop — one launch pair regardless of E (Qwen3-MoE
-            # has 128 experts), and every expert's weights stream once. The
-            # weighted mix over experts is one gather kernel (ops.moe_mix).
-            E = self.local_experts
-            xb = x.unsqueeze(0).expand(E, T, self.hidden)
-            gu = torch.bmm(xb, self.w13)  # [E, T, 2I]
-            h = ops.silu_mul(gu.reshape(E * T, 2 * self.inter))
-            y = torch.bmm(h.view(E, T, self.inter), self.w2)  # [E, T, H]
-            out = ops.moe_mix(y, weights, selected, self.expert_base)
-            out = tp_all_reduce(out)
-            if self.shared is not None:
-                gate = torch.sigmoid(
-                    torch.nn.functional.linear(x, self.shared_gate).float()
-                ).to(x.dtype)
-                out = out + gate * self.shared(x)
-            return out
+            return self._forward_bmm(x, weights, selected)
+        return self._forward_sparse(x, weights, selected)
+
+    def _forward_bmm(self, x, weights, selected):
+        """The dense path (T <= DENSE_TOKENS): every local expert over every
+        token."""
+        from ..parallel.comm import tp_all_reduce
+
+        T = x.shape[0]
+        # Batched over experts: two strided-batch GEMMs (bmm) instead of
+        # a per-expert loop — one launch pair regardless of E (Qwen3-MoE
+        # has 128 experts), and every expert's weights stream once. The
+        # weighted mix over experts is one gather kernel (ops.moe_mix).
+        E = self.local_experts
+        xb = x.unsqueeze(0).expand(E, T, self.hidden)
+        gu = torch.bmm(xb, self.w13)  # [E, T, 2I]
+        h = ops.silu_mul(gu.reshape(E * T, 2 * self.inter))
+        y = torch.bmm(h.view(E, T, self.inter), self.w2)  # [E, T, H]
+        out = ops.moe_mix(y, weights, selected, self.expert_base)
+        out = tp_all_reduce(out)
+        if self.shared is not None:
+            gate = torch.sigmoid(
+                torch.nn.functional.linear(x, self.shared_gate).float()
+            ).to(x.dtype)
+            out = out + gate * self.shared(x)
+        return out
+
+    def _forward_sparse(self, x, weights, selected):
+        """The sparse path (prefill-sized T, any expert shape)."""
+        from ..parallel.comm import tp_all_reduce
+
+        T = x.shape[0]
+        out = torch.zeros_like(x)
         # Sparse path (prefill-sized T): sort token-expert pairs once so
         # each expert sees a contiguous segment (one host sync per layer
         # for the segment table), run the expert FFNs into ONE flat output

@@ -944,6 +944,36 @@ def w8_moe_gemm(a, weight, counts, pairs, src_div: int, max_rows: int,
     return out
 
 
+def moe_bf16_supported(K: int, N: int) -> bool:
+    """Whether moe_bf16_gemm_kernel takes an expert GEMM with K inputs and N
+    outputs: its N tile is 128 columns wide and it walks K in chunks of 64."""
+    return K >= 64 and K % 64 == 0 and N >= 128 and N % 128 == 0
+
+
+def moe_bf16_gemm(a, weight, counts, pairs, src_div: int, max_rows: int,
+                  out=None):
+    """Routed grouped bf16 GEMM over the stacked local experts of an MoE
+    block (moe_bf16_gemm_kernel): w4_moe_gemm for weight = the bf16 tensor
+    [E, K, N] exactly as MoEMLP holds w13 / w2 ([E, in, out], no copy, no
+    repack): out[p] = a[p // src_div] @ weight[e] for every local expert e
+    and p in pairs[e][:counts[e]]. Same arguments, same capture rules. A
+    row's result does not depend on the batch it is computed in. No eager
+    fallback on GPU: a shape the kernel cannot take (moe_bf16_supported)
+    raises."""
+    if not a.is_cuda:
+        return ref.moe_bf16_gemm(a, weight, counts, pairs, src_div, out=out)
+    T = pairs.shape[1] if pairs.dim() == 2 else 0
+    top_k = a.shape[0] * src_div // max(T, 1)
+    if out is None:
+        out = torch.empty((T * top_k, weight.shape[2]), dtype=a.dtype,
+                          device=a.device)
+    if not a.is_contiguous() or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    _native().moe_bf16_gemm(out, a, weight, counts, pairs, top_k, src_div,
+                            max_rows)
+    return out
+
+
 def rmsnorm_fp8(x, weight, eps: float = 1e-6):
     """Fused RMSNorm -> per-token fp8 e4m3: (out8, inv_scale). GPU-only
     fast path (hidden <= 8192); otherwise compose the unfused ops."""

@@ -34,6 +34,7 @@ SOURCES = [
     os.path.join(CSRC, "sampling.hip"),
     os.path.join(CSRC, "topk_topp.hip"),
     os.path.join(CSRC, "moe.hip"),
+    os.path.join(CSRC, "moe_gemm.hip"),
     os.path.join(CSRC, "allreduce.hip"),
     os.path.join(CSRC, "lora.hip"),
     os.path.join(CSRC, "pooling.hip"),

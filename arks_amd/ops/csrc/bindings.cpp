@@ -172,6 +172,10 @@ void arks_w8_moe_gemm(void* out, const void* a, const void* w8,
                       const void* pairs, int n_experts, int t_cols,
                       int n_pairs, int src_div, int slabs, int n_total,
                       int k_total, int nw, hipStream_t stream);
+void arks_moe_bf16_gemm(void* out, const void* a, const void* w,
+                        const void* counts, const void* pairs, int n_experts,
+                        int t_cols, int n_pairs, int src_div, int slabs,
+                        int n_total, int k_total, hipStream_t stream);
 void arks_mx4_skinny_gemm(void* part, void* out, const void* a, const void* w,
                           const void* scales, const void* bias, int m_rows,
                           int n_total, int k_total, int k_per_split,
@@ -923,6 +927,59 @@ void w8_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w8,
                    (int)slabs, (int)n, (int)k, nw, current_stream());
 }
 
+// The same over stacked bf16 experts as the model holds them
+// (moe_bf16_gemm_kernel, moe_gemm.hip): w bf16 [E, K, N], N contiguous.
+void moe_bf16_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
+                   torch::Tensor counts, torch::Tensor pairs, int64_t top_k,
+                   int64_t src_div, int64_t max_rows) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
+              w.dim() == 3 && w.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "weight must be contiguous bf16 [E, K, N] on GPU");
+  const int64_t ne = w.size(0), k = w.size(1), n = w.size(2);
+  TORCH_CHECK(ne >= 1 && ne <= 65535, "need 1 <= E_local <= 65535");
+  TORCH_CHECK(k >= 64 && k % 64 == 0,
+              "bf16 MoE GEMM needs K % 64 == 0, got K=", k);
+  TORCH_CHECK(n >= 128 && n % 128 == 0,
+              "bf16 MoE GEMM needs N % 128 == 0, got N=", n);
+  TORCH_CHECK(n * k < ((int64_t)1 << 31), "expert weight too large");
+  check_bf16_contig(a, "a");
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(a.dim() == 2 && a.size(1) == k, "a must be [rows, K]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "a rows must be 16-byte aligned");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == torch::kInt32 &&
+              counts.is_contiguous() && counts.dim() == 1 &&
+              counts.size(0) == ne, "counts must be int32 [E_local] on GPU");
+  TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt32 &&
+              pairs.is_contiguous() && pairs.dim() == 2 &&
+              pairs.size(0) == ne && pairs.size(1) >= 1,
+              "pairs must be int32 [E_local, T] on GPU, got ", pairs.sizes());
+  const int64_t t_cols = pairs.size(1);
+  TORCH_CHECK(top_k >= 1, "top_k must be >= 1");
+  const int64_t n_pairs = t_cols * top_k;
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == n && out.size(0) == n_pairs,
+              "out must be [T*k, N] = [", n_pairs, ", ", n, "], got ",
+              out.sizes());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "out rows must be 8-byte aligned");
+  TORCH_CHECK(n_pairs < ((int64_t)1 << 31) / 2);
+  TORCH_CHECK(src_div >= 1 && a.size(0) * src_div >= n_pairs,
+              "a has ", a.size(0), " rows, too few for ", n_pairs,
+              " pairs at src_div=", src_div);
+  TORCH_CHECK(max_rows >= 1 && max_rows <= t_cols,
+              "need 1 <= max_rows <= T, got ", max_rows);
+  const auto dev = w.device();
+  TORCH_CHECK(a.device() == dev && out.device() == dev &&
+              counts.device() == dev && pairs.device() == dev);
+  const int64_t slabs = (max_rows + 63) / 64;
+  TORCH_CHECK(slabs <= 65535, "max_rows too large");
+  arks_moe_bf16_gemm(out.data_ptr(), a.data_ptr(), w.data_ptr(),
+                     counts.data_ptr(), pairs.data_ptr(), (int)ne,
+                     (int)t_cols, (int)n_pairs, (int)src_div, (int)slabs,
+                     (int)n, (int)k, current_stream());
+}
+
 // Checks shared by the consumers of split-K partials [nsplits, mrows, n].
 const void* check_partials(const torch::Tensor& part,
                            const c10::optional<torch::Tensor>& bias,
@@ -1526,6 +1583,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w8_skinny_gemm_partials", &w8_skinny_gemm_partials);
   m.def("w8_dequant", &w8_dequant);
   m.def("w8_moe_gemm", &w8_moe_gemm);
+  m.def("moe_bf16_gemm", &moe_bf16_gemm);
   m.def("mx4_skinny_gemm", &mx4_skinny_gemm);
   m.def("mx4_skinny_gemm_partials", &mx4_skinny_gemm_partials);
   m.def("mx4_dequant", &mx4_dequant);

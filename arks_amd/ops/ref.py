@@ -727,6 +727,28 @@ def w8_moe_gemm(a: torch.Tensor, weight, counts: torch.Tensor,
     return out
 
 
+def moe_bf16_gemm(a: torch.Tensor, weight: torch.Tensor,
+                  counts: torch.Tensor, pairs: torch.Tensor, src_div: int,
+                  out=None) -> torch.Tensor:
+    """out[p] = a[p // src_div] @ weight[e] for every local expert e and
+    p in pairs[e][:counts[e]]: a plain loop over experts (f32 accumulate, one
+    rounding to a's dtype). weight is the stacked bf16 [E, K, N] of an MoE
+    block. Rows of `out` that no local expert owns are left as they are
+    (zeros when out is None)."""
+    E, N = weight.shape[0], weight.shape[2]
+    T = pairs.shape[1]
+    n_pairs = T * (a.shape[0] * src_div // T)
+    if out is None:
+        out = torch.zeros(n_pairs, N, dtype=a.dtype, device=a.device)
+    for e in range(E):
+        p = pairs[e, :int(counts[e])].long()
+        if p.numel() == 0:
+            continue
+        src = torch.div(p, src_div, rounding_mode="floor")
+        out[p] = (a[src].float() @ weight[e].float()).to(out.dtype)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # MX4 (W4A16): OCP microscaling FP4 (MXFP4). e2m1 elements, one shared e8m0
 # scale per block of 32 along K:
