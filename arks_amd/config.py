@@ -168,9 +168,11 @@ class ModelConfig:
         fp4, per group of 32 with e8m0 scales, stored real_quantized; no
         per-layer overrides, no quantized outputs, bias or KV cache; anything
         else raises naming the offending field. input_tensors may be null or
-        a DYNAMIC spec, which is accepted and ignored: the activations stay
-        bf16 here, more precise than the checkpoint asks for. Static input
-        scales are refused (they would be tensors the engine never reads)."""
+        a DYNAMIC spec. By default the activations stay bf16, more precise
+        than the checkpoint asks for; EngineConfig.mx_activations="mxfp4"
+        honours the spec (dynamic MXFP4 inputs, group 32, e8m0: the same
+        format as the weights). Static input scales are refused (they would
+        be tensors the engine never reads)."""
         tail = ("the engine reads Quark MXFP4 with static fp4 weights, "
                 "per_group scales of group size 32 in e8m0, weights only")
 
@@ -670,6 +672,12 @@ class EngineConfig:
     # with quantization="int4" on an MoE model: also quantize the routed
     # experts and the shared expert at load (routed grouped W4 GEMM)
     quantize_experts: bool = False
+    # "bf16" | "mxfp4": with MXFP4 weights, also quantize the inputs of the
+    # MX4 layers dynamically to MXFP4 (group 32 along K, e8m0 scales), as a
+    # Quark MXFP4 export specifies them: W4A4, prefill on the block-scaled
+    # FP4 matrix instruction. lm_head, experts and excluded modules keep
+    # bf16 activations.
+    mx_activations: str = "bf16"
     # "auto" (bf16) | "fp8": e4m3 KV pages (halves the decode KV stream;
     # scale 1.0, opt-in like vLLM's --kv-cache-dtype fp8)
     kv_cache_dtype: str = "auto"
@@ -717,6 +725,17 @@ class EngineConfig:
                 f"quantization={self.quantization!r} (an AWQ checkpoint's "
                 "experts are 4-bit already)"
             )
+        if self.mx_activations not in ("bf16", "mxfp4"):
+            raise ValueError(
+                f"unknown mx_activations {self.mx_activations!r}: expected "
+                "'bf16' or 'mxfp4'"
+            )
+        if (self.mx_activations == "mxfp4"
+                and self.quantization not in (None, "mxfp4")):
+            raise ValueError(
+                "mx_activations='mxfp4' needs quantization='mxfp4' (or an "
+                f"MXFP4 checkpoint), got quantization={self.quantization!r}"
+            )
         if not self.enable_lora:
             if self.lora_modules:
                 raise ValueError("lora_modules given without enable_lora")
@@ -749,6 +768,16 @@ class EngineConfig:
             )
 
     def resolve_quantization(self, model_cfg: ModelConfig) -> str | None:
+        mode = self._resolve_quantization(model_cfg)
+        if self.mx_activations == "mxfp4" and mode != "mxfp4":
+            raise ValueError(
+                "mx_activations='mxfp4' needs MXFP4 weights, but the "
+                f"resolved quantization is {mode!r} (give "
+                "quantization='mxfp4' or an MXFP4 checkpoint)"
+            )
+        return mode
+
+    def _resolve_quantization(self, model_cfg: ModelConfig) -> str | None:
         """The mode the engine runs: an AWQ checkpoint selects "awq" on its
         own and excludes every other mode; "awq" needs such a checkpoint. A
         block-scaled FP8 checkpoint selects "fp8_block" on its own; "fp8"

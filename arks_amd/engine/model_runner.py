@@ -146,6 +146,12 @@ class ModelRunner:
                 torch.cuda.empty_cache()  # as for int4
         elif self.quantization is not None:
             raise ValueError(f"unknown quantization {self.quantization!r}")
+        if self.cfg.mx_activations == "mxfp4":
+            # W4A4: every MX4 layer quantizes its input too (lm_head, experts
+            # and excluded modules are not MX4 modules)
+            for mod in self.model.modules():
+                if getattr(mod, "mx4", False):
+                    mod.mx4_act = "mxfp4"
         # serving past max_position_embeddings: the rope table must cover
         # every reachable position (OOB table reads fault on GPU)
         if hasattr(self.model, "extend_rope_table"):

@@ -890,6 +890,116 @@ def mx4_linear(x, weight, bias=None, defer: bool = False, plan=None):
     return _wq_linear(_MX4, x, weight, bias, defer, plan)
 
 
+# W4A4: rows from which mx4a4_linear quantizes the activations to packed
+# MXFP4 and runs the scaled-MFMA GEMM; below it the activations are
+# quantized and expanded again (QDQ) and take the W4A16 route of mx4_linear,
+# which computes the same products. MEASURED on an MI355X with
+# scripts/bench_mx4.py --a4 (in-graph us, quantizer + MFMA GEMM vs QDQ +
+# mx4_linear; profiles/mx4_gemm.md): M=129: qkv 20.3 vs 39.9, o 20.1 vs 38.9,
+# gate_up 49.4 vs 171.2, down 86.2 vs 133.1, and every larger measured M
+# (160 .. 8192) likewise: the MFMA route wins on all four shapes. M=128:
+# down 95.3 vs 56.3 (the slabs win; qkv / o / gate_up already favour the
+# MFMA, 21.3 / 21.2 / 41.0 vs 33.0 / 30.1 / 87.8), M=64: only gate_up does.
+# So it sits right above the slab limit, the smallest measured M from which
+# the MFMA route wins everywhere.
+MX4A4_MFMA_MIN_M = MX4_SLAB_MAX_M + 1
+# mx4_mfma_gemm_kernel's workgroups take 128 rows once the 128-row grid
+# fills the 256 CUs twice (two workgroups fit a CU), else 64. A starting
+# rule from the grid sizes, not a measured crossover: the 64 / 128 crossover
+# is still to be measured (mx4a4_gemm's mtile argument forces either).
+_MX4A4_TILE128_MIN_WGS = 512
+
+
+def _check_mx4_act(x, weight, what: str):
+    if x.dim() != 2 or x.dtype != torch.bfloat16:
+        raise ValueError(f"{what} needs a 2-D bf16 input, got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    if weight is not None and _MX4.shape(weight)[1] != x.shape[1]:
+        raise ValueError(f"{what}: x has K={x.shape[1]}, weight "
+                         f"K={_MX4.shape(weight)[1]}")
+    if x.shape[1] % 128 != 0:
+        raise ValueError(f"{what} needs K % 128 == 0, got K={x.shape[1]}")
+
+
+def mx4_quantize_act(x, qdq: bool = False):
+    """Dynamic MXFP4 quantization of bf16 activations x [M, K] along K by the
+    rule of ref.mx4_quantize (mx4_act_quant_kernel on GPU). Returns (xq u8
+    [M, K/2], xs u8 [M, K/32]), the layout of an MX4 weight, or with qdq=True
+    the bf16 [M, K] those codes expand to (exactly)."""
+    _check_mx4_act(x, None, "mx4_quantize_act")
+    if not x.is_cuda:
+        return ref.mx4_qdq(x) if qdq else ref.mx4_quantize(x)
+    M, K = x.shape
+    if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    if qdq:
+        xhat = torch.empty((M, K), dtype=x.dtype, device=x.device)
+        if M:
+            _native().mx4_act_qdq(xhat, x)
+        return xhat
+    xq = torch.empty((M, K // 2), dtype=torch.uint8, device=x.device)
+    xs = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
+    if M:
+        _native().mx4_act_quant(xq, xs, x)
+    return xq, xs
+
+
+def mx4a4_gemm(xq, xs, weight, bias=None, mtile: int | None = None):
+    """bf16 [M, N] = dq(xq, xs) @ dq(weight)^T + bias with both operands
+    MXFP4 (xq u8 [M, K/2], xs u8 [M, K/32] from mx4_quantize_act; weight =
+    (mx4_weight, mx4_scales)), f32 accumulation starting from the bias: any
+    M >= 1, N % 64 == 0, K % 128 == 0, anything else raises. On GPU:
+    mx4_mfma_gemm_kernel on the block-scaled FP4 matrix instruction. On CPU:
+    the dequantized operands multiplied in f32.
+    mtile is for tests only: it forces the workgroup's rows (128 or 64) so
+    that both tile heights run at small shapes; callers leave it None."""
+    N, K = _MX4.shape(weight)
+    M = xq.shape[0] if xq.dim() == 2 else -1
+    if (M < 1 or N % 64 != 0 or K % 128 != 0
+            or tuple(xq.shape) != (M, K // 2)
+            or tuple(xs.shape) != (M, K // 32)
+            or xq.dtype != torch.uint8 or xs.dtype != torch.uint8):
+        raise ValueError(
+            f"mx4a4_gemm needs xq u8 [M, K/2] and xs u8 [M, K/32] with "
+            f"M >= 1 for a weight with N % 64 == 0 and K % 128 == 0, got xq "
+            f"{tuple(xq.shape)} {xq.dtype}, xs {tuple(xs.shape)} {xs.dtype}, "
+            f"N={N}, K={K}")
+    if mtile not in (None, 64, 128):
+        raise ValueError(f"mtile must be 64 or 128, got {mtile}")
+    if not xq.is_cuda:
+        y = ref.mx4_dequant(xq, xs) @ ref.mx4_dequant(*weight).t()
+        if bias is not None:
+            y = y + bias.float()
+        return y.to(torch.bfloat16)
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    if mtile is None:
+        wgs = -(-M // 128) * -(-N // 128)
+        mtile = 128 if wgs >= _MX4A4_TILE128_MIN_WGS else 64
+    _native().mx4a4_gemm(out, xq, xs, *weight, bias, mtile)
+    return out
+
+
+def mx4a4_linear(x, weight, bias=None, defer: bool = False, plan=None):
+    """y = mxfp4(x) @ dequant(weight)^T + bias: an MX4 layer with dynamic
+    MXFP4 activations (group 32 along K, e8m0 scales, the rule of
+    ref.mx4_quantize), as a Quark MXFP4 export specifies its inputs. On GPU,
+    from MX4A4_MFMA_MIN_M rows: mx4_act_quant_kernel packs x and
+    mx4_mfma_gemm_kernel multiplies FP4 by FP4 on the scaled MFMA, so the
+    weight is never expanded. Below: the quantizer writes the expanded
+    activations and mx4_linear runs on them (skinny kernel, slabs, defer and
+    plan as there). Both routes sum the same exact products in f32, so batch
+    size changes the result by summation order only. Scratch comes from the
+    caching allocator, so graph capture is safe. On CPU: ref.mx4a4_linear."""
+    if not x.is_cuda:
+        return ref.mx4a4_linear(x, *weight, bias)
+    _check_mx4_act(x, weight, "mx4a4_linear")
+    if x.shape[0] == 0:
+        return x.new_empty((0, _MX4.shape(weight)[0]))
+    if x.shape[0] >= MX4A4_MFMA_MIN_M:
+        return mx4a4_gemm(*mx4_quantize_act(x), weight, bias)
+    return mx4_linear(mx4_quantize_act(x, qdq=True), weight, bias, defer, plan)
+
+
 def w4_moe_gemm(a, packed, counts, pairs, src_div: int, max_rows: int,
                 out=None):
     """Routed grouped W4A16 GEMM over the stacked local experts of an MoE

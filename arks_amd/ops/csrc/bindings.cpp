@@ -183,6 +183,13 @@ void arks_mx4_skinny_gemm(void* part, void* out, const void* a, const void* w,
                           hipStream_t stream);
 void arks_mx4_dequant(void* out, const void* w, const void* scales,
                       int n_total, int k_total, hipStream_t stream);
+void arks_mx4_act_quant(void* xq, void* xs, void* xhat, const void* x,
+                        int m_rows, int k_total, int64_t x_stride, bool qdq,
+                        hipStream_t stream);
+void arks_mx4_mfma_gemm(void* out, const void* xq, const void* xs,
+                        const void* w, const void* ws, const void* bias,
+                        int m_rows, int n_total, int k_total, int mtile,
+                        hipStream_t stream);
 void arks_moe_route(void* counts, void* pairs, const void* ids, int n_pairs,
                     int T, int expert_base, int n_local, hipStream_t stream);
 void arks_mfma_probe(void* d, const void* a, const void* b, hipStream_t stream);
@@ -798,6 +805,84 @@ void mx4_dequant(torch::Tensor out, torch::Tensor w, torch::Tensor scales) {
   TORCH_CHECK(n * (k / 32) < (int64_t)1 << 39);
   arks_mx4_dequant(out.data_ptr(), w.data_ptr(), scales.data_ptr(), (int)n,
                    (int)k, current_stream());
+}
+
+// x bf16 [M, K] (unit column stride, rows 16 B aligned) to MXFP4
+// (mx4_act_quant_kernel): qdq writes xhat bf16 [M, K]; otherwise xq u8
+// [M, K/2] and xs u8 [M, K/32], the operand of mx4a4_gemm.
+void check_mx4_act(const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
+              x.dim() == 2 && x.size(0) >= 1 && x.stride(1) == 1 &&
+              x.stride(0) >= x.size(1) && x.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be bf16 [M, K] on GPU with 16 B aligned rows");
+  TORCH_CHECK(x.size(1) >= 128 && x.size(1) % 128 == 0,
+              "MX4 needs K % 128 == 0, got K=", x.size(1));
+  TORCH_CHECK(x.size(0) * (x.size(1) / 8) < (int64_t)1 << 39);
+}
+
+void check_mx4_act_packed(const torch::Tensor& xq, const torch::Tensor& xs,
+                          int64_t m, int64_t k, const at::Device& dev) {
+  TORCH_CHECK(xq.is_cuda() && xq.scalar_type() == torch::kUInt8 &&
+              xq.is_contiguous() && xq.dim() == 2 && xq.size(0) == m &&
+              xq.size(1) == k / 2 && xq.device() == dev &&
+              reinterpret_cast<uintptr_t>(xq.data_ptr()) % 16 == 0,
+              "xq must be contiguous uint8 [M, K/2] on the GPU of x / w");
+  TORCH_CHECK(xs.is_cuda() && xs.scalar_type() == torch::kUInt8 &&
+              xs.is_contiguous() && xs.dim() == 2 && xs.size(0) == m &&
+              xs.size(1) == k / 32 && xs.device() == dev &&
+              reinterpret_cast<uintptr_t>(xs.data_ptr()) % 4 == 0,
+              "xs must be contiguous uint8 [M, K/32] on the GPU of x / w");
+}
+
+void mx4_act_quant(torch::Tensor xq, torch::Tensor xs, torch::Tensor x) {
+  check_mx4_act(x);
+  check_mx4_act_packed(xq, xs, x.size(0), x.size(1), x.device());
+  arks_mx4_act_quant(xq.data_ptr(), xs.data_ptr(), nullptr, x.data_ptr(),
+                     (int)x.size(0), (int)x.size(1), x.stride(0), false,
+                     current_stream());
+}
+
+void mx4_act_qdq(torch::Tensor xhat, torch::Tensor x) {
+  check_mx4_act(x);
+  check_bf16_contig(xhat, "xhat");
+  TORCH_CHECK(xhat.dim() == 2 && xhat.sizes() == x.sizes() &&
+              xhat.device() == x.device() &&
+              reinterpret_cast<uintptr_t>(xhat.data_ptr()) % 16 == 0,
+              "xhat must be bf16 [M, K] like x");
+  arks_mx4_act_quant(nullptr, nullptr, xhat.data_ptr(), x.data_ptr(),
+                     (int)x.size(0), (int)x.size(1), x.stride(0), true,
+                     current_stream());
+}
+
+// out bf16 [M, N] = dq(xq, xs) @ dq(w, scales)^T + bias on the scaled MFMA
+// (mx4_mfma_gemm_kernel), any M >= 1. mtile = 128 or 64 rows per workgroup.
+void mx4a4_gemm(torch::Tensor out, torch::Tensor xq, torch::Tensor xs,
+                torch::Tensor w, torch::Tensor scales,
+                c10::optional<torch::Tensor> bias, int64_t mtile) {
+  const auto [n, k] = check_mx4_weight(w, scales);
+  const int64_t m = xq.dim() == 2 ? xq.size(0) : 0;
+  TORCH_CHECK(mtile == 128 || mtile == 64, "mtile must be 128 or 64");
+  // grid.y = ceil(M / mtile) must stay within 65535
+  TORCH_CHECK(m >= 1 && m <= 65535 * mtile,
+              "mx4a4_gemm needs 1 <= M <= 65535 * mtile, got M=", m);
+  check_mx4_act_packed(xq, xs, m, k, w.device());
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == m && out.size(1) == n &&
+              out.device() == w.device() &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "out must be bf16 [M, N] on the weight's GPU");
+  const void* bias_ptr = nullptr;
+  if (bias.has_value()) {
+    check_bf16_contig(*bias, "bias");
+    TORCH_CHECK(bias->numel() == n && bias->device() == w.device() &&
+                reinterpret_cast<uintptr_t>(bias->data_ptr()) % 8 == 0,
+                "bias must be bf16 [N], 8 B aligned");
+    bias_ptr = bias->data_ptr();
+  }
+  arks_mx4_mfma_gemm(out.data_ptr(), xq.data_ptr(), xs.data_ptr(),
+                     w.data_ptr(), scales.data_ptr(), bias_ptr, (int)m,
+                     (int)n, (int)k, (int)mtile, current_stream());
 }
 
 // Routed grouped GEMM over stacked experts (w4_moe_gemm_kernel):
@@ -1587,6 +1672,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx4_skinny_gemm", &mx4_skinny_gemm);
   m.def("mx4_skinny_gemm_partials", &mx4_skinny_gemm_partials);
   m.def("mx4_dequant", &mx4_dequant);
+  m.def("mx4_act_quant", &mx4_act_quant);
+  m.def("mx4_act_qdq", &mx4_act_qdq);
+  m.def("mx4a4_gemm", &mx4a4_gemm);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache, py::arg("positions"),
         py::arg("part"), py::arg("bias"), py::arg("q_out"), py::arg("k_cache"),

@@ -32,9 +32,13 @@
 // mx4_dequant_kernel expands the weight to bf16 [N, K] for the library GEMM
 // (M above the slab limit).
 //
-// Not here: the mfma_scale_f32_*_f8f6f4 instructions (they need a quantized
-// A operand; decode is bound by the weight bytes and the activations stay
-// bf16) and a routed grouped expert GEMM (MX4 routed experts are dequantized
+// mx4_act_quant_kernel turns bf16 activations into MXFP4 (packed, or
+// quantized and expanded again) for the W4A4 mode; the GEMM on the
+// mfma_scale_f32_16x16x128_f8f6f4 instruction that takes both operands as
+// FP4 is mx4_mfma_gemm.hip. The kernels of this file keep bf16 activations:
+// decode is bound by the weight bytes.
+//
+// Not here: a routed grouped expert GEMM (MX4 routed experts are dequantized
 // to bf16 at load).
 #include "wq_stream.h"
 
@@ -155,9 +159,97 @@ __global__ __launch_bounds__(256) void mx4_dequant_kernel(
     *reinterpret_cast<bf16x8*>(o + 8 * s) = mx4_frag(q[s], sc);
 }
 
+// bf16 activations [M, K] (row stride x_stride) to MXFP4 by the conversion
+// rule of ops/ref.py mx4_quantize, for the W4A4 GEMM (mx4_mfma_gemm.hip).
+// A lane owns 8 consecutive elements (one 16 B load) and four adjacent lanes
+// one MX block. The block's amax is the maximum of the integer magnitude
+// bits (order-preserving for finite bf16), two quad-permute steps wide; its
+// exponent field e gives the scale byte clamp(e - 2), i.e. a shared exponent
+// of floor(log2(amax)) - 2, or 127 for an all-zero block. Four
+// v_cvt_scalef32_pk_fp4_bf16 (round to nearest even, saturating, dividing by
+// the scale) make the lane's dword of eight nibbles.
+//   QDQ = false: xq u8 [M, K/2] (one coalesced dword per lane) and xs u8
+//                [M, K/32] (lane 0 of the quad), the layout of the weights
+//   QDQ = true:  the same codes expanded again by mx4_frag into bf16 [M, K],
+//                exactly: the input of the W4A16 kernels below the MFMA
+//                threshold, which then see the same activations
+// Compiled without the packed f32 VALU forms, as mx4_mfma_gemm.hip explains
+// (the kernel has no f32 arithmetic, so this costs nothing).
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push( \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+template <bool QDQ>
+__global__ __launch_bounds__(256) void mx4_act_quant_kernel(
+    uint32_t* __restrict__ xq,  // [M, K/8] dwords of nibbles (!QDQ)
+    uint8_t* __restrict__ xs,   // [M, K/32] (!QDQ)
+    bf16* __restrict__ xhat,    // [M, K] (QDQ)
+    const bf16* __restrict__ x, const int m_rows, const int k_total,
+    const int64_t x_stride) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int per_row = k_total / 8;  // a multiple of 4: quads never straddle
+  const bool in = idx < (int64_t)m_rows * per_row;
+  const int64_t row = in ? idx / per_row : 0;
+  const int c = in ? (int)(idx % per_row) : 0;
+  union {
+    u32x4 u;
+    bf16x2 p[4];
+  } v;
+  v.u = u32x4{0u, 0u, 0u, 0u};
+  if (in) v.u = *reinterpret_cast<const u32x4*>(x + row * x_stride + 8 * c);
+
+  uint32_t amax = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t d = v.u[i] & 0x7fff7fffu;
+    amax = max(amax, max(d & 0xffffu, d >> 16));
+  }
+  // quad_perm [1,0,3,2] then [2,3,0,1]: every lane of the quad gets the max
+  amax = max(amax, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)amax, 0xB1,
+                                                         0xf, 0xf, true));
+  amax = max(amax, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)amax, 0x4E,
+                                                         0xf, 0xf, true));
+  const int e = (int)(amax >> 7);
+  const uint32_t s = amax == 0 ? 127u : (uint32_t)min(max(e - 2, 2), 252);
+  const float sc = mx4_scale(s);
+  uint32_t q = 0;
+  q = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(q, v.p[0], sc, 0);
+  q = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(q, v.p[1], sc, 1);
+  q = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(q, v.p[2], sc, 2);
+  q = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(q, v.p[3], sc, 3);
+  if (!in) return;
+  if constexpr (QDQ) {
+    *reinterpret_cast<bf16x8*>(xhat + row * k_total + 8 * c) =
+        mx4_frag(q, sc);
+  } else {
+    xq[idx] = q;
+    if (c % 4 == 0) xs[row * (k_total / 32) + c / 4] = (uint8_t)s;
+  }
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
 }  // namespace arks
 
 using namespace arks;
+
+// qdq: write bf16 xhat [M, K]; else xq u8 [M, K/2] and xs u8 [M, K/32].
+extern "C" void arks_mx4_act_quant(void* xq, void* xs, void* xhat,
+                                   const void* x, int m_rows, int k_total,
+                                   int64_t x_stride, bool qdq,
+                                   hipStream_t stream) {
+  const int64_t lanes = (int64_t)m_rows * (k_total / 8);
+  dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+  if (qdq)
+    hipLaunchKernelGGL(mx4_act_quant_kernel<true>, grid, block, 0, stream,
+                       (uint32_t*)nullptr, (uint8_t*)nullptr, (bf16*)xhat,
+                       (const bf16*)x, m_rows, k_total, x_stride);
+  else
+    hipLaunchKernelGGL(mx4_act_quant_kernel<false>, grid, block, 0, stream,
+                       (uint32_t*)xq, (uint8_t*)xs, (bf16*)nullptr,
+                       (const bf16*)x, m_rows, k_total, x_stride);
+}
 
 extern "C" void arks_mx4_skinny_gemm(void* part, void* out, const void* a,
                                      const void* w, const void* scales,

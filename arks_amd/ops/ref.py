@@ -824,6 +824,24 @@ def mx4_linear(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor,
         x, mx4_dequant(packed, scales).to(x.dtype), bias)
 
 
+def mx4_qdq(x: torch.Tensor) -> torch.Tensor:
+    """x [M, K] quantized to MXFP4 along K by mx4_quantize and expanded
+    again, in x's dtype (exact for bf16 and wider): the activations a W4A4
+    layer multiplies."""
+    return mx4_dequant(*mx4_quantize(x)).to(x.dtype)
+
+
+def mx4a4_linear(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor,
+                 bias=None) -> torch.Tensor:
+    """The CPU emulation of a W4A4 MX layer: dynamic MXFP4 activations
+    (mx4_qdq) times the dequantized weight, summed in f32, then the bias and
+    the cast to x's dtype."""
+    y = mx4_qdq(x).float() @ mx4_dequant(packed, scales).t()
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype)
+
+
 POOL_LAST, POOL_MEAN, POOL_CLS = 0, 1, 2
 
 

@@ -321,12 +321,19 @@ def quantize_module_mx4(mod: nn.Module, name: str = "linear") -> None:
 
 
 def _mx4_linear(mod: nn.Module, x, bias, defer: bool):
+    # mx4_act = "mxfp4" (EngineConfig.mx_activations, set by the runner):
+    # the layer's input is quantized to MXFP4 as well (W4A4)
+    a4 = getattr(mod, "mx4_act", "bf16") == "mxfp4"
     if not x.is_cuda:
+        if a4:
+            from ..ops import ref
+
+            x = ref.mx4_qdq(x.reshape(-1, x.shape[-1])).view(x.shape)
         return F.linear(x, mod.weight_qdq, bias)
     from .. import ops
 
-    return ops.mx4_linear(x, (mod.mx4_weight, mod.mx4_scales), bias,
-                          defer=defer)
+    linear = ops.mx4a4_linear if a4 else ops.mx4_linear
+    return linear(x, (mod.mx4_weight, mod.mx4_scales), bias, defer=defer)
 
 
 class LoRAState:

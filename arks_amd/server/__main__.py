@@ -46,6 +46,11 @@ def parse_args(argv=None):
     p.add_argument("--quantize-experts", action="store_true",
                    help="with --quantization int4 on an MoE model: also "
                         "quantize the routed and shared experts")
+    p.add_argument("--mx-activations", choices=["bf16", "mxfp4"],
+                   default="bf16",
+                   help="with MXFP4 weights: mxfp4 also quantizes the layer "
+                        "inputs dynamically to MXFP4 (W4A4, as a Quark MXFP4 "
+                        "export specifies), prefill on the FP4 scaled MFMA")
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--speculative", choices=["ngram", "draft"], default=None,
                    help="speculative decoding: ngram (prompt lookup) or "
@@ -115,6 +120,7 @@ def build_engine_config(args):
         enforce_eager=args.enforce_eager,
         quantization=args.quantization,
         quantize_experts=args.quantize_experts,
+        mx_activations=args.mx_activations,
         kv_cache_dtype=args.kv_cache_dtype,
         speculative=args.speculative,
         draft_model=args.draft_model,

@@ -21,7 +21,16 @@ For M > 64 both MX4 routes are timed next to the one mx4_linear ships for
 that M: the skinny kernel once per 64-row slab (mx4_slab) and dequantize into
 the workspace + library GEMM (mx4_deq).
 
-    python scripts/bench_mx4.py [--rounds 5] [--out results.json]
+--a4 times the W4A4 mode instead, at prefill sizes (A4_MS rows): (a) mx4 =
+ops.mx4_linear, the route a W4A16 layer takes at that M; (b) bf16 = F.linear
+on bf16 weights; (c) quant = the activation quantizer alone; (d) gemm = the
+scaled-MFMA GEMM alone on packed activations, with its achieved FLOP/s
+(2 M N K over the time) and their share of PEAK_FP4; (e) a4 = quantizer +
+MFMA GEMM, what ops.mx4a4_linear runs from MX4A4_MFMA_MIN_M rows; and qdq_mx4
+= the QDQ quantizer + mx4_linear, what it runs below. Same method: graphs,
+weights cycled past the LLC, paths alternating every round.
+
+    python scripts/bench_mx4.py [--rounds 5] [--out results.json] [--a4]
 """
 
 from __future__ import annotations
@@ -45,7 +54,11 @@ SHAPES = {  # name: (N, K)
     "down": (3584, 18944),
 }
 MS = (1, 8, 16, 32, 64, 128, 256)
+A4_MS = (64, 128, 192, 256, 512, 2048, 8192)
 LLC_BYTES = 256 << 20
+# MI355X peak dense MXFP4 matrix rate, from AMD's published product
+# specification of the Instinct MI355X (10.1 PFLOP/s)
+PEAK_FP4 = 10.1e15
 BYTE_RATIO = 1.03  # (0.5 + 1/32) / (0.5 + 3/128)
 
 
@@ -117,11 +130,65 @@ def time_graph(g, ncalls, replays):
     return t0.elapsed_time(t1) * 1e3 / (replays * ncalls)
 
 
+def main_a4(args):
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    rows = []
+    print(f"{'shape':8} {'M':>5} {'path':8} {'us':>10} {'min..max':>21} "
+          f"{'TFLOP/s':>8} {'of peak':>8}")
+    for name in args.shapes.split(","):
+        n, k = SHAPES[name]
+        ncopy = -(-2 * LLC_BYTES // mx4_bytes(n, k))
+        ncopy16 = -(-2 * LLC_BYTES // (n * k * 2))
+        mx4 = [make_mx4(n, k, gen) for _ in range(ncopy)]
+        w16 = [torch.randn(n, k, dtype=torch.bfloat16, device="cuda",
+                           generator=gen) * 0.05 for _ in range(ncopy16)]
+        ops.reserve_dequant_workspace(n * k, "cuda")
+        for m in map(int, args.ms.split(",")):
+            x = torch.randn(m, k, dtype=torch.bfloat16, device="cuda",
+                            generator=gen) * 0.5
+            xq, xs = ops.mx4_quantize_act(x)
+            paths = {
+                "mx4": (lambda w: ops.mx4_linear(x, w), mx4),
+                "bf16": (lambda w: ops.linear_bf16(x, w), w16),
+                "quant": (lambda w: ops.mx4_quantize_act(x), mx4[:1] * 8),
+                "gemm": (lambda w: ops.mx4a4_gemm(xq, xs, w), mx4),
+                "a4": (lambda w: ops.mx4a4_gemm(*ops.mx4_quantize_act(x), w),
+                       mx4),
+                "qdq_mx4": (lambda w: ops.mx4_linear(
+                    ops.mx4_quantize_act(x, qdq=True), w), mx4),
+            }
+            graphs = {p: capture(fn, ws) for p, (fn, ws) in paths.items()}
+            res = {p: [] for p in paths}
+            for _ in range(args.rounds):  # alternate the paths every round
+                for p, (fn, ws) in paths.items():
+                    res[p].append(time_graph(graphs[p], len(ws),
+                                             max(3, 60 // len(ws))))
+            for p, ts in res.items():
+                med = statistics.median(ts)
+                flops = 2 * m * n * k / (med * 1e-6) if p == "gemm" else None
+                tail = (f"{flops / 1e12:8.0f} {flops / PEAK_FP4:8.1%}"
+                        if flops else "")
+                print(f"{name:8} {m:5d} {p:8} {med:10.1f} "
+                      f"{min(ts):10.1f}..{max(ts):<10.1f}{tail}", flush=True)
+                rows.append({"shape": name, "N": n, "K": k, "M": m, "path": p,
+                             "us_median": med, "us_min": min(ts),
+                             "us_max": max(ts), "flops": flops,
+                             "rounds": len(ts)})
+            del graphs
+        del mx4, w16
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shapes", default=",".join(SHAPES))
-    ap.add_argument("--ms", default=",".join(map(str, MS)))
+    ap.add_argument("--ms", default=None)
+    ap.add_argument("--a4", action="store_true",
+                    help="time the W4A4 mode at prefill sizes instead")
     ap.add_argument("--eager", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -129,6 +196,9 @@ def main():
         sys.exit("bench_mx4 needs a GPU and the built extension")
     if args.rounds < 3:
         sys.exit("the W4 spread needs at least three rounds")
+    args.ms = args.ms or ",".join(map(str, A4_MS if args.a4 else MS))
+    if args.a4:
+        return main_a4(args)
     gen = torch.Generator(device="cuda").manual_seed(0)
     modes = ("eager", "graph") if args.eager else ("graph",)
     rows = []

@@ -14,7 +14,13 @@ kv_blocks_at_0.90 is the pool the engine would size by itself at the default
 gpu_memory_utilization: the run's own (small, fixed) pool is added back to
 the free memory that profile_num_blocks sees.
 
+--prefill-len L adds a third engine, mxfp4 weights with
+mx_activations="mxfp4" (W4A4), and reports for every engine the time of one
+prefill of an L-token prompt (one warm-up prompt first; host clock around a
+device synchronise).
+
     python scripts/bench_mx4_engine.py [--model qwen2.5-7b] [--out r.json]
+                                       [--prefill-len 2048]
 """
 
 from __future__ import annotations
@@ -47,8 +53,8 @@ def weight_bytes(mc, mx4: bool) -> int:
     return mc.num_hidden_layers * per_layer + mc.vocab_size * H * 2
 
 
-def build(args, mx4: bool):
-    horizon = args.input_len + args.warmup + args.steps + 128
+def build(args, mx4: bool, a4: bool = False):
+    horizon = max(args.input_len, args.prefill_len) + args.warmup + args.steps + 128
     top = max(args.batches)
     return LLMEngine(EngineConfig(
         preset=args.model, device=args.device, max_num_seqs=max(top, 256),
@@ -56,7 +62,26 @@ def build(args, mx4: bool):
         max_model_len=horizon,
         kv_cache_blocks=(top * horizon + 15) // 16 + 64, seed=args.seed,
         quantization="mxfp4" if mx4 else None,
+        mx_activations="mxfp4" if a4 else "bf16",
     ))
+
+
+def prefill_ms(engine, args) -> float:
+    g = torch.Generator().manual_seed(args.seed + 1)
+    sync = torch.cuda.synchronize if args.device == "cuda" else (lambda: None)
+    for tag in ("warm", "timed"):
+        prompt = torch.randint(0, engine.model_cfg.vocab_size - 1,
+                               (args.prefill_len,), generator=g).tolist()
+        engine.add_request(prompt, SamplingParams(max_tokens=1,
+                                                  ignore_eos=True),
+                           request_id=f"prefill-{tag}")
+        sync()
+        t0 = time.time()
+        while engine.has_work():
+            engine.step()
+        sync()
+        ms = (time.time() - t0) * 1e3
+    return ms
 
 
 def kv_blocks_at_default(engine) -> int | None:
@@ -106,6 +131,7 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--prefill-len", type=int, default=0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda",
                     help="cpu only rehearses the script; its times mean nothing")
@@ -115,14 +141,24 @@ def main():
         sys.exit("bench_mx4_engine needs a GPU")
     result = {"model": args.model, "input_len": args.input_len,
               "steps": args.steps, "runs": []}
-    for mx4 in (False, True):
-        engine = build(args, mx4)
+    modes = [(False, False), (True, False)]
+    if args.prefill_len:
+        modes.append((True, True))
+    for mx4, a4 in modes:
+        engine = build(args, mx4, a4)
         mod = engine.runner.model.layers[0].mlp.down_proj
         assert bool(getattr(mod, "mx4", False)) == mx4
         engine.generate([[1, 2, 3] * 16, [4, 5] * 8],
                         SamplingParams(max_tokens=4, ignore_eos=True))
         blocks = kv_blocks_at_default(engine)
-        for batch in args.batches:
+        if args.prefill_len:
+            row = {"weights": "mxfp4" if mx4 else "bf16",
+                   "activations": "mxfp4" if a4 else "bf16",
+                   "prefill_len": args.prefill_len,
+                   "prefill_ms": round(prefill_ms(engine, args), 2)}
+            print(json.dumps(row), flush=True)
+            result["runs"].append(row)
+        for batch in ([] if a4 else args.batches):
             ms = decode_ms(engine, args, batch)
             wb = weight_bytes(engine.model_cfg, mx4)
             row = {"weights": "mxfp4" if mx4 else "bf16", "batch": batch,
