@@ -113,7 +113,9 @@ class ModelRunner:
         mx4_ckpt = (self.quantization == "mxfp4"
                     and self.model_cfg.quant_method == "mxfp4")
         if mx4_ckpt:
-            self.model.prepare_mxfp4_checkpoint()
+            # the routed experts stay MX4 where the grouped kernels run
+            self.model.prepare_mxfp4_checkpoint(
+                experts=self.device.type == "cuda")
         if self.cfg.model_path:
             from ..loader.safetensors_loader import load_model_weights
 
@@ -147,8 +149,9 @@ class ModelRunner:
         elif self.quantization is not None:
             raise ValueError(f"unknown quantization {self.quantization!r}")
         if self.cfg.mx_activations == "mxfp4":
-            # W4A4: every MX4 layer quantizes its input too (lm_head, experts
-            # and excluded modules are not MX4 modules)
+            # W4A4: every MX4 layer and every MoE block with MX4 experts
+            # quantizes its input too (lm_head, bf16 experts and excluded
+            # modules are not MX4 modules)
             for mod in self.model.modules():
                 if getattr(mod, "mx4", False):
                     mod.mx4_act = "mxfp4"

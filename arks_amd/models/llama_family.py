@@ -287,7 +287,7 @@ class MoEMLP(nn.Module):
     def bf16_routed_supported(self) -> bool:
         """What moe_bf16_gemm_kernel needs of both expert GEMMs (w13: K = H,
         N = 2I; w2: K = I, N = H)."""
-        return (not self.w4 and not self.w8
+        return (not self.w4 and not self.w8 and not self.mx4
                 and ops.moe_bf16_supported(self.hidden, 2 * self.inter)
                 and ops.moe_bf16_supported(self.inter, self.hidden))
 
@@ -579,10 +579,183 @@ class MoEMLP(nn.Module):
         del bf16
         self.finalize_w8(name)
 
+    # ---- MX4 experts (MXFP4 checkpoints, quantize_mx4) ----
+    # The checkpoint's nibbles and e8m0 scale bytes stacked per local expert,
+    # ops/ref.py's MX4 format with a leading expert dimension: w13_mx4
+    # [E, 2I, H/2] is [gate | up] along N with w13_mx4_scales [E, 2I, H/32];
+    # w2_mx4 [E, H, I/2] with w2_mx4_scales [E, H, I/32]: E*3*I*H*(1/2 + 1/32)
+    # bytes. The bf16 w13 / w2 parameters are dropped. On CPU the W4 / W8
+    # convention holds: bf16 [E, in, out] buffers named w13 / w2 (the exact
+    # dequantized values) stand in and the bf16 forward runs on them; on GPU
+    # an MX4 block has no bf16 copy of its experts.
+    mx4 = False
+    # "mxfp4" (EngineConfig.mx_activations, set by the runner on every module
+    # with mx4 true): the inputs of both expert GEMMs are MXFP4 too
+    mx4_act = "bf16"
+    # With MXFP4 activations, batches above this many tokens run both expert
+    # GEMMs on the scaled MFMA (ops.mx4a4_moe_gemm); up to it the activations
+    # are quantized and expanded again and the streaming kernel runs on them.
+    # It is DENSE_TOKENS, from where _forward_routed syncs for the longest
+    # list anyway. The crossover itself is NOT located: measured with
+    # scripts/bench_mx4_moe.py on an MI355X (whole block, eager us, MFMA vs
+    # streaming; profiles/mx4_moe.md) only above it, where the MFMA route
+    # wins on both shapes: T=512 qwen3-30b-a3b 162 vs 187, mixtral-8x7b 427
+    # vs 761; T=2048 304 vs 390, 1126 vs 2479. 257..511, and the MFMA route
+    # at T <= 256, were not measured.
+    MX4A4_MFMA_TOKENS = DENSE_TOKENS
+
+    def mx4_supported(self) -> bool:
+        """What the routed MX4 kernels need of both expert GEMMs: K a
+        multiple of 128 (N = 2I and H are then multiples of 64)."""
+        return self.hidden % 128 == 0 and self.inter % 128 == 0
+
+    def mx4_weight(self, which: str):
+        return (getattr(self, f"{which}_mx4"),
+                getattr(self, f"{which}_mx4_scales"))
+
+    def init_mx4(self, name: str = "moe") -> None:
+        """Switch to (empty) MX4 storage; the bf16 parameters are dropped, so
+        a block switched before its weights stream in never holds them."""
+        from ..ops import ref
+
+        if not self.mx4_supported():
+            raise ValueError(
+                f"{name}: MoE expert width {self.inter} is not supported: "
+                f"MX4 experts need hidden and expert widths that are "
+                f"multiples of 128, got hidden={self.hidden}, expert "
+                f"width={self.inter}")
+        dev = self.w13.device
+        E, H, I = self.local_experts, self.hidden, self.inter
+        del self._parameters["w13"]
+        del self._parameters["w2"]
+        for which, (N, K) in (("w13", (2 * I, H)), ("w2", (H, I))):
+            self.register_buffer(
+                f"{which}_mx4",
+                torch.zeros(E, N, K // 2, dtype=torch.uint8, device=dev),
+                persistent=False)
+            self.register_buffer(
+                f"{which}_mx4_scales",
+                torch.full((E, N, K // ref.MX4_BLOCK), 127,
+                           dtype=torch.uint8, device=dev),
+                persistent=False)
+        self.mx4 = True
+        self._mx4_got = set()   # (local expert, projection, kind) arrived
+        self._mx4_names = {}    # projection -> (checkpoint prefix, leaf)
+
+    def load_mx4_expert(self, name: str, le: int, proj: str, kind: str,
+                        t: torch.Tensor) -> None:
+        """One MXFP4 tensor (kind: weight / weight_scale, both uint8 with one
+        row per output channel) of local expert le's gate / up / down
+        projection into the stacked buffers, as a byte copy: gate fills rows
+        [0, I) of w13, up rows [I, 2I). Each tensor lands on its own; the
+        caller has checked the scale bytes' range."""
+        from ..ops import ref
+
+        H, I = self.hidden, self.inter
+        which, r0, N, K = {"gate": ("w13", 0, I, H), "up": ("w13", I, I, H),
+                           "down": ("w2", 0, H, I)}[proj]
+        div = {"weight": 2, "weight_scale": ref.MX4_BLOCK}.get(kind)
+        if div is None:
+            raise ValueError(f"{name}: unexpected tensor kind {kind!r} for "
+                             "an MXFP4 expert")
+        if t.dtype != torch.uint8 or tuple(t.shape) != (N, K // div):
+            raise ValueError(
+                f"{name}: {tuple(t.shape)} {t.dtype}, expected uint8 "
+                f"{(N, K // div)} for a {N}x{K} projection ([N, K/{div}] "
+                "bytes)")
+        self.mx4_weight(which)[kind == "weight_scale"][le, r0:r0 + N].copy_(t)
+        self._mx4_got.add((le, proj, kind))
+        head, sep, _ = name.rpartition(".experts.")
+        if sep and proj not in self._mx4_names:
+            self._mx4_names[proj] = (head, name.split(".")[-2])
+
+    def finalize_mx4(self, name: str = "moe") -> None:
+        """After loading: every (local expert, projection, kind) must have
+        arrived. On CPU keep the bf16 dequantized experts that the bf16
+        forward runs on."""
+        from ..ops import ref
+
+        got = getattr(self, "_mx4_got", None)
+        if got is not None:
+            style = 0
+            if self._mx4_names:
+                style = 1 if next(iter(self._mx4_names.values()))[1] in (
+                    "w1", "w2", "w3") else 0
+            for le in range(self.local_experts):
+                for proj, leaves in self._W8_PROJS.items():
+                    for kind in ("weight", "weight_scale"):
+                        if (le, proj, kind) in got:
+                            continue
+                        head, leaf = self._mx4_names.get(
+                            proj, (f"{name}", leaves[style]))
+                        raise ValueError(
+                            f"{head}.experts.{self.expert_base + le}.{leaf}."
+                            f"{kind}: missing from the checkpoint for the "
+                            f"MXFP4 experts of {name}")
+            self._mx4_got = None
+        if self.w13_mx4.is_cuda:
+            return
+        for which in ("w13", "w2"):
+            w, sc = self.mx4_weight(which)
+            deq = torch.stack([
+                ref.mx4_dequant(w[e], sc[e]).to(torch.bfloat16).t()
+                for e in range(self.local_experts)
+            ]).contiguous()
+            if which in self._buffers:
+                del self._buffers[which]
+            self.register_buffer(which, deq, persistent=False)
+
+    def quantize_mx4(self, name: str = "moe") -> None:
+        """MX4 of loaded bf16 experts by the OCP conversion rule, one expert
+        at a time (ops.ref.mx4_quantize). For tests and the bench script."""
+        from ..ops import ref
+
+        bf16 = {"w13": self.w13.data, "w2": self.w2.data}
+        self.init_mx4(name)
+        self._mx4_got = None     # filled here, nothing streams in
+        I = self.inter
+        for which, full in bf16.items():
+            w, sc = self.mx4_weight(which)
+            for e in range(self.local_experts):
+                # stored [in, out]; the quantizer takes [N, K] = [out, in].
+                # gate and up are separate tensors in a checkpoint (the
+                # blocks run along K, so the split changes no value).
+                rows = full[e].t()
+                parts = ((0, rows[:I]), (I, rows[I:])) if which == "w13" \
+                    else ((0, rows),)
+                for r0, part in parts:
+                    q, s = ref.mx4_quantize(part)
+                    w[e, r0:r0 + part.shape[0]].copy_(q)
+                    sc[e, r0:r0 + part.shape[0]].copy_(s)
+        del bf16
+        self.finalize_mx4(name)
+
+    def _forward_mx4(self, x):
+        """GPU forward of an MX4 block: _forward_routed over
+        ops.mx4_moe_gemm. With MXFP4 activations x is quantized once for the
+        w13 GEMM and h once, after silu_mul, for the w2 GEMM: up to
+        MX4A4_MFMA_TOKENS into the bf16 values the codes expand to, for the
+        streaming kernel; above it into packed codes for the scaled MFMA.
+        Both routes sum the same exact products in f32, so crossing the
+        boundary changes the summation order only."""
+        if self.mx4_act != "mxfp4":
+            gemm = ops.mx4_moe_gemm
+        elif x.shape[0] <= self.MX4A4_MFMA_TOKENS:
+            def gemm(a, *args, **kw):
+                return ops.mx4_moe_gemm(ops.mx4_quantize_act(a, qdq=True),
+                                        *args, **kw)
+        else:
+            def gemm(a, *args, **kw):
+                return ops.mx4a4_moe_gemm(*ops.mx4_quantize_act(a), *args,
+                                          **kw)
+        return self._forward_routed(x, gemm, self.mx4_weight("w13"),
+                                    self.mx4_weight("w2"))
+
     def _forward_routed(self, x, gemm, w13, w2):
         """GPU forward over routed experts (gemm = ops.w4_moe_gemm on the
-        packed W4 triples, ops.w8_moe_gemm on the W8 pairs, ops.moe_bf16_gemm
-        on the bf16 parameters themselves), the same for every T: route once, then two routed grouped GEMMs that stream only
+        packed W4 triples, ops.w8_moe_gemm on the W8 pairs, ops.mx4_moe_gemm
+        or ops.mx4a4_moe_gemm on the MX4 pairs, ops.moe_bf16_gemm on the
+        bf16 parameters themselves), the same for every T: route once, then two routed grouped GEMMs that stream only
         the experts the batch selected. Up to DENSE_TOKENS the launch shapes depend on T alone (no
         host sync; the decode graphs capture it); above it one sync per layer
         fetches the longest expert list to size the grid."""
@@ -627,6 +800,8 @@ class MoEMLP(nn.Module):
             return self._forward_routed(x, ops.w8_moe_gemm,
                                         self.w8_weight("w13"),
                                         self.w8_weight("w2"))
+        if self.mx4 and x.is_cuda:
+            return self._forward_mx4(x)
         T = x.shape[0]
         if (x.is_cuda and T <= self.ROUTED_BF16_TOKENS
                 and self.bf16_routed_supported()):
@@ -1110,7 +1285,7 @@ class LlamaFamilyForCausalLM(nn.Module):
             le = int(parts[4]) - layer.mlp.expert_base
             if not 0 <= le < layer.mlp.local_experts:
                 return None, stem, None, "skip"
-            if layer.mlp.w8 and parts[5] in (
+            if (layer.mlp.w8 or layer.mlp.mx4) and parts[5] in (
                     "gate_proj", "up_proj", "down_proj", "w1", "w3", "w2"):
                 return layer.mlp, stem, None, "expert"
             return None, stem, None, "dequant"
@@ -1282,8 +1457,11 @@ class LlamaFamilyForCausalLM(nn.Module):
     # ---- MXFP4 checkpoints (MX4, W4A16; format in ops/ref.py) ----
     # X.weight u8 [N, K/2] + X.weight_scale u8 [N, K/32] per quantized
     # projection, as a Quark MXFP4 export stores them. The candidate layers
-    # are _w4_targets(experts=True); routed experts (no grouped MX4 kernel)
-    # and a quantized lm_head are dequantized to bf16 at load.
+    # are _w4_targets(experts=True) plus, on a GPU, the routed experts of
+    # every MoE block, which keep their nibbles and scale bytes stacked for
+    # the grouped MX4 kernels (MoEMLP init_mx4). A block whose widths those
+    # kernels cannot take, or with experts on the exclude list, is
+    # dequantized to bf16 at load, as is a quantized lm_head.
     _MX4_KINDS = ("weight", "weight_scale")
 
     def _mx4_skipped(self, hf_name: str) -> bool:
@@ -1308,12 +1486,17 @@ class LlamaFamilyForCausalLM(nn.Module):
         for name, mod in self._w4_targets():
             quantize_module_mx4(mod, name)
 
-    def prepare_mxfp4_checkpoint(self) -> None:
+    def prepare_mxfp4_checkpoint(self, experts: bool | None = None) -> None:
         """Switch the quantized layers to (empty) MX4 storage BEFORE an MXFP4
         checkpoint streams in, so their bf16 weights are never allocated on
         the device; finalize_mx4() completes the switch after loading. The
         parts of a fused projection must all be quantized or all be on the
-        checkpoint's exclude list."""
+        checkpoint's exclude list.
+        experts: keep the routed experts of an MoE block in MX4 too, when
+        none of them is excluded and the block's widths pass
+        MoEMLP.mx4_supported(); any other block is dequantized to bf16 as its
+        tensors arrive. None means "the model is on a GPU": the grouped
+        kernels run there only, so a CPU model keeps bf16 experts."""
         from ..parallel.layers import init_module_mx4
 
         self._mx4_pending = {}
@@ -1331,6 +1514,13 @@ class LlamaFamilyForCausalLM(nn.Module):
                     "in bf16); they must all be MXFP4 or all excluded")
             init_module_mx4(mod, name)
             mod._mx4_got = set()
+        if experts is None:
+            experts = self.embed_tokens.weight.is_cuda
+        for name, moe in self._moe_blocks():
+            names = self._w8_expert_hf_names(name, moe)
+            if (experts and moe.mx4_supported()
+                    and not any(self._mx4_skipped(p) for p in names)):
+                moe.init_mx4(name)
 
     def finalize_mx4(self) -> None:
         from ..parallel.layers import finalize_module_mx4
@@ -1357,6 +1547,15 @@ class LlamaFamilyForCausalLM(nn.Module):
                     f"{name}: the checkpoint has no {sorted(missing)} for "
                     "this MXFP4 layer")
             finalize_module_mx4(mod)
+        dropped = False
+        for name, moe in self._moe_blocks():
+            if moe.mx4:
+                moe.finalize_mx4(name)
+                dropped = dropped or moe.w13_mx4.is_cuda
+        if dropped:
+            # the dropped bf16 experts sit in the caching allocator; hand
+            # them back so profile_num_blocks sees them as free
+            torch.cuda.empty_cache()
 
     def _route_mx4(self, full_name: str, w: torch.Tensor) -> bool:
         """Takes the tensors of an MXFP4 checkpoint (uint8 weights and their
@@ -1406,7 +1605,14 @@ class LlamaFamilyForCausalLM(nn.Module):
                     f"outside the supported [{ref.MX4_SCALE_MIN}, "
                     f"{ref.MX4_SCALE_MAX}] (0.5 * 2^(s-127) must be a normal "
                     "bf16 and 6 * 2^(s-127) finite; 255 is NaN)")
-        if how in ("dequant", "expert"):
+        if how == "expert":
+            parts = stem.split(".")
+            proj = {"gate_proj": "gate", "up_proj": "up", "down_proj": "down",
+                    "w1": "gate", "w3": "up", "w2": "down"}[parts[5]]
+            mod.load_mx4_expert(full_name, int(parts[4]) - mod.expert_base,
+                                proj, kind, w)
+            return True
+        if how == "dequant":
             self._mx4_dequant_load(full_name, stem, kind, w)
             return True
         if not getattr(mod, "mx4", False):
@@ -1481,10 +1687,15 @@ class LlamaFamilyForCausalLM(nn.Module):
         del self._mx4_pending[("dequant", stem)]
         if stem != "lm_head" and not self._mx4_experts_logged:
             self._mx4_experts_logged = True
+            mlp = self.layers[int(stem.split(".")[1])].mlp
+            why = ("the grouped MX4 kernels run on the GPU only, and only "
+                   "for blocks without excluded experts"
+                   if mlp.mx4_supported() else
+                   f"hidden={mlp.hidden}, expert width={mlp.inter}: the "
+                   "grouped MX4 kernels need multiples of 128")
             logging.getLogger(__name__).warning(
-                "MXFP4 routed experts are dequantized to bf16 at load (no "
-                "grouped MX4 kernel): the model holds its experts at bf16 "
-                "size")
+                "MXFP4 routed experts are dequantized to bf16 at load (%s): "
+                "the model holds these experts at bf16 size", why)
         dev = self.embed_tokens.weight.device
         plain = ref.mx4_dequant(pair["weight"].to(dev),
                                 pair["weight_scale"].to(dev)).to(self.dtype)

@@ -1054,6 +1054,77 @@ def w8_moe_gemm(a, weight, counts, pairs, src_div: int, max_rows: int,
     return out
 
 
+def mx4_moe_supported(K: int, N: int) -> bool:
+    """Whether mx4_moe_gemm_kernel and mx4_moe_mfma_gemm_kernel take an
+    expert GEMM with K inputs and N outputs: 64-row N tiles (the MFMA kernel
+    pads its 128-column tile by whole waves of 64) and 128-wide K chunks."""
+    return K >= 128 and K % 128 == 0 and N >= 64 and N % 64 == 0
+
+
+def _mx4_moe_out(rows: int, src_div: int, weight, pairs, out, device):
+    T = pairs.shape[1] if pairs.dim() == 2 else 0
+    top_k = rows * src_div // max(T, 1)
+    if out is None:
+        out = torch.empty((T * top_k, weight[0].shape[1]),
+                          dtype=torch.bfloat16, device=device)
+    return top_k, out
+
+
+def mx4_moe_gemm(a, weight, counts, pairs, src_div: int, max_rows: int,
+                 out=None):
+    """Routed grouped W4A16 MX GEMM over the stacked local experts of an MoE
+    block (mx4_moe_gemm_kernel): w4_moe_gemm for weight = (mx4 u8
+    [E, N, K/2], scales u8 [E, N, K/32]), the tensors of an MXFP4 checkpoint
+    stacked per expert:
+    out[p] = a[p // src_div] @ dequant(mx4[e], scales[e])^T for every local
+    expert e and p in pairs[e][:counts[e]]. Same arguments, same capture
+    rules, and no eager fallback on GPU either: a shape outside
+    mx4_moe_supported raises."""
+    if not a.is_cuda:
+        return ref.mx4_moe_gemm(a, weight, counts, pairs, src_div, out=out)
+    top_k, out = _mx4_moe_out(a.shape[0], src_div, weight, pairs, out,
+                              a.device)
+    if not a.is_contiguous() or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    _native().mx4_moe_gemm(out, a, *weight, counts, pairs, top_k, src_div,
+                           max_rows)
+    return out
+
+
+def mx4a4_moe_gemm(xq, xs, weight, counts, pairs, src_div: int,
+                   max_rows: int, out=None, mtile: int | None = None):
+    """mx4_moe_gemm with MXFP4 activations (xq u8 [rows, K/2], xs u8
+    [rows, K/32] from mx4_quantize_act) on the block-scaled FP4 matrix
+    instruction (mx4_moe_mfma_gemm_kernel), for prefill-sized batches:
+    out[p] = dq(xq, xs)[p // src_div] @ dequant(mx4[e], scales[e])^T, f32
+    accumulation, one rounding to bf16. The grid is (ceil(N/128), E_local,
+    ceil(max_rows/mtile)): workgroups take 64 rows of an expert's list, or 128
+    once max_rows >= 128 and the 128-row grid still has
+    _MX4A4_TILE128_MIN_WGS workgroups: a starting rule from the grid sizes,
+    not a located crossover. MEASURED with scripts/bench_mx4_moe.py on an
+    MI355X (whole block, eager us, 64 vs 128 rows; profiles/mx4_moe.md):
+    mixtral-8x7b T=512 511 vs 427, T=2048 1555 vs 1126 (the rule picks 128);
+    qwen3-30b-a3b T=512 163 vs 162 (it picks 64), T=2048 304 vs 312 (it picks
+    128, 2.7% slower). mtile is for tests only and forces either.
+    Same table arguments and capture rules as w4_moe_gemm. On CPU:
+    ref.mx4a4_moe_gemm."""
+    if mtile not in (None, 64, 128):
+        raise ValueError(f"mtile must be 64 or 128, got {mtile}")
+    if not xq.is_cuda:
+        return ref.mx4a4_moe_gemm(xq, xs, weight, counts, pairs, src_div,
+                                  out=out)
+    top_k, out = _mx4_moe_out(xq.shape[0], src_div, weight, pairs, out,
+                              xq.device)
+    if mtile is None:
+        E, N = weight[0].shape[0], weight[0].shape[1]
+        wgs = -(-N // 128) * E * -(-max_rows // 128)
+        mtile = (128 if max_rows >= 128 and wgs >= _MX4A4_TILE128_MIN_WGS
+                 else 64)
+    _native().mx4a4_moe_gemm(out, xq, xs, *weight, counts, pairs, top_k,
+                             src_div, max_rows, mtile)
+    return out
+
+
 def moe_bf16_supported(K: int, N: int) -> bool:
     """Whether moe_bf16_gemm_kernel takes an expert GEMM with K inputs and N
     outputs: its N tile is 128 columns wide and it walks K in chunks of 64."""

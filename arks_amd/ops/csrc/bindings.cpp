@@ -5,6 +5,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -190,6 +191,16 @@ void arks_mx4_mfma_gemm(void* out, const void* xq, const void* xs,
                         const void* w, const void* ws, const void* bias,
                         int m_rows, int n_total, int k_total, int mtile,
                         hipStream_t stream);
+void arks_mx4_moe_gemm(void* out, const void* a, const void* w,
+                       const void* scales, const void* counts,
+                       const void* pairs, int n_experts, int t_cols,
+                       int n_pairs, int src_div, int slabs, int n_total,
+                       int k_total, int nw, hipStream_t stream);
+void arks_mx4_moe_mfma_gemm(void* out, const void* xq, const void* xs,
+                            const void* w, const void* ws, const void* counts,
+                            const void* pairs, int n_experts, int t_cols,
+                            int n_pairs, int src_div, int slabs, int n_total,
+                            int k_total, int mtile, hipStream_t stream);
 void arks_moe_route(void* counts, void* pairs, const void* ids, int n_pairs,
                     int T, int expert_base, int n_local, hipStream_t stream);
 void arks_mfma_probe(void* d, const void* a, const void* b, hipStream_t stream);
@@ -1012,6 +1023,104 @@ void w8_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w8,
                    (int)slabs, (int)n, (int)k, nw, current_stream());
 }
 
+// What the two routed MX4 GEMMs share: the stacked experts w u8 [E, N, K/2]
+// and scales u8 [E, N, K/32], the routing table, and out bf16 [T*k, N] over
+// src_rows >= ceil(T*k / src_div) activation rows. Returns (E, N, K, T).
+std::array<int64_t, 4> check_mx4_moe(const torch::Tensor& out,
+                                     const torch::Tensor& w,
+                                     const torch::Tensor& scales,
+                                     const torch::Tensor& counts,
+                                     const torch::Tensor& pairs,
+                                     int64_t top_k, int64_t src_div,
+                                     int64_t max_rows, int64_t src_rows) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kUInt8 &&
+              w.dim() == 3 && w.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "mx4 weight must be contiguous uint8 [E, N, K/2] on GPU");
+  const int64_t ne = w.size(0), n = w.size(1), k = w.size(2) * 2;
+  TORCH_CHECK(ne >= 1 && ne <= 65535, "need 1 <= E_local <= 65535");
+  TORCH_CHECK(k >= 128 && k % 128 == 0, "MX4 needs K % 128 == 0, got K=", k);
+  TORCH_CHECK(n >= 64 && n % 64 == 0, "MX4 needs N % 64 == 0, got N=", n);
+  TORCH_CHECK(n * (k / 2) < ((int64_t)1 << 31), "expert weight too large");
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kUInt8 &&
+              scales.is_contiguous() && scales.dim() == 3 &&
+              scales.size(0) == ne && scales.size(1) == n &&
+              scales.size(2) == k / 32 &&
+              reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0,
+              "mx4 scales must be contiguous uint8 [E, N, K/32] on GPU");
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == torch::kInt32 &&
+              counts.is_contiguous() && counts.dim() == 1 &&
+              counts.size(0) == ne, "counts must be int32 [E_local] on GPU");
+  TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt32 &&
+              pairs.is_contiguous() && pairs.dim() == 2 &&
+              pairs.size(0) == ne && pairs.size(1) >= 1,
+              "pairs must be int32 [E_local, T] on GPU, got ", pairs.sizes());
+  const int64_t t_cols = pairs.size(1);
+  TORCH_CHECK(top_k >= 1, "top_k must be >= 1");
+  const int64_t n_pairs = t_cols * top_k;
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == n && out.size(0) == n_pairs &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "out must be [T*k, N] = [", n_pairs, ", ", n, "], got ",
+              out.sizes());
+  TORCH_CHECK(n_pairs < ((int64_t)1 << 31) / 2);
+  TORCH_CHECK(src_div >= 1 && src_rows * src_div >= n_pairs,
+              "the activations have ", src_rows, " rows, too few for ",
+              n_pairs, " pairs at src_div=", src_div);
+  TORCH_CHECK(max_rows >= 1 && max_rows <= t_cols,
+              "need 1 <= max_rows <= T, got ", max_rows);
+  const auto dev = w.device();
+  TORCH_CHECK(scales.device() == dev && out.device() == dev &&
+              counts.device() == dev && pairs.device() == dev);
+  return {ne, n, k, t_cols};
+}
+
+// w4_moe_gemm over stacked MX4 experts (mx4_moe_gemm_kernel): bf16
+// activations, the checkpoint's nibbles and scale bytes.
+void mx4_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
+                  torch::Tensor scales, torch::Tensor counts,
+                  torch::Tensor pairs, int64_t top_k, int64_t src_div,
+                  int64_t max_rows) {
+  check_bf16_contig(a, "a");
+  TORCH_CHECK(a.dim() == 2, "a must be [rows, K]");
+  const auto [ne, n, k, t_cols] = check_mx4_moe(
+      out, w, scales, counts, pairs, top_k, src_div, max_rows, a.size(0));
+  TORCH_CHECK(a.size(1) == k, "a must be [rows, K]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0 &&
+              a.device() == w.device(),
+              "a rows must be 16-byte aligned, on the weight's GPU");
+  const int64_t slabs = (max_rows + 63) / 64;
+  TORCH_CHECK(slabs <= 65535, "max_rows too large");
+  const int nw = (max_rows > 32 && n % 128 == 0) ? 2 : 1;  // as w4_moe_gemm
+  arks_mx4_moe_gemm(out.data_ptr(), a.data_ptr(), w.data_ptr(),
+                    scales.data_ptr(), counts.data_ptr(), pairs.data_ptr(),
+                    (int)ne, (int)t_cols, (int)(t_cols * top_k), (int)src_div,
+                    (int)slabs, (int)n, (int)k, nw, current_stream());
+}
+
+// The same with MXFP4 activations xq u8 [rows, K/2], xs u8 [rows, K/32] on
+// the scaled MFMA (mx4_moe_mfma_gemm_kernel). mtile = 128 or 64 rows of an
+// expert's list per workgroup.
+void mx4a4_moe_gemm(torch::Tensor out, torch::Tensor xq, torch::Tensor xs,
+                    torch::Tensor w, torch::Tensor scales,
+                    torch::Tensor counts, torch::Tensor pairs, int64_t top_k,
+                    int64_t src_div, int64_t max_rows, int64_t mtile) {
+  TORCH_CHECK(mtile == 128 || mtile == 64, "mtile must be 128 or 64");
+  const int64_t m = xq.dim() == 2 ? xq.size(0) : 0;
+  const auto [ne, n, k, t_cols] = check_mx4_moe(
+      out, w, scales, counts, pairs, top_k, src_div, max_rows, m);
+  check_mx4_act_packed(xq, xs, m, k, w.device());
+  // the kernel gathers rows of xq by 32-bit byte offsets
+  TORCH_CHECK(m * (k / 2) < ((int64_t)1 << 32), "xq too large");
+  const int64_t slabs = (max_rows + mtile - 1) / mtile;
+  TORCH_CHECK(slabs <= 65535, "max_rows too large");
+  arks_mx4_moe_mfma_gemm(out.data_ptr(), xq.data_ptr(), xs.data_ptr(),
+                         w.data_ptr(), scales.data_ptr(), counts.data_ptr(),
+                         pairs.data_ptr(), (int)ne, (int)t_cols,
+                         (int)(t_cols * top_k), (int)src_div, (int)slabs,
+                         (int)n, (int)k, (int)mtile, current_stream());
+}
+
 // The same over stacked bf16 experts as the model holds them
 // (moe_bf16_gemm_kernel, moe_gemm.hip): w bf16 [E, K, N], N contiguous.
 void moe_bf16_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
@@ -1675,6 +1784,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx4_act_quant", &mx4_act_quant);
   m.def("mx4_act_qdq", &mx4_act_qdq);
   m.def("mx4a4_gemm", &mx4a4_gemm);
+  m.def("mx4_moe_gemm", &mx4_moe_gemm);
+  m.def("mx4a4_moe_gemm", &mx4a4_moe_gemm);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache, py::arg("positions"),
         py::arg("part"), py::arg("bias"), py::arg("q_out"), py::arg("k_cache"),

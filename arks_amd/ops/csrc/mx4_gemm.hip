@@ -38,8 +38,15 @@
 // FP4 is mx4_mfma_gemm.hip. The kernels of this file keep bf16 activations:
 // decode is bound by the weight bytes.
 //
-// Not here: a routed grouped expert GEMM (MX4 routed experts are dequantized
-// to bf16 at load).
+// mx4_moe_gemm_kernel is the same chunk loop over the stacked experts of an
+// MoE block ([E, N, K/2] / [E, N, K/32]), its rows gathered and scattered
+// through the routing table that moe_route_kernel (moe.hip) writes; comment
+// at the kernel. Its prefill-sized W4A4 counterpart on the scaled MFMA is
+// mx4_moe_mfma_gemm_kernel (mx4_mfma_gemm.hip).
+//
+// Not here: a W4A16 MFMA kernel for prefill-sized batches with bf16
+// activations (the routed kernel runs them slab by slab, the dense layers
+// expand the weight for the library GEMM).
 #include "wq_stream.h"
 
 namespace arks {
@@ -140,6 +147,60 @@ __global__ __launch_bounds__(256) void mx4_skinny_gemm_kernel(
       ln, Mx4Weights<NW>(ln, w, scales, k_total),
       WqDenseRows<MT>{part, out, a, bias, m_rows, nsplits, a_stride}, n_total,
       k_total, k_per_split);
+}
+
+// Routed grouped W4A16 MX GEMM over the local experts of an MoE block:
+//   for e < E_local, i < counts[e], p = pairs[e][i]:
+//     out[p, :] = a[p / src_div, :] @ dequant(w[e], scales[e])^T
+// w8_moe_gemm_kernel (w8_gemm.hip; the notes are at w4_moe_gemm_kernel) with
+// Mx4Weights: the same grid = (N/(64*NW), E_local, slabs), a function of (N,
+// E_local, max_rows) only, so a decode batch captures into a graph; the same
+// uniform early return for a list shorter than the slab, the same prow table
+// and clamps, the same MT = 1..4 bodies picked once by ceil(rows / 16). The
+// expert's nibbles and scale bytes are reached by 64-bit offsets (e * N *
+// K/2 and e * N * K/32 bytes, multiples of 16 and 4: the loads of Mx4Weights
+// stay aligned); inside an expert the dense format's addressing is
+// unchanged. No zero-point, so no activation sums in LDS.
+template <int NW, int PF>
+__global__ __launch_bounds__(256) void mx4_moe_gemm_kernel(
+    bf16* __restrict__ out,              // [n_pairs, N]
+    const bf16* __restrict__ a,          // [>= ceil(n_pairs / src_div), K]
+    const uint8_t* __restrict__ w,       // [E, N, K/2] e2m1 pairs
+    const uint8_t* __restrict__ scales,  // [E, N, K/32] e8m0
+    const int* __restrict__ counts,      // [E]
+    const int* __restrict__ pairs,       // [E, t_cols]
+    const int t_cols, const int n_pairs, const int src_div,
+    const int n_total, const int k_total) {
+  const int e = blockIdx.y;
+  const int cnt = min(max(counts[e], 0), t_cols);
+  const int r0 = blockIdx.z * 64;
+  if (r0 >= cnt) return;  // uniform
+  const int rows = min(cnt - r0, 64);
+
+  __shared__ __attribute__((aligned(16))) WqLds<NW, false> lds;
+  __shared__ int prow[64];
+  if (threadIdx.x < 64) {
+    const int p = pairs[(int64_t)e * t_cols + r0 + min((int)threadIdx.x,
+                                                       rows - 1)];
+    prow[threadIdx.x] = min(max(p, 0), n_pairs - 1);
+  }
+  __syncthreads();
+
+  const int64_t ww = (int64_t)e * n_total * (k_total / 2);
+  const int64_t ws = (int64_t)e * n_total * (k_total / 32);
+  const WqLane ln(64 * NW);
+#define ARKS_MX4_MOE_SLAB(MT)                                             \
+  wq_stream<MT, PF>(                                                      \
+      lds, ln, Mx4Weights<NW>(ln, w + ww, scales + ws, k_total),          \
+      WqRoutedRows<MT>(out, a, prow, rows, src_div, k_total), 0, k_total, \
+      n_total)
+  switch ((rows + 15) / 16) {
+    case 1: ARKS_MX4_MOE_SLAB(1); break;
+    case 2: ARKS_MX4_MOE_SLAB(2); break;
+    case 3: ARKS_MX4_MOE_SLAB(3); break;
+    default: ARKS_MX4_MOE_SLAB(4); break;
+  }
+#undef ARKS_MX4_MOE_SLAB
 }
 
 // out[n][32c..32c+31] = bf16(e2m1 * 2^(s-127)): one MX block per thread, a
@@ -267,6 +328,27 @@ extern "C" void arks_mx4_skinny_gemm(void* part, void* out, const void* a,
                            (const uint8_t*)scales, (const bf16*)bias, m_rows,
                            n_total, k_total, k_per_split, nsplits, a_stride);
       });
+}
+
+// nw = 64-row N sub-tiles per workgroup (1 or 2); slabs = ceil(max_rows/64).
+extern "C" void arks_mx4_moe_gemm(void* out, const void* a, const void* w,
+                                  const void* scales, const void* counts,
+                                  const void* pairs, int n_experts,
+                                  int t_cols, int n_pairs, int src_div,
+                                  int slabs, int n_total, int k_total, int nw,
+                                  hipStream_t stream) {
+  dim3 grid(n_total / (64 * nw), n_experts, slabs), block(256);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, (bf16*)out,
+                       (const bf16*)a, (const uint8_t*)w,
+                       (const uint8_t*)scales, (const int*)counts,
+                       (const int*)pairs, t_cols, n_pairs, src_div, n_total,
+                       k_total);
+  };
+  if (nw == 2)
+    launch(mx4_moe_gemm_kernel<2, 1>);
+  else
+    launch(mx4_moe_gemm_kernel<1, 1>);
 }
 
 extern "C" void arks_mx4_dequant(void* out, const void* w, const void* scales,

@@ -47,6 +47,10 @@
 // add after the loop, and no f32 VALU arithmetic in the kernel. (An epilogue
 // add cost 36 more VGPRs and four spilled dwords at MT = 128 when compiled
 // without packed f32 forms, see below.) No split-K.
+//
+// mx4_moe_mfma_gemm_kernel is the same tile over the routed experts of an MoE
+// block: rows gathered and scattered through the routing table of
+// moe_route_kernel (moe.hip), one expert per grid.y; comment at the kernel.
 #include "common.h"
 
 // New kernels are compiled without the packed f32 VALU forms (v_pk_add_f32,
@@ -93,6 +97,29 @@ struct MmStage {
       if (kin && row0 + (int)threadIdx.x / 16 + 16 * i < nrows)
         q[i] = *reinterpret_cast<const mm_u32x4*>(
             base + (off + (uint32_t)(16 * i) * (k_total / 2)));
+    }
+  }
+
+  // The same for gathered rows (mx4_moe_mfma_gemm_kernel): row t / 16 + 16 i
+  // of the tile starts soff[i] bytes into src (its 16 B column included),
+  // live while it is below nrows. A row's nibbles are K/2 contiguous bytes,
+  // so the 16 B loads stay whole; one uniform base and 32-bit lane offsets
+  // again, the operand as a whole staying below 4 GB.
+  __device__ __forceinline__ void gather(const uint8_t* __restrict__ src,
+                                         const uint32_t (&soff)[ROWS / 16],
+                                         const int nrows, const int kc,
+                                         const int k_total) {
+    const bool kin = kc + 32 * (int)(threadIdx.x % 16) < k_total;
+    const uint8_t* base = src + kc / 2;
+#pragma unroll
+    for (int i = 0; i < ROWS / 16; ++i) {
+      q[i] = mm_u32x4{0u, 0u, 0u, 0u};
+      uint32_t o = soff[i];
+      // opaque to the optimizer: base + o must not leave the K loop as a
+      // 64-bit address per load (the registers that costs spill)
+      asm volatile("" : "+v"(o));
+      if (kin && (int)threadIdx.x / 16 + 16 * i < nrows)
+        q[i] = *reinterpret_cast<const mm_u32x4*>(base + o);
     }
   }
 
@@ -238,6 +265,149 @@ __global__ __launch_bounds__(256, 2) void mx4_mfma_gemm_kernel(
   }
 }
 
+// Routed grouped W4A4 GEMM over the local experts of an MoE block, for
+// prefill-sized batches:
+//   for e < E_local, i < counts[e], p = pairs[e][i]:
+//     out[p, :] = dq(xq, xs)[p / src_div, :] @ dq(w[e], ws[e])^T
+// The tile, the operand mapping, the single swizzled stage with register
+// prefetch and the scale dwords are mx4_mfma_gemm_kernel's. What differs:
+//   grid = (ceil(N/128), E_local, ceil(max_rows/MT)): workgroup (., e, z)
+//   owns rows [z MT, z MT + MT) of expert e's list and returns at once
+//   (uniform, before any barrier) when the list is shorter than that.
+//   Row table. prow[i] in LDS is the pair (= output row) of tile row i, read
+//   from pairs[e] and clamped to [0, n_pairs); entries past the end of the
+//   list repeat its last pair, so no table read leaves the list.
+//   Activations are gathered: tile row i is row prow[i] / src_div of xq and
+//   xs (src_div = top_k reads the token's row for the w13 GEMM, 1 the pair's
+//   own row of h for w2). A thread keeps the byte offsets of its MT/16 staging
+//   loads and of its MT/32 scale dwords in registers, 32 bits each against a
+//   uniform base (the bindings keep xq below 4 GB). They pass through an empty
+//   asm in the loop: hoisted out of it as 64-bit addresses they cost 16 B of
+//   scratch per lane at MT = 128; so it is 255 VGPRs and none (MT = 64: 148).
+//   The addressing inside a row is unchanged.
+//   Tails as there: tile rows at or past the slab's length, weight rows at or
+//   past N and columns at k >= K are staged as zeros with scale byte 0.
+//   Expert e's nibbles and scale bytes start e * N * K/2 and e * N * K/32
+//   bytes in (64-bit offsets); inside an expert nothing changes.
+//   Epilogue. No bias, so the accumulators start at zero; tile row i < rows
+//   is rounded to bf16 and stored to out[prow[i]] as 8 B vectors. Rows of out
+//   that belong to no local expert are not written.
+template <int MT>
+__global__ __launch_bounds__(256, 2) void mx4_moe_mfma_gemm_kernel(
+    bf16* __restrict__ out,          // [n_pairs, N]
+    const uint8_t* __restrict__ xq,  // [>= ceil(n_pairs / src_div), K/2]
+    const uint8_t* __restrict__ xs,  // [same rows, K/32]
+    const uint8_t* __restrict__ w,   // [E, N, K/2] e2m1 pairs
+    const uint8_t* __restrict__ ws,  // [E, N, K/32] e8m0
+    const int* __restrict__ counts,  // [E]
+    const int* __restrict__ pairs,   // [E, t_cols]
+    const int t_cols, const int n_pairs, const int src_div,
+    const int n_total, const int k_total) {
+  constexpr int TM = MT / 32;  // 16-row activation tiles per wave
+  const int e = blockIdx.y;
+  const int cnt = min(max(counts[e], 0), t_cols);
+  const int r0 = blockIdx.z * MT;
+  if (r0 >= cnt) return;  // uniform
+  const int rows = min(cnt - r0, MT);
+
+  __shared__ mm_u32x4 lds[(MM_NT + MT) * 16];
+  __shared__ int prow[MT];
+  mm_u32x4* const w_lds = lds;
+  mm_u32x4* const x_lds = lds + MM_NT * 16;
+  if (threadIdx.x < MT) {
+    const int p = pairs[(int64_t)e * t_cols + r0 + min((int)threadIdx.x,
+                                                       rows - 1)];
+    prow[threadIdx.x] = min(max(p, 0), n_pairs - 1);
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x % WAVE_SIZE;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE_SIZE);
+  const int r = lane % 16, g = lane / 16;
+  const int wm = wave / 2, wn = wave % 2;
+  const int n0 = blockIdx.x * MM_NT;
+  const int nw0 = n0 + 64 * wn;       // this wave's first column
+  const int mw0 = (MT / 2) * wm;      // and first tile row
+  const bool active = nw0 < n_total;  // wave-uniform
+  const uint8_t* const we = w + (int64_t)e * n_total * (k_total / 2);
+  const uint8_t* const wse = ws + (int64_t)e * n_total * (k_total / 32);
+
+  // byte offsets of this thread's staging loads in xq and of its scale
+  // dwords in xs, at kc = 0
+  uint32_t soff[MT / 16], xoff[TM];
+#pragma unroll
+  for (int i = 0; i < MT / 16; ++i)
+    soff[i] = (uint32_t)(prow[threadIdx.x / 16 + 16 * i] / src_div) *
+                  (k_total / 2) + 16 * (threadIdx.x % 16);
+#pragma unroll
+  for (int t = 0; t < TM; ++t)
+    xoff[t] = (uint32_t)(prow[mw0 + 16 * t + r] / src_div) * (k_total / 32) +
+              4 * g;
+
+  mm_f32x4 acc[4][TM];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int t = 0; t < TM; ++t) acc[j][t] = mm_f32x4{0.f, 0.f, 0.f, 0.f};
+
+  MmStage<MM_NT> wst;
+  MmStage<MT> xst;
+  uint32_t wsc[4], xsc[TM], wsc_next[4] = {}, xsc_next[TM] = {};
+  const auto fetch = [&](const int kc, uint32_t (&wd)[4], uint32_t (&xd)[TM]) {
+    wst.load(we, n0, n_total, kc, k_total);
+    xst.gather(xq, soff, rows, kc, k_total);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      wd[j] = mm_scales(wse, nw0 + 16 * j, r, n_total, kc, g, k_total);
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+      uint32_t o = xoff[t];
+      asm volatile("" : "+v"(o));  // as in MmStage::gather
+      xd[t] = 0u;
+      if (mw0 + 16 * t + r < rows && kc + 128 * g < k_total)
+        xd[t] = *reinterpret_cast<const uint32_t*>(xs + kc / 32 + o);
+    }
+  };
+
+  fetch(0, wsc, xsc);
+  for (int kc = 0; kc < k_total; kc += MM_KS) {
+    wst.store(w_lds);
+    xst.store(x_lds);
+    const bool more = kc + MM_KS < k_total;
+    if (more) fetch(kc + MM_KS, wsc_next, xsc_next);
+    __syncthreads();  // the stage is in LDS
+    if (active) {
+      const mm_u32x4* wl = w_lds + 64 * wn * 16;
+      const mm_u32x4* xl = x_lds + mw0 * 16;
+      mm_step<0, TM>(acc, wl, xl, wsc, xsc, r, g);
+      mm_step<1, TM>(acc, wl, xl, wsc, xsc, r, g);
+      mm_step<2, TM>(acc, wl, xl, wsc, xsc, r, g);
+      mm_step<3, TM>(acc, wl, xl, wsc, xsc, r, g);
+    }
+    __syncthreads();  // every wave has read it: the next one may land
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wsc[j] = wsc_next[j];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) xsc[t] = xsc_next[t];
+  }
+  if (!active) return;
+
+  // acc[j][t][v] = out[prow[mw0 + 16 t + r]][nw0 + 16 j + 4 g + v]
+#pragma unroll
+  for (int t = 0; t < TM; ++t) {
+    const int m = mw0 + 16 * t + r;
+    if (m >= rows) continue;
+    bf16* orow = out + (int64_t)prow[m] * n_total + nw0 + 4 * g;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ushort4v o;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) o[v] = float_to_bf16_bits(acc[j][t][v]);
+      *reinterpret_cast<ushort4v*>(orow + 16 * j) = o;
+    }
+  }
+}
+
 }  // namespace arks
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -265,4 +435,28 @@ extern "C" void arks_mx4_mfma_gemm(void* out, const void* xq, const void* xs,
     launch(mx4_mfma_gemm_kernel<128>);
   else
     launch(mx4_mfma_gemm_kernel<64>);
+}
+
+// mtile: 128 or 64 (ops.mx4a4_moe_gemm chooses). grid = (ceil(N/128),
+// E_local, slabs) with slabs = ceil(max_rows / mtile).
+extern "C" void arks_mx4_moe_mfma_gemm(void* out, const void* xq,
+                                       const void* xs, const void* w,
+                                       const void* ws, const void* counts,
+                                       const void* pairs, int n_experts,
+                                       int t_cols, int n_pairs, int src_div,
+                                       int slabs, int n_total, int k_total,
+                                       int mtile, hipStream_t stream) {
+  dim3 grid((unsigned)((n_total + MM_NT - 1) / MM_NT), n_experts, slabs),
+      block(256);
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, (bf16*)out,
+                       (const uint8_t*)xq, (const uint8_t*)xs,
+                       (const uint8_t*)w, (const uint8_t*)ws,
+                       (const int*)counts, (const int*)pairs, t_cols, n_pairs,
+                       src_div, n_total, k_total);
+  };
+  if (mtile == 128)
+    launch(mx4_moe_mfma_gemm_kernel<128>);
+  else
+    launch(mx4_moe_mfma_gemm_kernel<64>);
 }

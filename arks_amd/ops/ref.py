@@ -842,6 +842,43 @@ def mx4a4_linear(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor,
     return y.to(x.dtype)
 
 
+def mx4_moe_gemm(a: torch.Tensor, weight, counts: torch.Tensor,
+                 pairs: torch.Tensor, src_div: int, out=None) -> torch.Tensor:
+    """out[p] = a[p // src_div] @ mx4_dequant(mx4[e], scales[e])^T for every
+    local expert e and p in pairs[e][:counts[e]]: a plain loop over experts
+    (f32 accumulate, one rounding to a's dtype). weight is the stacked pair
+    (mx4 u8 [E, N, K/2], scales u8 [E, N, K/32]). Rows of `out` that no
+    local expert owns are left as they are (zeros when out is None)."""
+    w, scales = weight
+    E, N = w.shape[0], w.shape[1]
+    T = pairs.shape[1]
+    n_pairs = T * (a.shape[0] * src_div // T)
+    if out is None:
+        out = torch.zeros(n_pairs, N, dtype=a.dtype, device=a.device)
+    for e in range(E):
+        p = pairs[e, :int(counts[e])].long()
+        if p.numel() == 0:
+            continue
+        src = torch.div(p, src_div, rounding_mode="floor")
+        out[p] = (a[src].float()
+                  @ mx4_dequant(w[e], scales[e]).t()).to(out.dtype)
+    return out
+
+
+def mx4a4_moe_gemm(xq: torch.Tensor, xs: torch.Tensor, weight,
+                   counts: torch.Tensor, pairs: torch.Tensor, src_div: int,
+                   out=None) -> torch.Tensor:
+    """mx4_moe_gemm on the MXFP4 activations (xq u8 [rows, K/2], xs u8
+    [rows, K/32]) expanded by mx4_dequant, rounded once to bf16."""
+    if out is None:
+        T = pairs.shape[1]
+        out = torch.zeros(T * (xq.shape[0] * src_div // T),
+                          weight[0].shape[1], dtype=torch.bfloat16,
+                          device=xq.device)
+    return mx4_moe_gemm(mx4_dequant(xq, xs), weight, counts, pairs, src_div,
+                        out=out)
+
+
 POOL_LAST, POOL_MEAN, POOL_CLS = 0, 1, 2
 
 
