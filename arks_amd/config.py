@@ -678,6 +678,13 @@ class EngineConfig:
     # FP4 matrix instruction. lm_head, experts and excluded modules keep
     # bf16 activations.
     mx_activations: str = "bf16"
+    # "bf16" | "fp8": with block-scaled FP8 weights, also quantize the inputs
+    # of the dense W8 layers dynamically to e4m3 (one f32 scale per token per
+    # 128 columns), as such a checkpoint's activation_scheme "dynamic"
+    # specifies: W8A8, prefill-sized batches on the FP8 matrix instruction.
+    # Decode-sized batches, lm_head, experts and skipped modules keep bf16
+    # activations.
+    w8_activations: str = "bf16"
     # "auto" (bf16) | "fp8": e4m3 KV pages (halves the decode KV stream;
     # scale 1.0, opt-in like vLLM's --kv-cache-dtype fp8)
     kv_cache_dtype: str = "auto"
@@ -736,6 +743,17 @@ class EngineConfig:
                 "mx_activations='mxfp4' needs quantization='mxfp4' (or an "
                 f"MXFP4 checkpoint), got quantization={self.quantization!r}"
             )
+        if self.w8_activations not in ("bf16", "fp8"):
+            raise ValueError(
+                f"unknown w8_activations {self.w8_activations!r}: expected "
+                "'bf16' or 'fp8'"
+            )
+        if (self.w8_activations == "fp8"
+                and self.quantization not in (None, "fp8")):
+            raise ValueError(
+                "w8_activations='fp8' needs a block-scaled FP8 checkpoint, "
+                f"got quantization={self.quantization!r}"
+            )
         if not self.enable_lora:
             if self.lora_modules:
                 raise ValueError("lora_modules given without enable_lora")
@@ -774,6 +792,12 @@ class EngineConfig:
                 "mx_activations='mxfp4' needs MXFP4 weights, but the "
                 f"resolved quantization is {mode!r} (give "
                 "quantization='mxfp4' or an MXFP4 checkpoint)"
+            )
+        if self.w8_activations == "fp8" and mode != "fp8_block":
+            raise ValueError(
+                "w8_activations='fp8' needs block-scaled FP8 (W8) weights, "
+                f"but the resolved quantization is {mode!r} (give a "
+                "block-scaled FP8 checkpoint)"
             )
         return mode
 

@@ -155,6 +155,13 @@ class ModelRunner:
             for mod in self.model.modules():
                 if getattr(mod, "mx4", False):
                     mod.mx4_act = "mxfp4"
+        if self.cfg.w8_activations == "fp8":
+            # W8A8: every dense W8 layer quantizes prefill-sized inputs to
+            # FP8 (lm_head and skipped modules are not W8 modules; W8 experts
+            # keep their routed W8A16 kernel)
+            for mod in self.model.modules():
+                if getattr(mod, "w8", False):
+                    mod.w8_act = "fp8"
         # serving past max_position_embeddings: the rope table must cover
         # every reachable position (OOB table reads fault on GPU)
         if hasattr(self.model, "extend_rope_table"):

@@ -1000,6 +1000,111 @@ def mx4a4_linear(x, weight, bias=None, defer: bool = False, plan=None):
     return mx4_linear(mx4_quantize_act(x, qdq=True), weight, bias, defer, plan)
 
 
+# W8A8: rows from which w8a8_linear quantizes the activations to FP8 and
+# runs the FP8 MFMA GEMM; below it the layer is w8_linear as it was. It sits
+# right above the slab limit, the first size that takes the dequant-and-
+# library route this replaces: a value from the code, and it stayed there,
+# because NO measured M makes the new route win on all four Qwen2.5-7B
+# shapes. MEASURED on an MI355X with scripts/bench_w8.py --a8 (in-graph us,
+# quantizer + MFMA GEMM vs w8_linear; profiles/w8_gemm.md section 3):
+# M=129: qkv 48.3 vs 31.8, o 48.3 vs 30.5, gate_up 113.7 vs 153.9, down 226.5
+# vs 117.5; M=512: 51.8 vs 40.5, 50.5 vs 33.6, 193.2 vs 223.2, 233.3 vs 206.7;
+# M=8192: 297.3 vs 223.9, 242.6 vs 158.6, 2207.5 vs 1702.2, 1302.8 vs 906.7.
+# gate_up wins from 129 to 512 rows and nothing else does: the GEMM has a
+# floor of about 1.6 us per 128-k block (46 us on qkv / o, 222 us on down at
+# every M <= 512) and reaches 0.94-1.02 PFLOP/s at M = 8192, below what the
+# library gets from the expanded weight. The mode therefore stays opt-in.
+W8A8_MFMA_MIN_M = W8_SLAB_MAX_M + 1
+# w8_mfma_gemm_kernel's workgroups take 128 rows once the 128-row grid has a
+# workgroup for each of the 256 CUs, else 64. MEASURED in the same table
+# (gemm64 vs gemm128): up to 144 workgroups of 128 rows the 64-row tile wins
+# (qkv M=512: 46.9 vs 54.7 us, down M=512: 223.3 vs 266.6), from 296 on the
+# 128-row tile does (gate_up M=128: 80.2 vs 100.6, o M=2048: 59.6 vs 92.5,
+# down M=2048: 278.1 vs 466.5; gate_up M=129 / 192 within 2.4%). Nothing was
+# measured between 144 and 296.
+_W8A8_TILE128_MIN_WGS = 256
+
+
+def w8_quantize_act(x):
+    """Dynamic FP8 quantization of bf16 activations x [M, K], K % 128 == 0,
+    by the rule of ref.w8_quantize_act (w8_act_quant_kernel on GPU, bit-equal
+    to it): (xq float8_e4m3fn [M, K], xs f32 [M, K/128])."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or x.shape[1] % 128 != 0:
+        raise ValueError("w8_quantize_act needs a 2-D bf16 input with "
+                         f"K % 128 == 0, got {tuple(x.shape)} {x.dtype}")
+    if not x.is_cuda:
+        return ref.w8_quantize_act(x)
+    M, K = x.shape
+    if (x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.stride(0) < K
+            or x.data_ptr() % 16 != 0):
+        x = x.contiguous()
+    xq = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device)
+    xs = torch.empty((M, K // 128), dtype=torch.float32, device=x.device)
+    if M:
+        _native().w8_act_quant(xq, xs, x)
+    return xq, xs
+
+
+def w8a8_gemm(xq, xs, weight, bias=None, mtile: int | None = None):
+    """bf16 [M, N] = sum_kb (xs[m, kb] * ws[kb, n]) * (xq[m, kb] . w8[n, kb])
+    + bias for FP8 activations (xq e4m3fn [M, K], xs f32 [M, K/128] from
+    w8_quantize_act) and a W8 weight (w8_weight, w8_scales), f32 accumulation
+    starting from the bias: any M >= 1, N % 64 == 0, K % 128 == 0, anything
+    else raises. On GPU: w8_mfma_gemm_kernel on the FP8 matrix instruction,
+    one MFMA per scale block, rescaled on the VALU. On CPU: the dequantized
+    operands multiplied in f32.
+    mtile is for tests only: it forces the workgroup's rows (128 or 64) so
+    that both tile heights run at small shapes; callers leave it None."""
+    N, K = _W8.shape(weight)
+    M = xq.shape[0] if xq.dim() == 2 else -1
+    if (M < 1 or N % 64 != 0 or K % 128 != 0
+            or tuple(xq.shape) != (M, K)
+            or tuple(xs.shape) != (M, K // 128)
+            or tuple(weight[1].shape) != (K // 128, N)
+            or xq.dtype != torch.float8_e4m3fn or xs.dtype != torch.float32
+            or weight[0].dtype != torch.float8_e4m3fn
+            or weight[1].dtype != torch.float32):
+        raise ValueError(
+            f"w8a8_gemm needs xq e4m3fn [M, K] and xs f32 [M, K/128] with "
+            f"M >= 1 for a W8 weight with N % 64 == 0 and K % 128 == 0, got "
+            f"xq {tuple(xq.shape)} {xq.dtype}, xs {tuple(xs.shape)} "
+            f"{xs.dtype}, N={N}, K={K}, scales {tuple(weight[1].shape)}")
+    if mtile not in (None, 64, 128):
+        raise ValueError(f"mtile must be 64 or 128, got {mtile}")
+    if not xq.is_cuda:
+        y = ref.w8_dequant_act(xq, xs) @ ref.w8_dequant(*weight).t()
+        if bias is not None:
+            y = y + bias.float()
+        return y.to(torch.bfloat16)
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    if mtile is None:
+        wgs = -(-M // 128) * -(-N // 128)
+        mtile = 128 if wgs >= _W8A8_TILE128_MIN_WGS else 64
+    _native().w8a8_gemm(out, xq, xs, *weight, bias, mtile)
+    return out
+
+
+def w8a8_linear(x, weight, bias=None, defer: bool = False, plan=None):
+    """A W8 layer with dynamic FP8 activations, as a block-scaled FP8
+    checkpoint declares them (activation_scheme: dynamic). From
+    W8A8_MFMA_MIN_M rows: w8_act_quant_kernel quantizes x per row per 128
+    columns and w8_mfma_gemm_kernel multiplies FP8 by FP8, so the weight is
+    never expanded. Below it: exactly w8_linear (bf16 activations; the skinny
+    kernel and slabs, defer and plan as there), so decode is untouched and
+    stays the more precise computation of the two. Scratch comes from the
+    caching allocator, so graph capture is safe. On CPU the same routing on
+    the reference emulations."""
+    if x.dim() == 2 and x.shape[0] >= W8A8_MFMA_MIN_M:
+        if not x.is_cuda:
+            return ref.w8a8_linear(x, *weight, bias)
+        if x.dtype != torch.bfloat16 or x.shape[1] != _W8.shape(weight)[1]:
+            raise ValueError(
+                f"w8a8_linear needs a bf16 input with K="
+                f"{_W8.shape(weight)[1]}, got {tuple(x.shape)} {x.dtype}")
+        return w8a8_gemm(*w8_quantize_act(x), weight, bias)
+    return w8_linear(x, weight, bias, defer, plan)
+
+
 def w4_moe_gemm(a, packed, counts, pairs, src_div: int, max_rows: int,
                 out=None):
     """Routed grouped W4A16 GEMM over the stacked local experts of an MoE

@@ -173,6 +173,12 @@ void arks_w8_moe_gemm(void* out, const void* a, const void* w8,
                       const void* pairs, int n_experts, int t_cols,
                       int n_pairs, int src_div, int slabs, int n_total,
                       int k_total, int nw, hipStream_t stream);
+void arks_w8_act_quant(void* xq, void* xs, const void* x, int m_rows,
+                       int k_total, int64_t x_stride, hipStream_t stream);
+void arks_w8_mfma_gemm(void* out, const void* xq, const void* xs,
+                       const void* w8, const void* ws, const void* bias,
+                       int m_rows, int n_total, int k_total, int mtile,
+                       hipStream_t stream);
 void arks_moe_bf16_gemm(void* out, const void* a, const void* w,
                         const void* counts, const void* pairs, int n_experts,
                         int t_cols, int n_pairs, int src_div, int slabs,
@@ -753,6 +759,72 @@ void w8_dequant(torch::Tensor out, torch::Tensor w8, torch::Tensor scales) {
   TORCH_CHECK(n * (k / 16) < (int64_t)1 << 39);
   arks_w8_dequant(out.data_ptr(), w8.data_ptr(), scales.data_ptr(), (int)n,
                   (int)k, current_stream());
+}
+
+// FP8 activations of a W8A8 layer (w8_mfma_gemm.hip): xq e4m3fn [M, K] and xs
+// f32 [M, K/128], one scale per row per 128 k.
+void check_w8_act_quantized(const torch::Tensor& xq, const torch::Tensor& xs,
+                            int64_t m, int64_t k, const at::Device& dev) {
+  TORCH_CHECK(xq.is_cuda() && xq.scalar_type() == at::kFloat8_e4m3fn &&
+              xq.is_contiguous() && xq.dim() == 2 && xq.size(0) == m &&
+              xq.size(1) == k && xq.device() == dev &&
+              reinterpret_cast<uintptr_t>(xq.data_ptr()) % 16 == 0,
+              "xq must be contiguous float8_e4m3fn [M, K] on the GPU of x / w");
+  TORCH_CHECK(xs.is_cuda() && xs.scalar_type() == torch::kFloat32 &&
+              xs.is_contiguous() && xs.dim() == 2 && xs.size(0) == m &&
+              xs.size(1) == k / 128 && xs.device() == dev &&
+              reinterpret_cast<uintptr_t>(xs.data_ptr()) % 4 == 0,
+              "xs must be contiguous f32 [M, K/128] on the GPU of x / w");
+}
+
+// x bf16 [M, K] (unit column stride, rows 16 B aligned and at least K apart)
+// to xq / xs by the rule of ops/ref.py w8_quantize_act (w8_act_quant_kernel).
+void w8_act_quant(torch::Tensor xq, torch::Tensor xs, torch::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
+              x.dim() == 2 && x.size(0) >= 1 && x.stride(1) == 1 &&
+              x.stride(0) >= x.size(1) && x.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be bf16 [M, K] on GPU with 16 B aligned rows");
+  TORCH_CHECK(x.size(1) >= 128 && x.size(1) % 128 == 0,
+              "W8A8 needs K % 128 == 0, got K=", x.size(1));
+  TORCH_CHECK(x.size(0) * (x.size(1) / 8) < (int64_t)1 << 39);
+  check_w8_act_quantized(xq, xs, x.size(0), x.size(1), x.device());
+  arks_w8_act_quant(xq.data_ptr(), xs.data_ptr(), x.data_ptr(),
+                    (int)x.size(0), (int)x.size(1), x.stride(0),
+                    current_stream());
+}
+
+// out bf16 [M, N] = sum over k-blocks of (xs * ws) * (xq . w8) + bias on the
+// FP8 MFMA (w8_mfma_gemm_kernel), any M >= 1. mtile = 128 or 64 rows per
+// workgroup.
+void w8a8_gemm(torch::Tensor out, torch::Tensor xq, torch::Tensor xs,
+               torch::Tensor w8, torch::Tensor scales,
+               c10::optional<torch::Tensor> bias, int64_t mtile) {
+  const auto [n, k] = check_w8_weight(w8, scales);
+  const int64_t m = xq.dim() == 2 ? xq.size(0) : 0;
+  TORCH_CHECK(mtile == 128 || mtile == 64, "mtile must be 128 or 64");
+  // grid.y = ceil(M / mtile) must stay within 65535
+  TORCH_CHECK(m >= 1 && m <= 65535 * mtile,
+              "w8a8_gemm needs 1 <= M <= 65535 * mtile, got M=", m);
+  // a tile's 32-bit lane offsets span 128 rows of K bytes
+  TORCH_CHECK(k < (int64_t)1 << 24, "w8a8_gemm needs K < 2^24, got K=", k);
+  check_w8_act_quantized(xq, xs, m, k, w8.device());
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == m && out.size(1) == n &&
+              out.device() == w8.device() &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "out must be bf16 [M, N] on the weight's GPU");
+  const void* bias_ptr = nullptr;
+  if (bias.has_value()) {
+    check_bf16_contig(*bias, "bias");
+    TORCH_CHECK(bias->numel() == n && bias->device() == w8.device() &&
+                reinterpret_cast<uintptr_t>(bias->data_ptr()) % 8 == 0,
+                "bias must be bf16 [N], 8 B aligned");
+    bias_ptr = bias->data_ptr();
+  }
+  arks_w8_mfma_gemm(out.data_ptr(), xq.data_ptr(), xs.data_ptr(),
+                    w8.data_ptr(), scales.data_ptr(), bias_ptr, (int)m,
+                    (int)n, (int)k, (int)mtile, current_stream());
 }
 
 // MX4 weight (mx4_gemm.hip): the checkpoint's tensors, u8 [N, K/2] with two
@@ -1777,6 +1849,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w8_skinny_gemm_partials", &w8_skinny_gemm_partials);
   m.def("w8_dequant", &w8_dequant);
   m.def("w8_moe_gemm", &w8_moe_gemm);
+  m.def("w8_act_quant", &w8_act_quant);
+  m.def("w8a8_gemm", &w8a8_gemm);
   m.def("moe_bf16_gemm", &moe_bf16_gemm);
   m.def("mx4_skinny_gemm", &mx4_skinny_gemm);
   m.def("mx4_skinny_gemm_partials", &mx4_skinny_gemm_partials);

@@ -703,6 +703,50 @@ def w8_linear(x: torch.Tensor, w8: torch.Tensor, scales: torch.Tensor,
         x, w8_dequant(w8, scales).to(x.dtype), bias)
 
 
+def w8_quantize_act(x: torch.Tensor):
+    """Dynamic FP8 activations of a W8A8 layer: the rule of w8_quantize on
+    1 x 128 groups. x [M, K] with K % 128 == 0 -> (xq e4m3fn [M, K], xs f32
+    [M, K/128]): per row and block of 128 consecutive k, s = amax / 448 in
+    f32 (1 for an all-zero block) and the code is clamp(x / s, -448, 448) in
+    f32 rounded to nearest even."""
+    M, K = x.shape
+    if K % W8_BLOCK != 0:
+        raise ValueError(
+            f"w8_quantize_act needs K % {W8_BLOCK} == 0, got K={K}")
+    blocks = x.float().view(M, K // W8_BLOCK, W8_BLOCK)
+    amax = blocks.abs().amax(dim=2)
+    s = torch.where(amax > 0, amax / W8_MAX, torch.ones_like(amax))
+    q = (blocks / s[:, :, None]).clamp(-W8_MAX, W8_MAX)
+    return q.reshape(M, K).to(torch.float8_e4m3fn), s
+
+
+def w8_dequant_act(xq: torch.Tensor, xs: torch.Tensor) -> torch.Tensor:
+    """f32 [M, K] = float(xq) * xs[m, k // 128]."""
+    M, K = xq.shape
+    if K % W8_BLOCK != 0 or tuple(xs.shape) != (M, K // W8_BLOCK):
+        raise ValueError(
+            f"xs {tuple(xs.shape)} does not match codes {tuple(xq.shape)}: "
+            f"expected [{M}, K/{W8_BLOCK}]")
+    return xq.float() * xs.float().repeat_interleave(W8_BLOCK, dim=1)
+
+
+def w8_qdq_act(x: torch.Tensor) -> torch.Tensor:
+    """f32 [M, K]: x quantized by w8_quantize_act and expanded again, the
+    activations a W8A8 layer multiplies."""
+    return w8_dequant_act(*w8_quantize_act(x))
+
+
+def w8a8_linear(x: torch.Tensor, w8: torch.Tensor, scales: torch.Tensor,
+                bias=None) -> torch.Tensor:
+    """The CPU emulation of a W8A8 layer: dynamic FP8 activations
+    (w8_qdq_act) times the dequantized weight, summed in f32, then the bias
+    and the cast to bf16."""
+    y = w8_qdq_act(x) @ w8_dequant(w8, scales).t()
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(torch.bfloat16)
+
+
 def w8_moe_gemm(a: torch.Tensor, weight, counts: torch.Tensor,
                 pairs: torch.Tensor, src_div: int, out=None) -> torch.Tensor:
     """out[p] = a[p // src_div] @ (float(w8[e]) * scales[e])^T for every

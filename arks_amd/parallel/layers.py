@@ -237,11 +237,18 @@ def quantize_module_w8(mod: nn.Module, name: str = "linear") -> None:
 
 
 def _w8_linear(mod: nn.Module, x, bias, defer: bool):
-    if not x.is_cuda:
-        return F.linear(x, mod.weight_qdq, bias)
+    # w8_act = "fp8" (EngineConfig.w8_activations, set by the runner): inputs
+    # of at least ops.W8A8_MFMA_MIN_M rows are quantized to FP8 as well (W8A8)
+    a8 = getattr(mod, "w8_act", "bf16") == "fp8"
     from .. import ops
 
-    return ops.w8_linear(x, (mod.w8_weight, mod.w8_scales), bias, defer=defer)
+    if not x.is_cuda:
+        x2 = x.reshape(-1, x.shape[-1])
+        if a8 and x2.shape[0] >= ops.W8A8_MFMA_MIN_M:
+            x = ops.ref.w8_qdq_act(x2).to(x.dtype).view(x.shape)
+        return F.linear(x, mod.weight_qdq, bias)
+    linear = ops.w8a8_linear if a8 else ops.w8_linear
+    return linear(x, (mod.w8_weight, mod.w8_scales), bias, defer=defer)
 
 
 def _mx4_check_shape(mod: nn.Module, name: str) -> tuple[int, int]:

@@ -51,6 +51,12 @@ def parse_args(argv=None):
                    help="with MXFP4 weights: mxfp4 also quantizes the layer "
                         "inputs dynamically to MXFP4 (W4A4, as a Quark MXFP4 "
                         "export specifies), prefill on the FP4 scaled MFMA")
+    p.add_argument("--w8-activations", choices=["bf16", "fp8"],
+                   default="bf16",
+                   help="with a block-scaled FP8 checkpoint: fp8 also "
+                        "quantizes the dense layers' inputs dynamically per "
+                        "token per 128 columns (W8A8, as the checkpoint's "
+                        "activation_scheme specifies), prefill on the FP8 MFMA")
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     p.add_argument("--speculative", choices=["ngram", "draft"], default=None,
                    help="speculative decoding: ngram (prompt lookup) or "
@@ -121,6 +127,7 @@ def build_engine_config(args):
         quantization=args.quantization,
         quantize_experts=args.quantize_experts,
         mx_activations=args.mx_activations,
+        w8_activations=args.w8_activations,
         kv_cache_dtype=args.kv_cache_dtype,
         speculative=args.speculative,
         draft_model=args.draft_model,

@@ -16,7 +16,17 @@ For M > 64 both W8 routes are timed next to the one w8_linear ships for that
 M: the skinny kernel once per 64-row slab (w8_slab) and dequantize into the
 workspace + library GEMM (w8_deq).
 
-    python scripts/bench_w8.py [--rounds 5] [--out results.json]
+--a8 times the W8A8 mode instead, at prefill sizes (A8_MS rows): (a) w8 =
+ops.w8_linear, the route a W8A16 layer takes at that M (slabs up to
+W8_SLAB_MAX_M rows, dequantize + library GEMM above); (b) bf16 = the library
+GEMM on bf16 weights; (c) quant = the activation quantizer alone; (d) gemm64 /
+gemm128 = the FP8 MFMA GEMM alone on quantized activations with either tile
+height, with the achieved FLOP/s (2 M N K over the time) and their share of
+PEAK_FP8; (e) a8 = quantizer + MFMA GEMM with the shipped tile rule, what
+ops.w8a8_linear runs from W8A8_MFMA_MIN_M rows. Same method: in-graph times,
+weights cycled past the LLC, paths alternating every round.
+
+    python scripts/bench_w8.py [--rounds 5] [--out results.json] [--a8]
 """
 
 from __future__ import annotations
@@ -40,7 +50,11 @@ SHAPES = {  # name: (N, K)
     "down": (3584, 18944),
 }
 MS = (1, 8, 32, 64, 96, 128, 256)
+A8_MS = (64, 128, 129, 192, 256, 512, 2048, 8192)
 LLC_BYTES = 256 << 20
+# MI355X peak dense FP8 matrix rate, from AMD's published product
+# specification of the Instinct MI355X (5.0 PFLOP/s)
+PEAK_FP8 = 5.0e15
 
 
 def w8_bytes(n, k):
@@ -97,15 +111,80 @@ def time_graph(g, ncalls, replays):
     return t0.elapsed_time(t1) * 1e3 / (replays * ncalls)
 
 
+def main_a8(args):
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    rows = []
+    print(f"{'shape':8} {'M':>5} {'path':8} {'us':>10} {'min..max':>21} "
+          f"{'TFLOP/s':>8} {'of peak':>8}")
+    for name in args.shapes.split(","):
+        n, k = SHAPES[name]
+        ncopy16 = -(-2 * LLC_BYTES // (n * k * 2))
+        ncopy8 = -(-2 * LLC_BYTES // w8_bytes(n, k))
+        w16 = [torch.randn(n, k, dtype=torch.bfloat16, device="cuda",
+                           generator=gen) * 0.05 for _ in range(ncopy16)]
+        w8 = [make_w8(n, k, gen) for _ in range(ncopy8)]
+        ops.reserve_dequant_workspace(n * k, "cuda")
+        for m in map(int, args.ms.split(",")):
+            x = torch.randn(m, k, dtype=torch.bfloat16, device="cuda",
+                            generator=gen) * 0.5
+            xq, xs = ops.w8_quantize_act(x)
+            paths = {
+                "w8": (lambda w: ops.w8_linear(x, w), w8),
+                "bf16": (lambda w: ops.linear_bf16(x, w), w16),
+                "quant": (lambda w: ops.w8_quantize_act(x), w8[:1] * 8),
+                "gemm64": (lambda w: ops.w8a8_gemm(xq, xs, w, mtile=64), w8),
+                "gemm128": (lambda w: ops.w8a8_gemm(xq, xs, w, mtile=128),
+                            w8),
+                "a8": (lambda w: ops.w8a8_gemm(*ops.w8_quantize_act(x), w),
+                       w8),
+            }
+            # every path once before the first capture: the split-K workspace
+            # that w8_linear and linear_bf16 share grows to the larger of
+            # their needs here, so no graph keeps a pointer that a later
+            # path's warm-up would have freed
+            for fn, ws in paths.values():
+                fn(ws[0])
+            torch.cuda.synchronize()
+            graphs = {p: capture(fn, ws) for p, (fn, ws) in paths.items()}
+            res = {p: [] for p in paths}
+            for _ in range(args.rounds):  # alternate the paths every round
+                for p, (fn, ws) in paths.items():
+                    res[p].append(time_graph(graphs[p], len(ws),
+                                             max(3, 60 // len(ws))))
+            for p, ts in res.items():
+                med = statistics.median(ts)
+                flops = (2 * m * n * k / (med * 1e-6)
+                         if p.startswith("gemm") else None)
+                tail = (f"{flops / 1e12:8.0f} {flops / PEAK_FP8:8.1%}"
+                        if flops else "")
+                print(f"{name:8} {m:5d} {p:8} {med:10.1f} "
+                      f"{min(ts):10.1f}..{max(ts):<10.1f}{tail}", flush=True)
+                rows.append({"shape": name, "N": n, "K": k, "M": m, "path": p,
+                             "us_median": med, "us_min": min(ts),
+                             "us_max": max(ts), "flops": flops,
+                             "rounds": len(ts)})
+            del graphs
+        del w16, w8
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shapes", default=",".join(SHAPES))
-    ap.add_argument("--ms", default=",".join(map(str, MS)))
+    ap.add_argument("--ms", default=None)
+    ap.add_argument("--a8", action="store_true",
+                    help="time the W8A8 mode at prefill sizes instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available() or not ops.native_available():
         sys.exit("bench_w8 needs a GPU and the built extension")
+    args.ms = args.ms or ",".join(map(str, A8_MS if args.a8 else MS))
+    if args.a8:
+        return main_a8(args)
     gen = torch.Generator(device="cuda").manual_seed(0)
     rows = []
     print(f"{'shape':8} {'M':>4} {'mode':6} {'path':8} {'us':>9} "
