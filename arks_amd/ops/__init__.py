@@ -621,7 +621,9 @@ def linear_bf16(x, weight, bias=None, defer: bool = False):
 # Rows one launch of the shared skinny kernel takes (MT <= 4 tiles of 16).
 W4_SKINNY_MAX_M = W8_SKINNY_MAX_M = _WQ_SKINNY_MAX_M = 64
 # 64 < M <= this: the skinny kernel once per 64-row slab; above it the
-# weight is dequantized into the workspace for the library GEMM. Measured
+# fused-dequant MFMA GEMM (wqa16_mfma_gemm.hip) inside the M ranges of
+# _wqa16_rows, where it was measured faster, and otherwise the weight is
+# dequantized into the workspace for the library GEMM. Measured
 # separately per format: crossovers and numbers in w4_linear's and
 # w8_linear's docstrings (W8: the M = 96 / 128 / 256 rows of
 # profiles/w8_gemm.md).
@@ -661,19 +663,24 @@ class _WqFormat(NamedTuple):
     ref_linear: Callable   # CPU reference: (x, weight tuple, bias) -> y
     ref_dequant: Callable  # CPU reference: weight tuple -> f32 [N, K]
     slab_max_m: int        # W4_SLAB_MAX_M / W8_SLAB_MAX_M
+    a16_rows: Callable     # (N, K) -> (lo, hi) rows that run the fused-dequant
+    #                        MFMA GEMM instead of dequant + library, or None
 
 
 _W4 = _WqFormat(
     "w4", lambda w: (w[0].shape[0], w[0].shape[1] * 8), ref.w4_linear,
-    lambda w: ref.w4_dequant(*ref.w4_unpack(w)), W4_SLAB_MAX_M)
+    lambda w: ref.w4_dequant(*ref.w4_unpack(w)), W4_SLAB_MAX_M,
+    lambda N, K: _wqa16_rows("w4", N, K))
 _W8 = _WqFormat(
     "w8", lambda w: tuple(w[0].shape),
     lambda x, w, bias: ref.w8_linear(x, *w, bias),
-    lambda w: ref.w8_dequant(*w), W8_SLAB_MAX_M)
+    lambda w: ref.w8_dequant(*w), W8_SLAB_MAX_M,
+    lambda N, K: _wqa16_rows("w8", N, K))
 _MX4 = _WqFormat(
     "mx4", lambda w: (w[0].shape[0], w[0].shape[1] * 2),
     lambda x, w, bias: ref.mx4_linear(x, *w, bias),
-    lambda w: ref.mx4_dequant(*w), MX4_SLAB_MAX_M)
+    lambda w: ref.mx4_dequant(*w), MX4_SLAB_MAX_M,
+    lambda N, K: _wqa16_rows("mx4", N, K))
 
 
 def _wq_plan(M: int, N: int, K: int):
@@ -813,6 +820,9 @@ def _wq_linear(fmt: _WqFormat, x, weight, bias, defer: bool, plan):
         return _wq_skinny(fmt, x, weight, bias, defer, plan)
     if M <= fmt.slab_max_m:
         return _wq_slabs(fmt, x, weight, bias)
+    rows = fmt.a16_rows(N, K)
+    if rows and rows[0] <= M and (rows[1] is None or M <= rows[1]):
+        return _wqa16_gemm(fmt, x, weight, bias, None)
     return _wq_dequant_linear(fmt, x, weight, bias)
 
 
@@ -821,8 +831,10 @@ def w4_linear(x, packed, bias=None, defer: bool = False, plan=None):
     (qweight, scales, zeros). On GPU: the W4 streaming kernel for M <= 64
     (defer=True returns a SplitKPending when it splits K, as skinny_gemm
     does); M up to W4_SLAB_MAX_M runs that kernel per 64-row slab; above it
-    the weight is expanded to bf16 in the preallocated workspace and the
-    library GEMM runs on it. No eager fallback: a shape the kernels cannot
+    w4a16_gemm (the fused-dequant MFMA GEMM) runs inside the M range
+    _wqa16_rows gives for the shape, and outside it the weight is expanded to
+    bf16 in the preallocated workspace and the library GEMM runs on it (the
+    numbers behind the ranges are in _wqa16_rows). No eager fallback: a shape the kernels cannot
     take raises. On CPU: the reference emulation.
     plan overrides _w4_plan for M <= 64 (tests force a split count with it).
 
@@ -843,8 +855,11 @@ def w8_linear(x, weight, bias=None, defer: bool = False, plan=None):
     [N, K], w8_scales f32 [K/128, N]). On GPU: the W8 streaming kernel for
     M <= 64 (defer=True returns a SplitKPending when it splits K, as
     skinny_gemm does); M up to W8_SLAB_MAX_M runs that kernel per 64-row
-    slab; above it the weight is expanded to bf16 in the preallocated
-    workspace and the library GEMM runs on it. No eager fallback: a shape the
+    slab; above it w8a16_gemm (the fused-dequant MFMA GEMM) runs inside the M
+    range _wqa16_rows gives for the shape, and outside it the weight is
+    expanded to bf16 in the preallocated workspace and the library GEMM runs
+    on it (the numbers behind the ranges are in _wqa16_rows). No eager
+    fallback: a shape the
     kernels cannot take raises. On CPU: the reference emulation.
     plan overrides _w8_plan for M <= 64 (tests force a split count with it).
 
@@ -867,8 +882,11 @@ def mx4_linear(x, weight, bias=None, defer: bool = False, plan=None):
     tensors of an MXFP4 checkpoint). On GPU: the MX4 streaming kernel for
     M <= 64 (defer=True returns a SplitKPending when it splits K, as
     skinny_gemm does); M up to MX4_SLAB_MAX_M runs that kernel per 64-row
-    slab; above it the weight is expanded to bf16 in the preallocated
-    workspace and the library GEMM runs on it. No eager fallback: a shape the
+    slab; above it mx4a16_gemm (the fused-dequant MFMA GEMM) runs inside the
+    M range _wqa16_rows gives for the shape, and outside it the weight is
+    expanded to bf16 in the preallocated workspace and the library GEMM runs
+    on it (the numbers behind the ranges are in _wqa16_rows). No eager
+    fallback: a shape the
     kernels cannot take (N % 64, K % 128) raises. On CPU: the reference
     emulation.
     plan overrides _mx4_plan for M <= 64 (tests force a split count with it).
@@ -888,6 +906,115 @@ def mx4_linear(x, weight, bias=None, defer: bool = False, plan=None):
     vs 172.5, down 101.1 vs 148.4 — slabs win. MX4_SLAB_MAX_M stays at the W8
     value, the last measured size where slabs win on every shape."""
     return _wq_linear(_MX4, x, weight, bias, defer, plan)
+
+
+# wqa16_mfma_gemm_kernel's workgroups take 64 rows while the 64-row grid fits
+# the 256 CUs in one round (one workgroup per CU), else 128. MEASURED with
+# scripts/bench_{w4,w8,mx4}.py (both heights forced, M = 96 .. 2048 on the
+# four Qwen2.5-7B shapes, tables in profiles/*_gemm.md): this picks the faster
+# height in all 84 cells, e.g. W8 o M=512 (224 workgroups of 64 rows) 30.0 vs
+# 37.9 us, qkv M=512 (288) 55.7 vs 38.2, gate_up M=128 (592) 89.5 vs 76.6.
+_WQA16_TILE64_MAX_WGS = 256
+
+
+def _wqa16_mtile(M: int, N: int) -> int:
+    return 64 if -(-M // 64) * -(-N // 128) <= _WQA16_TILE64_MAX_WGS else 128
+
+
+# Inclusive M ranges (hi None = no upper end) in which the fused-dequant GEMM
+# replaces dequant + library, per format and weight aspect: "wide" N >= 4 K
+# (gate_up), "tall" K >= 4 N (down), else "square" (qkv, o).
+_WQA16_ROWS = {
+    "w4": {"wide": (129, 512), "tall": (512, None), "square": (129, 192)},
+    "w8": {"wide": (129, 512), "tall": (512, None), "square": (129, 192)},
+    "mx4": {"wide": (129, 1024), "tall": (192, None), "square": (129, 512)},
+}
+
+
+def _wqa16_rows(name: str, N: int, K: int):
+    """The M range (lo, hi) in which {name}_linear runs the fused-dequant MFMA
+    GEMM (wqa16_mfma_gemm.hip) on a weight [N, K] instead of expanding it for
+    the library GEMM. A range ends at the last measured M where the new
+    kernel's median beat dequant + library by more than both min..max spreads
+    and whose neighbours towards the range did too.
+
+    MEASURED on an MI355X with scripts/bench_{w4,w8,mx4}.py (in-graph us,
+    weights cycled past the LLC, new kernel with the tile _wqa16_mtile picks
+    vs dequant + library; full tables with bf16 in profiles/*_gemm.md):
+    W4  gate_up M=128 81.2 vs 151.6, 512 204.9 vs 223.2, 1024 403.9 vs 370.2
+        (loses); down 256 167.1 vs 138.0 (loses), 512 166.6 vs 203.2, 2048
+        384.3 vs 394.4; qkv 192 35.4 vs 41.8, 256 35.4 vs 47.7, 512 41.4 vs
+        39.8 (loses); o 192 35.4 vs 38.8, 256 35.3 vs 30.3 (loses: the range
+        of the square shapes ends at 192 for both).
+    W8  gate_up 128 76.6 vs 150.8, 512 204.1 vs 223.4, 1024 395.7 vs 368.5
+        (loses); down 256 139.9 vs 140.2 (tie), 512 140.0 vs 204.8, 2048 377.6
+        vs 395.4; qkv 192 30.3 vs 38.8, 512 38.2 vs 40.9; o 192 30.1 vs 37.2,
+        256 29.8 vs 29.0 (loses).
+    MX4 gate_up 128 67.1 vs 165.4, 1024 325.1 vs 389.0, 2048 627.1 vs 598.2
+        (loses); down 128 119.8 vs 119.3 (tie), 192 117.9 vs 133.2, 2048 308.9
+        vs 405.6; qkv 512 31.9 vs 42.5, 1024 62.5 vs 52.5 (loses); o 512 24.9
+        vs 37.2, 1024 33.2 vs 44.5, 2048 64.7 vs 62.6 (loses).
+    Above its range a shape keeps the old route: the kernel levels off at
+    0.65-0.74 PFLOP/s (W4, W8) and 0.73-0.90 (MX4), below the library GEMM on
+    the expanded weight. bf16 weights stay faster than every W4 / W8 cell but
+    qkv 256 and down 512; MX4 beats bf16 on qkv / o 192, down 256 .. 512 and
+    2048, gate_up 128."""
+    aspect = "wide" if N >= 4 * K else "tall" if K >= 4 * N else "square"
+    return _WQA16_ROWS[name][aspect]
+
+
+def wqa16_min_m(fmt: str, N: int, K: int):
+    """The smallest M at which w4_linear / w8_linear / mx4_linear (fmt = "w4",
+    "w8", "mx4") runs the fused-dequant MFMA GEMM for a weight [N, K], or
+    None if no M does (the routing rule is _wqa16_rows)."""
+    rows = {"w4": _W4, "w8": _W8, "mx4": _MX4}[fmt].a16_rows(N, K)
+    return None if rows is None else rows[0]
+
+
+def _wqa16_gemm(fmt: _WqFormat, x, weight, bias, mtile):
+    what = fmt.name + "a16_gemm"
+    N, wk = fmt.shape(weight)
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or x.shape[0] < 1:
+        raise ValueError(f"{what} needs a bf16 input [M, K] with M >= 1, got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    M, K = x.shape
+    if wk != K or N % 64 != 0 or K % 128 != 0:
+        raise ValueError(f"{what} needs N % 64 == 0 and K % 128 == 0 with "
+                         f"the K of x, got x K={K}, weight N={N} K={wk}")
+    if mtile not in (None, 64, 128):
+        raise ValueError(f"mtile must be 64 or 128, got {mtile}")
+    if not x.is_cuda:
+        return fmt.ref_linear(x, weight, bias)
+    if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    getattr(_native(), what)(out, x, *weight, bias,
+                             mtile or _wqa16_mtile(M, N))
+    return out
+
+
+def w4a16_gemm(x, packed, bias=None, mtile: int | None = None):
+    """bf16 [M, N] = x @ bf16(dequant(packed))^T + bias for bf16 x [M, K]
+    (rows may be strided) and a packed W4 weight, f32 accumulation starting
+    from the bias: any M >= 1, N % 64 == 0, K % 128 == 0, anything else
+    raises. On GPU: wqa16_mfma_gemm_kernel, which decodes the weight tile by
+    tile into LDS (bit-equal to w4_dequant) and feeds the bf16 MFMA; no
+    workspace. On CPU: ref.w4_linear.
+    mtile forces the workgroup's rows (128 or 64); None chooses by the grid
+    (_wqa16_mtile)."""
+    return _wqa16_gemm(_W4, x, packed, bias, mtile)
+
+
+def w8a16_gemm(x, weight, bias=None, mtile: int | None = None):
+    """w4a16_gemm for a W8 weight (w8_weight, w8_scales): the weight tile in
+    LDS is bit-equal to w8_dequant. On CPU: ref.w8_linear."""
+    return _wqa16_gemm(_W8, x, weight, bias, mtile)
+
+
+def mx4a16_gemm(x, weight, bias=None, mtile: int | None = None):
+    """w4a16_gemm for an MX4 weight (mx4_weight, mx4_scales): the weight tile
+    in LDS is bit-equal to mx4_dequant (exact). On CPU: ref.mx4_linear."""
+    return _wqa16_gemm(_MX4, x, weight, bias, mtile)
 
 
 # W4A4: rows from which mx4a4_linear quantizes the activations to packed

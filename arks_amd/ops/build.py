@@ -33,6 +33,7 @@ SOURCES = [
     os.path.join(CSRC, "w8_mfma_gemm.hip"),
     os.path.join(CSRC, "mx4_gemm.hip"),
     os.path.join(CSRC, "mx4_mfma_gemm.hip"),
+    os.path.join(CSRC, "wqa16_mfma_gemm.hip"),
     os.path.join(CSRC, "sampling.hip"),
     os.path.join(CSRC, "topk_topp.hip"),
     os.path.join(CSRC, "moe.hip"),

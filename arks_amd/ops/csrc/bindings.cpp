@@ -179,6 +179,19 @@ void arks_w8_mfma_gemm(void* out, const void* xq, const void* xs,
                        const void* w8, const void* ws, const void* bias,
                        int m_rows, int n_total, int k_total, int mtile,
                        hipStream_t stream);
+void arks_w4a16_mfma_gemm(void* out, const void* x, const void* qw,
+                          const void* scales, const void* zeros,
+                          const void* bias, int m_rows, int n_total,
+                          int k_total, int64_t x_stride, int mtile,
+                          hipStream_t stream);
+void arks_w8a16_mfma_gemm(void* out, const void* x, const void* w8,
+                          const void* scales, const void* bias, int m_rows,
+                          int n_total, int k_total, int64_t x_stride,
+                          int mtile, hipStream_t stream);
+void arks_mx4a16_mfma_gemm(void* out, const void* x, const void* w,
+                           const void* scales, const void* bias, int m_rows,
+                           int n_total, int k_total, int64_t x_stride,
+                           int mtile, hipStream_t stream);
 void arks_moe_bf16_gemm(void* out, const void* a, const void* w,
                         const void* counts, const void* pairs, int n_experts,
                         int t_cols, int n_pairs, int src_div, int slabs,
@@ -888,6 +901,78 @@ void mx4_dequant(torch::Tensor out, torch::Tensor w, torch::Tensor scales) {
   TORCH_CHECK(n * (k / 32) < (int64_t)1 << 39);
   arks_mx4_dequant(out.data_ptr(), w.data_ptr(), scales.data_ptr(), (int)n,
                    (int)k, current_stream());
+}
+
+// Everything the fused-dequant bf16 MFMA GEMMs (wqa16_mfma_gemm.hip) check
+// that does not depend on the weight format, for a weight [n, k] on `dev`:
+// x bf16 [M, K] with unit column stride and 16 B aligned rows, out bf16
+// [M, N], bias bf16 [N] or none, mtile = 128 or 64 rows per workgroup.
+// Returns the bias pointer (null without one).
+const void* check_wqa16(const torch::Tensor& out, const torch::Tensor& x,
+                        const c10::optional<torch::Tensor>& bias, int64_t n,
+                        int64_t k, const at::Device& dev, int64_t mtile) {
+  TORCH_CHECK(mtile == 128 || mtile == 64, "mtile must be 128 or 64");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
+              x.dim() == 2 && x.size(1) == k && x.stride(1) == 1 &&
+              x.stride(0) >= k && x.stride(0) % 8 == 0 && x.device() == dev &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be bf16 [M, K] on the weight's GPU with 16 B aligned "
+              "rows");
+  const int64_t m = x.size(0);
+  // grid.y = ceil(M / mtile) must stay within 65535
+  TORCH_CHECK(m >= 1 && m <= 65535 * mtile,
+              "wqa16 gemm needs 1 <= M <= 65535 * mtile, got M=", m);
+  // a tile's 32-bit lane offsets span 128 rows of x or of the weight
+  TORCH_CHECK(k < (int64_t)1 << 24 && x.stride(0) < (int64_t)1 << 24,
+              "wqa16 gemm needs K and the row stride of x below 2^24");
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == m && out.size(1) == n &&
+              out.device() == dev &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "out must be bf16 [M, N] on the weight's GPU");
+  if (!bias.has_value()) return nullptr;
+  check_bf16_contig(*bias, "bias");
+  TORCH_CHECK(bias->numel() == n && bias->device() == dev &&
+              reinterpret_cast<uintptr_t>(bias->data_ptr()) % 8 == 0,
+              "bias must be bf16 [N], 8 B aligned");
+  return bias->data_ptr();
+}
+
+// out bf16 [M, N] = x @ bf16(dequant(W))^T + bias with the weight decoded
+// inside the kernel (wqa16_mfma_gemm_kernel), any M >= 1: one entry per
+// weight format, each taking the layer's tensors as they are.
+void w4a16_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor qw,
+                torch::Tensor scales, torch::Tensor zeros,
+                c10::optional<torch::Tensor> bias, int64_t mtile) {
+  const auto [n, k] = check_w4_packed(qw, scales, zeros);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qw.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(scales.data_ptr()) % 2 == 0,
+              "qweight must be 16 B aligned");
+  const void* b = check_wqa16(out, x, bias, n, k, qw.device(), mtile);
+  arks_w4a16_mfma_gemm(out.data_ptr(), x.data_ptr(), qw.data_ptr(),
+                       scales.data_ptr(), zeros.data_ptr(), b, (int)x.size(0),
+                       (int)n, (int)k, x.stride(0), (int)mtile,
+                       current_stream());
+}
+
+void w8a16_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w8,
+                torch::Tensor scales, c10::optional<torch::Tensor> bias,
+                int64_t mtile) {
+  const auto [n, k] = check_w8_weight(w8, scales);
+  const void* b = check_wqa16(out, x, bias, n, k, w8.device(), mtile);
+  arks_w8a16_mfma_gemm(out.data_ptr(), x.data_ptr(), w8.data_ptr(),
+                       scales.data_ptr(), b, (int)x.size(0), (int)n, (int)k,
+                       x.stride(0), (int)mtile, current_stream());
+}
+
+void mx4a16_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
+                 torch::Tensor scales, c10::optional<torch::Tensor> bias,
+                 int64_t mtile) {
+  const auto [n, k] = check_mx4_weight(w, scales);
+  const void* b = check_wqa16(out, x, bias, n, k, w.device(), mtile);
+  arks_mx4a16_mfma_gemm(out.data_ptr(), x.data_ptr(), w.data_ptr(),
+                        scales.data_ptr(), b, (int)x.size(0), (int)n, (int)k,
+                        x.stride(0), (int)mtile, current_stream());
 }
 
 // x bf16 [M, K] (unit column stride, rows 16 B aligned) to MXFP4
@@ -1852,6 +1937,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w8_act_quant", &w8_act_quant);
   m.def("w8a8_gemm", &w8a8_gemm);
   m.def("moe_bf16_gemm", &moe_bf16_gemm);
+  m.def("w4a16_gemm", &w4a16_gemm);
+  m.def("w8a16_gemm", &w8a16_gemm);
+  m.def("mx4a16_gemm", &mx4a16_gemm);
   m.def("mx4_skinny_gemm", &mx4_skinny_gemm);
   m.def("mx4_skinny_gemm_partials", &mx4_skinny_gemm_partials);
   m.def("mx4_dequant", &mx4_dequant);

@@ -44,9 +44,9 @@
 // at the kernel. Its prefill-sized W4A4 counterpart on the scaled MFMA is
 // mx4_moe_mfma_gemm_kernel (mx4_mfma_gemm.hip).
 //
-// Not here: a W4A16 MFMA kernel for prefill-sized batches with bf16
-// activations (the routed kernel runs them slab by slab, the dense layers
-// expand the weight for the library GEMM).
+// Not here: the W4A16 MFMA kernel for prefill-sized batches of the dense
+// layers with bf16 activations is wqa16_mfma_gemm.hip; the routed kernel
+// still runs such batches slab by slab.
 #include "wq_stream.h"
 
 namespace arks {

@@ -18,8 +18,11 @@ M <= 64 the last column checks the expectation above against the measured W4
 spread (max - min over the rounds).
 
 For M > 64 both MX4 routes are timed next to the one mx4_linear ships for
-that M: the skinny kernel once per 64-row slab (mx4_slab) and dequantize into
-the workspace + library GEMM (mx4_deq).
+that M: the skinny kernel once per 64-row slab (mx4_slab), dequantize into
+the workspace + library GEMM (mx4_deq), and the fused-dequant MFMA GEMM with
+64- and 128-row workgroup tiles (mx4_a16t64 / mx4_a16t128; TF/s = 2 M N K over
+the median), whose output is first compared with mx4_deq's on the same inputs
+against the bound of tests/test_wqa16_gpu.py.
 
 --a4 times the W4A4 mode instead, at prefill sizes (A4_MS rows): (a) mx4 =
 ops.mx4_linear, the route a W4A16 layer takes at that M; (b) bf16 = F.linear
@@ -182,6 +185,16 @@ def main_a4(args):
             json.dump(rows, f, indent=1)
 
 
+def check_a16(name, m, x, wd, y_old, *ys_new):
+    """Old route (dequant + library) against the fused GEMM on the same
+    inputs: max |new - old| over the bound of two f32 summation orders."""
+    y, t = y_old.float(), x.float().abs() @ wd.float().abs().t()
+    tol = 2.0 ** -8 * y.abs() + x.shape[1] * 2.0 ** -23 * t
+    worst = max(((o.float() - y).abs() / tol).max().item() for o in ys_new)
+    print(f"{name:8} {m:4d} a16 vs deq: max |diff| / bound = {worst:.3f}",
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -202,8 +215,8 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(0)
     modes = ("eager", "graph") if args.eager else ("graph",)
     rows = []
-    print(f"{'shape':8} {'M':>4} {'mode':6} {'path':8} {'us':>9} "
-          f"{'min..max':>19} {'GB/s':>8}  vs W4")
+    print(f"{'shape':8} {'M':>4} {'mode':6} {'path':11} {'us':>9} "
+          f"{'min..max':>19} {'GB/s':>8} {'TF/s':>7}  vs W4")
     for name in args.shapes.split(","):
         n, k = SHAPES[name]
         ncopy16 = -(-2 * LLC_BYTES // (n * k * 2))
@@ -229,6 +242,14 @@ def main():
                 paths["mx4_deq"] = (
                     lambda w: ops._wq_dequant_linear(ops._MX4, x, w, None),
                     mx4, mx4_bytes(n, k))
+                for mt in (64, 128):
+                    paths[f"mx4_a16t{mt}"] = (
+                        lambda w, mt=mt: ops.mx4a16_gemm(x, w, mtile=mt),
+                        mx4, mx4_bytes(n, k))
+                check_a16(name, m, x, ops.mx4_dequant(mx4[0]),
+                          paths["mx4_deq"][0](mx4[0]),
+                          paths["mx4_a16t64"][0](mx4[0]),
+                          paths["mx4_a16t128"][0](mx4[0]))
             graphs = {p: capture(fn, ws) for p, (fn, ws, _) in paths.items()}
             res = {(mode, p): [] for mode in modes for p in paths}
             for _ in range(args.rounds):  # alternate the paths every round
@@ -249,13 +270,15 @@ def main():
                 if p == "mx4" and mode == "graph" and m <= 64:
                     verdict = (f"{'ok' if med <= bound else 'MISS'} "
                                f"(<= {bound:.1f})")
-                print(f"{name:8} {m:4d} {mode:6} {p:8} {med:9.1f} "
-                      f"{min(ts):9.1f}..{max(ts):<9.1f}{gbs:8.0f}  {verdict}",
-                      flush=True)
+                tfs = 2 * m * n * k / med / 1e6
+                print(f"{name:8} {m:4d} {mode:6} {p:11} {med:9.1f} "
+                      f"{min(ts):9.1f}..{max(ts):<9.1f}{gbs:8.0f} {tfs:7.1f}"
+                      f"  {verdict}", flush=True)
                 rows.append({"shape": name, "N": n, "K": k, "M": m,
                              "mode": mode, "path": p, "us_median": med,
                              "us_min": min(ts), "us_max": max(ts),
-                             "weight_gbs": gbs, "rounds": len(ts),
+                             "weight_gbs": gbs, "tflops": tfs,
+                             "rounds": len(ts),
                              "w4_bound_us": bound if verdict else None})
             del graphs
         del w16, w4, mx4

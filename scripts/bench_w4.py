@@ -9,8 +9,12 @@ rounds and their min..max spread, and the effective weight bandwidth (bytes
 of the weight as stored, over the median time).
 
 For M > 64 both W4 routes are timed next to the one w4_linear ships for that
-M: the skinny kernel once per 64-row slab (w4_slab) and dequantize into the
-workspace + library GEMM (w4_deq).
+M: the skinny kernel once per 64-row slab (w4_slab), dequantize into the
+workspace + library GEMM (w4_deq), and the fused-dequant MFMA GEMM with 64-
+and 128-row workgroup tiles (w4_a16t64 / w4_a16t128; TF/s = 2 M N K over the
+median). Before timing, the fused GEMM's output is compared with w4_deq's on
+the same inputs against |d| <= 2^-8 |y| + K 2^-23 (|x| @ |W|^T), the bound of
+tests/test_wqa16_gpu.py, and the worst ratio is printed.
 
     python scripts/bench_w4.py [--rounds 5] [--out results.json]
 """
@@ -94,6 +98,16 @@ def time_graph(g, ncalls, replays):
     return t0.elapsed_time(t1) * 1e3 / (replays * ncalls)
 
 
+def check_a16(name, m, x, wd, y_old, *ys_new):
+    """Old route (dequant + library) against the fused GEMM on the same
+    inputs: max |new - old| over the bound of two f32 summation orders."""
+    y, t = y_old.float(), x.float().abs() @ wd.float().abs().t()
+    tol = 2.0 ** -8 * y.abs() + x.shape[1] * 2.0 ** -23 * t
+    worst = max(((o.float() - y).abs() / tol).max().item() for o in ys_new)
+    print(f"{name:8} {m:4d} a16 vs deq: max |diff| / bound = {worst:.3f}",
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -105,8 +119,8 @@ def main():
         sys.exit("bench_w4 needs a GPU and the built extension")
     gen = torch.Generator(device="cuda").manual_seed(0)
     rows = []
-    print(f"{'shape':8} {'M':>4} {'mode':6} {'path':8} {'us':>9} "
-          f"{'min..max':>19} {'GB/s':>8}")
+    print(f"{'shape':8} {'M':>4} {'mode':6} {'path':10} {'us':>9} "
+          f"{'min..max':>19} {'GB/s':>8} {'TF/s':>7}")
     for name in args.shapes.split(","):
         n, k = SHAPES[name]
         ncopy16 = -(-2 * LLC_BYTES // (n * k * 2))
@@ -129,6 +143,14 @@ def main():
                 paths["w4_deq"] = (
                     lambda w: ops._wq_dequant_linear(ops._W4, x, w, None), w4,
                     w4_bytes(n, k))
+                for mt in (64, 128):
+                    paths[f"w4_a16t{mt}"] = (
+                        lambda w, mt=mt: ops.w4a16_gemm(x, w, mtile=mt), w4,
+                        w4_bytes(n, k))
+                check_a16(name, m, x, ops.w4_dequant(w4[0]),
+                          paths["w4_deq"][0](w4[0]),
+                          paths["w4_a16t64"][0](w4[0]),
+                          paths["w4_a16t128"][0](w4[0]))
             graphs = {p: capture(fn, ws) for p, (fn, ws, _) in paths.items()}
             res = {(mode, p): [] for mode in ("eager", "graph")
                    for p in paths}
@@ -142,13 +164,15 @@ def main():
             for (mode, p), ts in res.items():
                 med = statistics.median(ts)
                 gbs = paths[p][2] / med / 1e3
-                print(f"{name:8} {m:4d} {mode:6} {p:8} {med:9.1f} "
-                      f"{min(ts):9.1f}..{max(ts):<9.1f}{gbs:8.0f}",
+                tfs = 2 * m * n * k / med / 1e6
+                print(f"{name:8} {m:4d} {mode:6} {p:10} {med:9.1f} "
+                      f"{min(ts):9.1f}..{max(ts):<9.1f}{gbs:8.0f} {tfs:7.1f}",
                       flush=True)
                 rows.append({"shape": name, "N": n, "K": k, "M": m,
                              "mode": mode, "path": p, "us_median": med,
                              "us_min": min(ts), "us_max": max(ts),
-                             "weight_gbs": gbs, "rounds": len(ts)})
+                             "weight_gbs": gbs, "tflops": tfs,
+                             "rounds": len(ts)})
             del graphs
         del w16, w4
         torch.cuda.empty_cache()
