@@ -284,6 +284,31 @@ class MoEMLP(nn.Module):
     ROUTED_BF16_TOKENS = DENSE_TOKENS
     routed_bf16_calls = 0   # forwards that took the routed bf16 path
 
+    # Quantized experts with bf16 activations above DENSE_TOKENS: once the
+    # mean expert list T * k / E has this many rows, both expert GEMMs run the
+    # fused-dequant MFMA kernel (ops.w4a16_moe_gemm / w8a16_moe_gemm /
+    # mx4a16_moe_gemm: a weight tile is decoded once per 128 rows of a list);
+    # below it the streaming kernels as before.
+    # MEASURED with scripts/bench_{w4,w8,mx4}_moe.py on an MI355X (whole
+    # block, eager us, MFMA route with 128-row tiles vs streaming, median of
+    # 5 alternating rounds, min..max disjoint unless said; section "Prefill
+    # on the fused-dequant MFMA kernel" of profiles/{w4,w8,mx4}_moe.md), by
+    # mean rows (mixtral-8x7b T=512 .. 4096 is 128 .. 1024 rows, qwen3-30b-a3b
+    # T=2048 / 4096 is 128 / 256):
+    # W4  mixtral 256 rows 1572 vs 1430 (loses), 512 2620 vs 2714, 1024 4907
+    #     vs 5367; qwen 256 rows 934 vs 833 (loses).
+    # W8  mixtral 128 rows 845 vs 946, 256 1375 vs 1636, 512 2458 vs 3018,
+    #     1024 4631 vs 5799; qwen 128 rows 539 vs 529 (loses), 256 881 vs 923.
+    #     128 rows wins on one shape only, so the rule starts at 256.
+    # MX4 mixtral 256 rows 1375 vs 1376 (tie), 512 2227 vs 2503, 1024 4197 vs
+    #     4948; qwen 256 rows 801 vs 686 (loses).
+    # Nothing was measured between these sizes. The bf16 block stays faster
+    # than every quantized route from T=1024 on mixtral (T=2048: 1862 us).
+    W4A16_MOE_MIN_ROWS = 512
+    W8A16_MOE_MIN_ROWS = 256
+    MX4A16_MOE_MIN_ROWS = 512
+    routed_wqa16_calls = 0  # forwards that took the fused-dequant MFMA route
+
     def bf16_routed_supported(self) -> bool:
         """What moe_bf16_gemm_kernel needs of both expert GEMMs (w13: K = H,
         N = 2I; w2: K = I, N = H)."""
@@ -732,15 +757,19 @@ class MoEMLP(nn.Module):
 
     def _forward_mx4(self, x):
         """GPU forward of an MX4 block: _forward_routed over
-        ops.mx4_moe_gemm. With MXFP4 activations x is quantized once for the
+        ops.mx4_moe_gemm (bf16 activations: ops.mx4a16_moe_gemm for the
+        prefill sizes MX4A16_MOE_MIN_ROWS names). With MXFP4 activations x is quantized once for the
         w13 GEMM and h once, after silu_mul, for the w2 GEMM: up to
         MX4A4_MFMA_TOKENS into the bf16 values the codes expand to, for the
         streaming kernel; above it into packed codes for the scaled MFMA.
         Both routes sum the same exact products in f32, so crossing the
         boundary changes the summation order only."""
         if self.mx4_act != "mxfp4":
-            gemm = ops.mx4_moe_gemm
-        elif x.shape[0] <= self.MX4A4_MFMA_TOKENS:
+            return self._forward_routed(
+                x, ops.mx4_moe_gemm, self.mx4_weight("w13"),
+                self.mx4_weight("w2"),
+                (ops.mx4a16_moe_gemm, self.MX4A16_MOE_MIN_ROWS))
+        if x.shape[0] <= self.MX4A4_MFMA_TOKENS:
             def gemm(a, *args, **kw):
                 return ops.mx4_moe_gemm(ops.mx4_quantize_act(a, qdq=True),
                                         *args, **kw)
@@ -751,14 +780,23 @@ class MoEMLP(nn.Module):
         return self._forward_routed(x, gemm, self.mx4_weight("w13"),
                                     self.mx4_weight("w2"))
 
-    def _forward_routed(self, x, gemm, w13, w2):
+    def _forward_routed(self, x, gemm, w13, w2, prefill=None):
         """GPU forward over routed experts (gemm = ops.w4_moe_gemm on the
         packed W4 triples, ops.w8_moe_gemm on the W8 pairs, ops.mx4_moe_gemm
         or ops.mx4a4_moe_gemm on the MX4 pairs, ops.moe_bf16_gemm on the
-        bf16 parameters themselves), the same for every T: route once, then two routed grouped GEMMs that stream only
-        the experts the batch selected. Up to DENSE_TOKENS the launch shapes depend on T alone (no
+        bf16 parameters themselves), the same for every T: route once, then
+        two routed grouped GEMMs that stream only the experts the batch
+        selected. Up to DENSE_TOKENS the launch shapes depend on T alone (no
         host sync; the decode graphs capture it); above it one sync per layer
-        fetches the longest expert list to size the grid."""
+        fetches the longest expert list to size the grid.
+        prefill = (op, min_rows) names the fused-dequant MFMA GEMM of the
+        format (ops.w4a16_moe_gemm / w8a16_moe_gemm / mx4a16_moe_gemm) and
+        its measured rule (W4A16_MOE_MIN_ROWS and its siblings): above
+        DENSE_TOKENS, once the mean list T * k / E has min_rows rows (None:
+        never), both GEMMs run it instead of `gemm` and routed_wqa16_calls
+        advances. It computes the
+        same bf16 weights times the same activations in f32, in another
+        summation order."""
         from ..parallel.comm import tp_all_reduce
 
         T, k = x.shape[0], self.top_k
@@ -768,6 +806,11 @@ class MoEMLP(nn.Module):
                                       self.local_experts)
         max_rows = (T if T <= self.DENSE_TOKENS
                     else max(1, int(counts.max().item())))
+        if (prefill is not None and T > self.DENSE_TOKENS
+                and prefill[1] is not None
+                and T * k >= prefill[1] * self.num_experts):
+            gemm = prefill[0]
+            self.routed_wqa16_calls += 1
         gu = gemm(x, w13, counts, pairs, k, max_rows)      # [T*k, 2I]
         h = ops.silu_mul(gu)                               # [T*k, I]
         # y row 0 is a zero row: the pairs of experts other ranks own are
@@ -793,13 +836,15 @@ class MoEMLP(nn.Module):
 
     def forward(self, x):
         if self.w4 and x.is_cuda:
-            return self._forward_routed(x, ops.w4_moe_gemm,
-                                        self.w4_packed("w13"),
-                                        self.w4_packed("w2"))
+            return self._forward_routed(
+                x, ops.w4_moe_gemm, self.w4_packed("w13"),
+                self.w4_packed("w2"),
+                (ops.w4a16_moe_gemm, self.W4A16_MOE_MIN_ROWS))
         if self.w8 and x.is_cuda:
-            return self._forward_routed(x, ops.w8_moe_gemm,
-                                        self.w8_weight("w13"),
-                                        self.w8_weight("w2"))
+            return self._forward_routed(
+                x, ops.w8_moe_gemm, self.w8_weight("w13"),
+                self.w8_weight("w2"),
+                (ops.w8a16_moe_gemm, self.W8A16_MOE_MIN_ROWS))
         if self.mx4 and x.is_cuda:
             return self._forward_mx4(x)
         T = x.shape[0]

@@ -1357,6 +1357,92 @@ def mx4a4_moe_gemm(xq, xs, weight, counts, pairs, src_div: int,
     return out
 
 
+# wqa16_moe_mfma_gemm_kernel's workgroups take 128 rows of an expert's list
+# once max_rows >= 128 and the 128-row grid still has this many workgroups,
+# else 64. MEASURED with scripts/bench_{w4,w8,mx4}_moe.py (whole block, eager
+# us, 64 vs 128 rows forced; profiles/*_moe.md): wherever a list reaches 128
+# rows the 128-row tile is faster, e.g. W8 mixtral-8x7b T=512 1150 vs 845,
+# T=2048 3648 vs 2458, qwen3-30b-a3b T=2048 662 vs 539; MX4 mixtral T=512 940
+# vs 775. 512 is the smallest 128-row grid among them (mixtral T=512, w2: 32
+# N tiles x 8 experts x 2 slabs); no smaller one was measured.
+_WQA16_MOE_TILE128_MIN_WGS = 512
+# Grid order of wqa16_moe_mfma_gemm_kernel: True puts the slabs of one
+# (expert, N tile) next to each other instead of the N tiles. MEASURED slower
+# (profiles/w4_moe.md section 5); only the benchmark scripts set it.
+_WQA16_MOE_SLAB_MAJOR = False
+_WQA16_MOE_KDIV = {"w4": 8, "w8": 1, "mx4": 2}  # K / last dim of the weight
+
+
+def _wqa16_moe_gemm(name: str, a, weight, counts, pairs, src_div, max_rows,
+                    out, mtile):
+    what = name + "a16_moe_gemm"
+    if mtile not in (None, 64, 128):
+        raise ValueError(f"mtile must be 64 or 128, got {mtile}")
+    if not a.is_cuda:
+        return getattr(ref, name + "_moe_gemm")(a, weight, counts, pairs,
+                                                src_div, out=out)
+    w = weight[0]
+    E, N = (w.shape[0], w.shape[1]) if w.dim() == 3 else (0, 0)
+    K = w.shape[2] * _WQA16_MOE_KDIV[name] if w.dim() == 3 else 0
+    if (a.dim() != 2 or a.dtype != torch.bfloat16 or E < 1 or a.shape[1] != K
+            or N % 64 != 0 or K % 128 != 0 or pairs.dim() != 2
+            or tuple(counts.shape) != (E,) or pairs.shape[0] != E):
+        raise ValueError(
+            f"{what} needs a bf16 input [rows, K], stacked experts [E, N, "
+            f"K] with N % 64 == 0 and K % 128 == 0, counts [E] and pairs "
+            f"[E, T], got a {tuple(a.shape)} {a.dtype}, weight "
+            f"{[tuple(t.shape) for t in weight]}, counts "
+            f"{tuple(counts.shape)}, pairs {tuple(pairs.shape)}")
+    T = pairs.shape[1]
+    top_k = a.shape[0] * src_div // max(T, 1)
+    if out is None:
+        out = torch.empty((T * top_k, N), dtype=torch.bfloat16,
+                          device=a.device)
+    if not a.is_contiguous() or a.data_ptr() % 16 != 0:
+        a = a.contiguous()
+    if mtile is None:
+        wgs = -(-N // 128) * E * -(-max_rows // 128)
+        mtile = (128 if max_rows >= 128 and wgs >= _WQA16_MOE_TILE128_MIN_WGS
+                 else 64)
+    getattr(_native(), what)(out, a, *weight, counts, pairs, top_k, src_div,
+                             max_rows, mtile, int(_WQA16_MOE_SLAB_MAJOR))
+    return out
+
+
+def w4a16_moe_gemm(a, packed, counts, pairs, src_div: int, max_rows: int,
+                   out=None, mtile: int | None = None):
+    """w4_moe_gemm for prefill-sized batches on the bf16 matrix instruction
+    (wqa16_moe_mfma_gemm_kernel): for every local expert e and every p in
+    pairs[e][:counts[e]], out[p] = a[p // src_div] @ bf16(dequant(W[e]))^T,
+    the weight tile decoded in LDS once per mtile rows of an expert's list
+    (bit-equal to w4_dequant), f32 accumulation, one rounding to bf16. N % 64
+    == 0 and K % 128 == 0, anything else raises. Same table arguments and
+    capture rules as w4_moe_gemm; the grid is (ceil(N/128), E_local,
+    ceil(max_rows/mtile)). mtile is for tests only (128 or 64); None takes
+    128 once max_rows >= 128 and the 128-row grid has
+    _WQA16_MOE_TILE128_MIN_WGS workgroups. On CPU: ref.w4_moe_gemm."""
+    return _wqa16_moe_gemm("w4", a, packed, counts, pairs, src_div, max_rows,
+                           out, mtile)
+
+
+def w8a16_moe_gemm(a, weight, counts, pairs, src_div: int, max_rows: int,
+                   out=None, mtile: int | None = None):
+    """w4a16_moe_gemm for stacked W8 experts (w8 e4m3fn [E, N, K], scales f32
+    [E, K/128, N]); the tile in LDS is bit-equal to w8_dequant. On CPU:
+    ref.w8_moe_gemm."""
+    return _wqa16_moe_gemm("w8", a, weight, counts, pairs, src_div, max_rows,
+                           out, mtile)
+
+
+def mx4a16_moe_gemm(a, weight, counts, pairs, src_div: int, max_rows: int,
+                    out=None, mtile: int | None = None):
+    """w4a16_moe_gemm for stacked MX4 experts (mx4 u8 [E, N, K/2], scales u8
+    [E, N, K/32]) with bf16 activations; the tile in LDS is bit-equal to
+    mx4_dequant (exact). On CPU: ref.mx4_moe_gemm."""
+    return _wqa16_moe_gemm("mx4", a, weight, counts, pairs, src_div, max_rows,
+                           out, mtile)
+
+
 def moe_bf16_supported(K: int, N: int) -> bool:
     """Whether moe_bf16_gemm_kernel takes an expert GEMM with K inputs and N
     outputs: its N tile is 128 columns wide and it walks K in chunks of 64."""

@@ -192,6 +192,24 @@ void arks_mx4a16_mfma_gemm(void* out, const void* x, const void* w,
                            const void* scales, const void* bias, int m_rows,
                            int n_total, int k_total, int64_t x_stride,
                            int mtile, hipStream_t stream);
+void arks_w4a16_moe_mfma_gemm(void* out, const void* a, const void* qw,
+                              const void* scales, const void* zeros,
+                              const void* counts, const void* pairs,
+                              int n_experts, int t_cols, int n_pairs,
+                              int src_div, int slabs, int n_total, int k_total,
+                              int mtile, int slab_major, hipStream_t stream);
+void arks_w8a16_moe_mfma_gemm(void* out, const void* a, const void* w8,
+                              const void* scales, const void* counts,
+                              const void* pairs, int n_experts, int t_cols,
+                              int n_pairs, int src_div, int slabs, int n_total,
+                              int k_total, int mtile, int slab_major,
+                              hipStream_t stream);
+void arks_mx4a16_moe_mfma_gemm(void* out, const void* a, const void* w,
+                               const void* scales, const void* counts,
+                               const void* pairs, int n_experts, int t_cols,
+                               int n_pairs, int src_div, int slabs,
+                               int n_total, int k_total, int mtile,
+                               int slab_major, hipStream_t stream);
 void arks_moe_bf16_gemm(void* out, const void* a, const void* w,
                         const void* counts, const void* pairs, int n_experts,
                         int t_cols, int n_pairs, int src_div, int slabs,
@@ -1278,6 +1296,147 @@ void mx4a4_moe_gemm(torch::Tensor out, torch::Tensor xq, torch::Tensor xs,
                          (int)n, (int)k, (int)mtile, current_stream());
 }
 
+// Everything the routed fused-dequant MFMA GEMMs (wqa16_moe_mfma_gemm_kernel)
+// check that does not depend on the weight format, for E stacked experts
+// [n, k] on `dev`: a bf16 [rows, K] contiguous, out bf16 [T*k, N], the
+// routing table, mtile = 128 or 64 rows of an expert's list per workgroup.
+// The table's contents are clamped to these extents in the kernel. Returns
+// (T, slabs).
+std::array<int64_t, 2> check_wqa16_moe(
+    const torch::Tensor& out, const torch::Tensor& a,
+    const torch::Tensor& counts, const torch::Tensor& pairs, int64_t ne,
+    int64_t n, int64_t k, const at::Device& dev, int64_t top_k,
+    int64_t src_div, int64_t max_rows, int64_t mtile) {
+  TORCH_CHECK(mtile == 128 || mtile == 64, "mtile must be 128 or 64");
+  TORCH_CHECK(ne >= 1 && ne <= 65535, "need 1 <= E_local <= 65535");
+  TORCH_CHECK(k >= 128 && k % 128 == 0, "needs K % 128 == 0, got K=", k);
+  TORCH_CHECK(n >= 64 && n % 64 == 0, "needs N % 64 == 0, got N=", n);
+  // a weight tile's 32-bit lane offsets span 128 rows of K elements
+  TORCH_CHECK(k < (int64_t)1 << 24 && n < (int64_t)1 << 23,
+              "needs K below 2^24 and N below 2^23");
+  check_bf16_contig(a, "a");
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(a.dim() == 2 && a.size(1) == k && a.device() == dev &&
+              reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "a must be bf16 [rows, K] on the weight's GPU, 16 B aligned, "
+              "got ", a.sizes());
+  // the kernel gathers rows of a by 32-bit element offsets
+  TORCH_CHECK(a.numel() <= (int64_t)1 << 32,
+              "a must end within 2^32 elements, got ", a.sizes());
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == torch::kInt32 &&
+              counts.is_contiguous() && counts.dim() == 1 &&
+              counts.size(0) == ne && counts.device() == dev,
+              "counts must be int32 [E_local] on GPU");
+  TORCH_CHECK(pairs.is_cuda() && pairs.scalar_type() == torch::kInt32 &&
+              pairs.is_contiguous() && pairs.dim() == 2 &&
+              pairs.size(0) == ne && pairs.size(1) >= 1 &&
+              pairs.device() == dev,
+              "pairs must be int32 [E_local, T] on GPU, got ", pairs.sizes());
+  const int64_t t_cols = pairs.size(1);
+  TORCH_CHECK(top_k >= 1, "top_k must be >= 1");
+  const int64_t n_pairs = t_cols * top_k;
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == n && out.size(0) == n_pairs &&
+              out.device() == dev &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "out must be [T*k, N] = [", n_pairs, ", ", n, "], got ",
+              out.sizes());
+  TORCH_CHECK(n_pairs < ((int64_t)1 << 31) / 2);
+  TORCH_CHECK(src_div >= 1 && a.size(0) * src_div >= n_pairs,
+              "a has ", a.size(0), " rows, too few for ", n_pairs,
+              " pairs at src_div=", src_div);
+  TORCH_CHECK(max_rows >= 1 && max_rows <= t_cols,
+              "need 1 <= max_rows <= T, got ", max_rows);
+  const int64_t slabs = (max_rows + mtile - 1) / mtile;
+  TORCH_CHECK(slabs <= 65535 && (n + 127) / 128 <= 65535,
+              "max_rows or N too large");
+  return {t_cols, slabs};
+}
+
+// The routed grouped GEMMs with the weight decoded inside the MFMA kernel
+// (wqa16_moe_mfma_gemm_kernel), for prefill-sized batches: the arguments of
+// w4_moe_gemm / w8_moe_gemm / mx4_moe_gemm plus mtile. slab_major = 1 selects
+// the other grid order, for the benchmark scripts only.
+void w4a16_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor qw,
+                    torch::Tensor scales, torch::Tensor zeros,
+                    torch::Tensor counts, torch::Tensor pairs, int64_t top_k,
+                    int64_t src_div, int64_t max_rows, int64_t mtile,
+                    int64_t slab_major) {
+  TORCH_CHECK(qw.is_cuda() && qw.scalar_type() == torch::kInt32 &&
+              qw.dim() == 3 && qw.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(qw.data_ptr()) % 16 == 0,
+              "qweight must be contiguous int32 [E, N, K/8] on GPU");
+  const int64_t ne = qw.size(0), n = qw.size(1), k = qw.size(2) * 8;
+  const auto dev = qw.device();
+  const auto [t_cols, slabs] = check_wqa16_moe(
+      out, a, counts, pairs, ne, n, k, dev, top_k, src_div, max_rows, mtile);
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kFloat16 &&
+              scales.is_contiguous() && scales.dim() == 3 &&
+              scales.size(0) == ne && scales.size(1) == k / 128 &&
+              scales.size(2) == n && scales.device() == dev,
+              "scales must be contiguous f16 [E, K/128, N] on GPU");
+  TORCH_CHECK(zeros.is_cuda() && zeros.scalar_type() == torch::kUInt8 &&
+              zeros.is_contiguous() && zeros.dim() == 3 &&
+              zeros.size(0) == ne && zeros.size(1) == k / 128 &&
+              zeros.size(2) == n && zeros.device() == dev,
+              "zeros must be contiguous uint8 [E, K/128, N] on GPU");
+  arks_w4a16_moe_mfma_gemm(out.data_ptr(), a.data_ptr(), qw.data_ptr(),
+                           scales.data_ptr(), zeros.data_ptr(),
+                           counts.data_ptr(), pairs.data_ptr(), (int)ne,
+                           (int)t_cols, (int)(t_cols * top_k), (int)src_div,
+                           (int)slabs, (int)n, (int)k, (int)mtile,
+                           (int)(slab_major != 0), current_stream());
+}
+
+void w8a16_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w8,
+                    torch::Tensor scales, torch::Tensor counts,
+                    torch::Tensor pairs, int64_t top_k, int64_t src_div,
+                    int64_t max_rows, int64_t mtile, int64_t slab_major) {
+  TORCH_CHECK(w8.is_cuda() && w8.scalar_type() == at::kFloat8_e4m3fn &&
+              w8.dim() == 3 && w8.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(w8.data_ptr()) % 16 == 0,
+              "w8 weight must be contiguous float8_e4m3fn [E, N, K] on GPU");
+  const int64_t ne = w8.size(0), n = w8.size(1), k = w8.size(2);
+  const auto dev = w8.device();
+  const auto [t_cols, slabs] = check_wqa16_moe(
+      out, a, counts, pairs, ne, n, k, dev, top_k, src_div, max_rows, mtile);
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kFloat32 &&
+              scales.is_contiguous() && scales.dim() == 3 &&
+              scales.size(0) == ne && scales.size(1) == k / 128 &&
+              scales.size(2) == n && scales.device() == dev,
+              "scales must be contiguous f32 [E, K/128, N] on GPU");
+  arks_w8a16_moe_mfma_gemm(out.data_ptr(), a.data_ptr(), w8.data_ptr(),
+                           scales.data_ptr(), counts.data_ptr(),
+                           pairs.data_ptr(), (int)ne, (int)t_cols,
+                           (int)(t_cols * top_k), (int)src_div, (int)slabs,
+                           (int)n, (int)k, (int)mtile,
+                           (int)(slab_major != 0), current_stream());
+}
+
+void mx4a16_moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
+                     torch::Tensor scales, torch::Tensor counts,
+                     torch::Tensor pairs, int64_t top_k, int64_t src_div,
+                     int64_t max_rows, int64_t mtile, int64_t slab_major) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kUInt8 &&
+              w.dim() == 3 && w.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "mx4 weight must be contiguous uint8 [E, N, K/2] on GPU");
+  const int64_t ne = w.size(0), n = w.size(1), k = w.size(2) * 2;
+  const auto dev = w.device();
+  const auto [t_cols, slabs] = check_wqa16_moe(
+      out, a, counts, pairs, ne, n, k, dev, top_k, src_div, max_rows, mtile);
+  TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kUInt8 &&
+              scales.is_contiguous() && scales.dim() == 3 &&
+              scales.size(0) == ne && scales.size(1) == n &&
+              scales.size(2) == k / 32 && scales.device() == dev,
+              "mx4 scales must be contiguous uint8 [E, N, K/32] on GPU");
+  arks_mx4a16_moe_mfma_gemm(out.data_ptr(), a.data_ptr(), w.data_ptr(),
+                            scales.data_ptr(), counts.data_ptr(),
+                            pairs.data_ptr(), (int)ne, (int)t_cols,
+                            (int)(t_cols * top_k), (int)src_div, (int)slabs,
+                            (int)n, (int)k, (int)mtile,
+                            (int)(slab_major != 0), current_stream());
+}
+
 // The same over stacked bf16 experts as the model holds them
 // (moe_bf16_gemm_kernel, moe_gemm.hip): w bf16 [E, K, N], N contiguous.
 void moe_bf16_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
@@ -1948,6 +2107,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mx4a4_gemm", &mx4a4_gemm);
   m.def("mx4_moe_gemm", &mx4_moe_gemm);
   m.def("mx4a4_moe_gemm", &mx4a4_moe_gemm);
+  m.def("w4a16_moe_gemm", &w4a16_moe_gemm);
+  m.def("w8a16_moe_gemm", &w8a16_moe_gemm);
+  m.def("mx4a16_moe_gemm", &mx4a16_moe_gemm);
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm);
   m.def("splitk_rope_and_cache", &splitk_rope_and_cache, py::arg("positions"),
         py::arg("part"), py::arg("bias"), py::arg("q_out"), py::arg("k_cache"),

@@ -155,6 +155,13 @@ struct WaW4 {
     const uint16_t* scales;  // [K/128, N] f16
     const uint8_t* zeros;    // [K/128, N]
   };
+  // The tensors of expert e of a stack [E, ...] (64-bit offsets; scales and
+  // zeros are [E, K/128, N]).
+  static __device__ __forceinline__ Args expert(const Args& w, const int e,
+                                                const int n, const int k) {
+    const int64_t g = (int64_t)e * (k / 128) * n;
+    return {w.qw + (int64_t)e * n * (k / 8), w.scales + g, w.zeros + g};
+  }
   // thread t: quarter t % 4 (4 words = 32 k) of rows t / 4 + 64 i
   wa_u32x4 q[LOADS];
   uint16_t sc[LOADS];
@@ -221,6 +228,11 @@ struct WaW8 {
     const uint8_t* w8;    // [N, K] e4m3fn
     const float* scales;  // [K/128, N]
   };
+  static __device__ __forceinline__ Args expert(const Args& w, const int e,
+                                                const int n, const int k) {
+    return {w.w8 + (int64_t)e * n * k,
+            w.scales + (int64_t)e * (k / 128) * n};
+  }
   // thread t: piece t % 8 (16 B = 16 k) of rows t / 8 + 32 i
   wa_u32x4 q[LOADS];
   float sc[LOADS];
@@ -279,6 +291,11 @@ struct WaMx4 {
     const uint8_t* w;       // [N, K/2] e2m1 pairs
     const uint8_t* scales;  // [N, K/32] e8m0
   };
+  static __device__ __forceinline__ Args expert(const Args& w, const int e,
+                                                const int n, const int k) {
+    return {w.w + (int64_t)e * n * (k / 2),
+            w.scales + (int64_t)e * n * (k / 32)};
+  }
   // thread t: MX block t % 4 (16 B = 32 k) of rows t / 4 + 64 i
   wa_u32x4 q[LOADS];
   uint8_t sc[LOADS];
@@ -349,6 +366,22 @@ struct WaActs {
       const int r = threadIdx.x / 16 + 16 * i;
       off[i] = wa_clamped(m0, r, m_rows) * (uint32_t)x_stride;
       ok[i] = m0 + r < m_rows;
+    }
+  }
+
+  // Gathered rows (wqa16_moe_mfma_gemm_kernel): tile row i is row prow[i] /
+  // src_div of the contiguous a [., K], live while i < rows. 32-bit element
+  // offsets against the uniform base a: the bindings keep a within 2^32
+  // elements.
+  __device__ __forceinline__ WaActs(const bf16* a, const int* prow,
+                                    const int rows, const int src_div,
+                                    const int k_total) {
+    base = a + 8 * (threadIdx.x % 16);
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      const int r = threadIdx.x / 16 + 16 * i;
+      off[i] = (uint32_t)(prow[r] / src_div) * (uint32_t)k_total;
+      ok[i] = r < rows;
     }
   }
 
@@ -426,48 +459,18 @@ __device__ __forceinline__ wa_bf16x8 wa_as_bf16(const wa_u32x4 v) {
   return c.b;
 }
 
-// One workgroup tile. TAIL: the tile reaches past M or N.
-template <typename F, int MT, bool TAIL>
-__device__ __forceinline__ void wa_tile(
-    wa_u32x4* lds, bf16* __restrict__ out, const bf16* __restrict__ x,
-    const typename F::Args& w, const bf16* __restrict__ bias,
-    const int m_rows, const int n_total, const int k_total,
-    const int64_t x_stride) {
-  constexpr int TM = MT / 32;                      // 16-row tiles per wave
+// The K loop of a workgroup tile, shared by the dense and the routed kernel:
+// wave (wm, wn) adds the products of its MT/2 x 64 part to acc, the weight
+// rows coming from wst and the activation rows from xst.
+template <bool TAIL, typename F, int MT>
+__device__ __forceinline__ void wa_k_loop(wa_f32x4 (&acc)[4][MT / 32],
+                                          wa_u32x4* lds, F& wst,
+                                          WaActs<MT>& xst, const int nkb,
+                                          const int wm, const int wn,
+                                          const int r, const int g) {
+  constexpr int TM = MT / 32;
   constexpr int STAGE = (WA_NT + MT) * WA_UNITS;  // 16 B units of one buffer
   constexpr int VALU = (F::PART_VALU + 4 * TM - 1) / (4 * TM);
-
-  const int lane = threadIdx.x % WAVE_SIZE;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE_SIZE);
-  const int r = lane % 16, g = lane / 16;
-  const int wm = wave / 2, wn = wave % 2;
-  const int n0 = blockIdx.x * WA_NT, m0 = blockIdx.y * MT;
-  const int nw0 = n0 + 64 * wn;        // this wave's first column
-  const int mw0 = m0 + (MT / 2) * wm;  // and first row
-  const bool active = nw0 < n_total;   // wave-uniform
-  const int nkb = k_total / WA_KB;
-
-  // acc[j][t][v] = out[mw0 + 16 t + r][nw0 + 16 j + 4 g + v], starting from
-  // the bias
-  wa_f32x4 acc[4][TM];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < TM; ++t) acc[j][t] = wa_f32x4{0.f, 0.f, 0.f, 0.f};
-  if (bias != nullptr && active) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const ushort4v bv =
-          *reinterpret_cast<const ushort4v*>(bias + nw0 + 16 * j + 4 * g);
-#pragma unroll
-      for (int t = 0; t < TM; ++t)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[j][t][v] = bf16_bits_to_float(bv[v]);
-    }
-  }
-
-  F wst(w, n0, n_total, k_total);
-  WaActs<MT> xst(x, m0, m_rows, x_stride);
   wa_load_all(wst, 0);
   wa_load_all(xst, 0);
   // stage 0 into buffer 0, every slot refilled for stage 1
@@ -518,6 +521,49 @@ __device__ __forceinline__ void wa_tile(
     wa_schedule_step<0, 4 * TM, VALU>();
     wa_barrier();  // cur may be overwritten, nxt is complete
   }
+}
+
+// One workgroup tile. TAIL: the tile reaches past M or N.
+template <typename F, int MT, bool TAIL>
+__device__ __forceinline__ void wa_tile(
+    wa_u32x4* lds, bf16* __restrict__ out, const bf16* __restrict__ x,
+    const typename F::Args& w, const bf16* __restrict__ bias,
+    const int m_rows, const int n_total, const int k_total,
+    const int64_t x_stride) {
+  constexpr int TM = MT / 32;  // 16-row tiles per wave
+
+  const int lane = threadIdx.x % WAVE_SIZE;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE_SIZE);
+  const int r = lane % 16, g = lane / 16;
+  const int wm = wave / 2, wn = wave % 2;
+  const int n0 = blockIdx.x * WA_NT, m0 = blockIdx.y * MT;
+  const int nw0 = n0 + 64 * wn;        // this wave's first column
+  const int mw0 = m0 + (MT / 2) * wm;  // and first row
+  const bool active = nw0 < n_total;   // wave-uniform
+  const int nkb = k_total / WA_KB;
+
+  // acc[j][t][v] = out[mw0 + 16 t + r][nw0 + 16 j + 4 g + v], starting from
+  // the bias
+  wa_f32x4 acc[4][TM];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int t = 0; t < TM; ++t) acc[j][t] = wa_f32x4{0.f, 0.f, 0.f, 0.f};
+  if (bias != nullptr && active) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const ushort4v bv =
+          *reinterpret_cast<const ushort4v*>(bias + nw0 + 16 * j + 4 * g);
+#pragma unroll
+      for (int t = 0; t < TM; ++t)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc[j][t][v] = bf16_bits_to_float(bv[v]);
+    }
+  }
+
+  F wst(w, n0, n_total, k_total);
+  WaActs<MT> xst(x, m0, m_rows, x_stride);
+  wa_k_loop<TAIL>(acc, lds, wst, xst, nkb, wm, wn, r, g);
   if (!active) return;
 
 #pragma unroll
@@ -554,6 +600,124 @@ __global__ __launch_bounds__(256) void wqa16_mfma_gemm_kernel(
                          x_stride);
 }
 
+// ---- routed experts --------------------------------------------------------
+// The same tile over the routed experts of an MoE block, for prefill-sized
+// batches:
+//   for e < E_local, i < counts[e], p = pairs[e][i]:
+//     out[p, :] = a[p / src_div, :] @ bf16(dequant(W[e]))^T
+// with the experts stacked as MoEMLP holds them (a leading E on every tensor
+// of the format; W4 / W8 scales and zeros are [E, K/128, N]). The decoders,
+// the swizzled double-buffered tile, the K loop with its four-part decode
+// interleave and the schedule hints are the dense kernel's (wa_k_loop); a
+// weight is decoded once per MT rows of an expert's list instead of once per
+// 64 as in the streaming kernels. What differs:
+//   Work split. A workgroup owns rows [slab MT, slab MT + MT) of expert e's
+//   list times 128 columns. counts[e] is clamped to [0, t_cols]; a workgroup
+//   whose slab starts at or past it returns at once (uniform, before any
+//   barrier), so the grid is sized by the longest list alone.
+//   Grid order. grid = (ceil(N/128), E_local, slabs), N tiles fastest, as in
+//   mx4_moe_mfma_gemm_kernel. slab_major = 1 is (slabs, ceil(N/128),
+//   E_local): the workgroups that decode the same weight tile (one expert,
+//   one N tile) dispatched next to each other, so that they would share it in
+//   a cache. MEASURED slower (profiles/w4_moe.md section 5: W4 block, 128-row
+//   tiles, mixtral-8x7b T=512 1164 vs 1029 us, T=2048 2645 vs 2600;
+//   qwen3-30b-a3b T=2048 707 vs 596), so nothing but the benchmark scripts
+//   selects it. Consecutive workgroups go to different XCDs, each with an L2
+//   of its own, so neighbours in the grid do not share one; whether that is
+//   the cause was not measured.
+//   Row table. prow[i] in LDS is the pair (= output row) of tile row i, read
+//   from pairs[e] and clamped to [0, n_pairs); entries past the end of the
+//   list repeat its last pair, so no table read and no gather leaves its
+//   tensor, whatever the table holds.
+//   Gather. Tile row i is row prow[i] / src_div of a (src_div = top_k reads
+//   the token's row for the w13 GEMM, 1 the pair's own row of h for w2):
+//   WaActs keeps one 32-bit element offset per staging load against the
+//   uniform base a (the bindings keep a within 2^32 elements). Tile rows at or
+//   past the slab's length are staged as zeros (TAIL), as weight rows past N.
+//   Epilogue. No bias: the accumulators start at zero. Tile row i < rows is
+//   rounded to bf16 and stored to out[prow[i]] as 8 B vectors. Rows of out
+//   that belong to no local expert are not written.
+// No split-K, no atomics: a given (shape, table, mtile) always sums in the
+// same order, which is the dense kernel's, so a row's result is that of
+// wqa16_mfma_gemm_kernel on the same row and expert.
+template <typename F, int MT, bool TAIL>
+__device__ __forceinline__ void wa_moe_tile(
+    wa_u32x4* lds, const int* prow, bf16* __restrict__ out,
+    const bf16* __restrict__ a, const typename F::Args& we, const int rows,
+    const int n0, const int src_div, const int n_total, const int k_total) {
+  constexpr int TM = MT / 32;  // 16-row tiles per wave
+
+  const int lane = threadIdx.x % WAVE_SIZE;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE_SIZE);
+  const int r = lane % 16, g = lane / 16;
+  const int wm = wave / 2, wn = wave % 2;
+  const int nw0 = n0 + 64 * wn;       // this wave's first column
+  const int mw0 = (MT / 2) * wm;      // and first tile row
+  const bool active = nw0 < n_total;  // wave-uniform
+
+  wa_f32x4 acc[4][TM];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int t = 0; t < TM; ++t) acc[j][t] = wa_f32x4{0.f, 0.f, 0.f, 0.f};
+
+  F wst(we, n0, n_total, k_total);
+  WaActs<MT> xst(a, prow, rows, src_div, k_total);
+  wa_k_loop<TAIL>(acc, lds, wst, xst, k_total / WA_KB, wm, wn, r, g);
+  if (!active) return;
+
+  // acc[j][t][v] = out[prow[mw0 + 16 t + r]][nw0 + 16 j + 4 g + v]
+#pragma unroll
+  for (int t = 0; t < TM; ++t) {
+    const int m = mw0 + 16 * t + r;
+    if (TAIL && m >= rows) continue;
+    bf16* orow = out + (int64_t)prow[m] * n_total + nw0 + 4 * g;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ushort4v o;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) o[v] = float_to_bf16_bits(acc[j][t][v]);
+      *reinterpret_cast<ushort4v*>(orow + 16 * j) = o;
+    }
+  }
+}
+
+template <typename F, int MT>
+__global__ __launch_bounds__(256) void wqa16_moe_mfma_gemm_kernel(
+    bf16* __restrict__ out,          // [n_pairs, N]
+    const bf16* __restrict__ a,      // [>= ceil(n_pairs / src_div), K]
+    const typename F::Args w,        // the stacked experts' tensors
+    const int* __restrict__ counts,  // [E]
+    const int* __restrict__ pairs,   // [E, t_cols]
+    const int t_cols, const int n_pairs, const int src_div,
+    const int n_total, const int k_total, const int slab_major) {
+  const int slab = slab_major ? blockIdx.x : blockIdx.z;
+  const int nt = slab_major ? blockIdx.y : blockIdx.x;
+  const int e = slab_major ? blockIdx.z : blockIdx.y;
+  const int cnt = min(max(counts[e], 0), t_cols);
+  const int r0 = slab * MT;
+  if (r0 >= cnt) return;  // uniform
+  const int rows = min(cnt - r0, MT);
+
+  __shared__ wa_u32x4 lds[2 * (WA_NT + MT) * WA_UNITS];
+  __shared__ int prow[MT];
+  if (threadIdx.x < MT) {
+    const int p = pairs[(int64_t)e * t_cols + r0 + min((int)threadIdx.x,
+                                                       rows - 1)];
+    prow[threadIdx.x] = min(max(p, 0), n_pairs - 1);
+  }
+  wa_barrier();
+
+  const typename F::Args we = F::expert(w, e, n_total, k_total);
+  // workgroup-uniform: full tiles carry no tail code
+  if ((nt + 1) * WA_NT <= n_total && rows == MT)
+    wa_moe_tile<F, MT, false>(lds, prow, out, a, we, rows, nt * WA_NT,
+                              src_div, n_total, k_total);
+  else
+    wa_moe_tile<F, MT, true>(lds, prow, out, a, we, rows, nt * WA_NT, src_div,
+                             n_total, k_total);
+}
+
 }  // namespace arks
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -580,6 +744,64 @@ static void wqa16_launch(void* out, const void* x, const typename F::Args& w,
     launch(wqa16_mfma_gemm_kernel<F, 128>);
   else
     launch(wqa16_mfma_gemm_kernel<F, 64>);
+}
+
+// mtile: 128 or 64 (the bindings check), slabs = ceil(max_rows / mtile).
+// grid = (ceil(N/128), E_local, slabs), or (slabs, ceil(N/128), E_local)
+// with slab_major = 1.
+template <typename F>
+static void wqa16_moe_launch(void* out, const void* a,
+                             const typename F::Args& w, const void* counts,
+                             const void* pairs, int n_experts, int t_cols,
+                             int n_pairs, int src_div, int slabs, int n_total,
+                             int k_total, int mtile, int slab_major,
+                             hipStream_t stream) {
+  const unsigned ntiles = (unsigned)((n_total + WA_NT - 1) / WA_NT);
+  const dim3 grid = slab_major ? dim3(slabs, ntiles, n_experts)
+                               : dim3(ntiles, n_experts, slabs),
+             block(256);
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, (bf16*)out,
+                       (const bf16*)a, w, (const int*)counts,
+                       (const int*)pairs, t_cols, n_pairs, src_div, n_total,
+                       k_total, slab_major);
+  };
+  if (mtile == 128)
+    launch(wqa16_moe_mfma_gemm_kernel<F, 128>);
+  else
+    launch(wqa16_moe_mfma_gemm_kernel<F, 64>);
+}
+
+extern "C" void arks_w4a16_moe_mfma_gemm(
+    void* out, const void* a, const void* qw, const void* scales,
+    const void* zeros, const void* counts, const void* pairs, int n_experts,
+    int t_cols, int n_pairs, int src_div, int slabs, int n_total, int k_total,
+    int mtile, int slab_major, hipStream_t stream) {
+  wqa16_moe_launch<WaW4>(out, a,
+                         {(const uint32_t*)qw, (const uint16_t*)scales,
+                          (const uint8_t*)zeros},
+                         counts, pairs, n_experts, t_cols, n_pairs, src_div,
+                         slabs, n_total, k_total, mtile, slab_major, stream);
+}
+
+extern "C" void arks_w8a16_moe_mfma_gemm(
+    void* out, const void* a, const void* w8, const void* scales,
+    const void* counts, const void* pairs, int n_experts, int t_cols,
+    int n_pairs, int src_div, int slabs, int n_total, int k_total, int mtile,
+    int slab_major, hipStream_t stream) {
+  wqa16_moe_launch<WaW8>(out, a, {(const uint8_t*)w8, (const float*)scales},
+                         counts, pairs, n_experts, t_cols, n_pairs, src_div,
+                         slabs, n_total, k_total, mtile, slab_major, stream);
+}
+
+extern "C" void arks_mx4a16_moe_mfma_gemm(
+    void* out, const void* a, const void* w, const void* scales,
+    const void* counts, const void* pairs, int n_experts, int t_cols,
+    int n_pairs, int src_div, int slabs, int n_total, int k_total, int mtile,
+    int slab_major, hipStream_t stream) {
+  wqa16_moe_launch<WaMx4>(out, a, {(const uint8_t*)w, (const uint8_t*)scales},
+                          counts, pairs, n_experts, t_cols, n_pairs, src_div,
+                          slabs, n_total, k_total, mtile, slab_major, stream);
 }
 
 extern "C" void arks_w4a16_mfma_gemm(void* out, const void* x, const void* qw,

@@ -7,7 +7,11 @@ One MoE block (MoEMLP.forward: router, experts, mix) of the qwen3-30b-a3b and
 mixtral-8x7b shapes. Paths:
   bf16     the block as an MXFP4 checkpoint's experts were held before MX4
            storage: dequantized to bf16 at load
-  mx4      MX4 experts, bf16 activations (mx4_moe_gemm_kernel at every T)
+  mx4      MX4 experts, bf16 activations (mx4_moe_gemm_kernel at every T,
+           as before the fused-dequant MFMA kernel existed)
+  mx4-64   the same above MoEMLP.DENSE_TOKENS on wqa16_moe_mfma_gemm_kernel
+  mx4-128  forced to 64- / 128-row workgroups (with --grid-orders also
+           mx4-64s / mx4-128s: the grid order (slabs, N tiles, experts))
   a4       MX4 experts, MXFP4 activations, T <= MoEMLP.MX4A4_MFMA_TOKENS
            (quantize-expand, then mx4_moe_gemm_kernel)
   a4-64    the same above it: mx4_moe_mfma_gemm_kernel forced to 64-row
@@ -36,7 +40,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import arks_amd.ops as ops  # noqa: E402
 from arks_amd.config import PRESET_CONFIGS  # noqa: E402
 from bench_w4 import LLC_BYTES, time_eager, time_graph  # noqa: E402
-from bench_w4_moe import BLOCKS  # noqa: E402
+from bench_w4_moe import BLOCKS, quant_paths, run_path  # noqa: E402
 from bench_w4_moe import make_block as make_bf16_block  # noqa: E402
 
 TS = (1, 8, 64, 256, 512, 2048)
@@ -72,9 +76,9 @@ def make_block(cfg, mx4: bool, gen):
     return blk
 
 
-def paths_for(T: int, boundary: int):
-    return ("bf16", "mx4") + (("a4",) if T <= boundary
-                              else ("a4-64", "a4-128"))
+def paths_for(T: int, boundary: int, dense_tokens: int, grid_orders: bool):
+    return (("bf16",) + quant_paths("mx4", T, dense_tokens, grid_orders)
+            + (("a4",) if T <= boundary else ("a4-64", "a4-128")))
 
 
 def run(blk, x, path):
@@ -83,18 +87,19 @@ def run(blk, x, path):
     if path.startswith("a4"):
         blk.mx4_act = "mxfp4"
         ops._MX4A4_TILE128_MIN_WGS = 1 << 30 if path == "a4-64" else 0
-    else:
-        blk.mx4_act = "bf16"
-    return blk(x)
+        return blk(x)
+    blk.mx4_act = "bf16"
+    return run_path(blk, x, path)
 
 
 def bench(args):
     from arks_amd.models.llama_family import MoEMLP
 
     rule = ops._MX4A4_TILE128_MIN_WGS
+    rules = ops._WQA16_MOE_TILE128_MIN_WGS, ops._WQA16_MOE_SLAB_MAJOR
     gen = torch.Generator(device="cuda").manual_seed(0)
     rows = []
-    print(f"{'block':14} {'T':>4} {'path':6} {'mode':5} {'copies':>6} "
+    print(f"{'block':14} {'T':>4} {'path':8} {'mode':5} {'copies':>6} "
           f"{'us':>9} {'min..max':>21} {'touched MB':>10}")
     for name in args.blocks.split(","):
         cfg = PRESET_CONFIGS[name]
@@ -102,7 +107,8 @@ def bench(args):
         for T in map(int, args.ts.split(",")):
             x = torch.randn(T, cfg.hidden_size, dtype=torch.bfloat16,
                             device="cuda", generator=gen)
-            paths = paths_for(T, MoEMLP.MX4A4_MFMA_TOKENS)
+            paths = paths_for(T, MoEMLP.MX4A4_MFMA_TOKENS,
+                              MoEMLP.DENSE_TOKENS, args.grid_orders)
             # the routed kernels read at most the T*k selected experts
             touched = {p: min(E, T * k) * expert_bytes(cfg, p != "bf16")
                        for p in paths}
@@ -141,7 +147,7 @@ def bench(args):
             for p, ts in res.items():
                 med = statistics.median(ts)
                 mode = "graph" if p in graphs else "eager"
-                print(f"{name:14} {T:4d} {p:6} {mode:5} {ncopy[p]:6d} "
+                print(f"{name:14} {T:4d} {p:8} {mode:5} {ncopy[p]:6d} "
                       f"{med:9.1f} {min(ts):10.1f}..{max(ts):<10.1f}"
                       f"{touched[p] / 1e6:10.1f}", flush=True)
                 rows.append({"block": name, "T": T, "path": p, "mode": mode,
@@ -151,6 +157,7 @@ def bench(args):
             del graphs, blocks
             torch.cuda.empty_cache()
     ops._MX4A4_TILE128_MIN_WGS = rule
+    ops._WQA16_MOE_TILE128_MIN_WGS, ops._WQA16_MOE_SLAB_MAJOR = rules
     return rows
 
 
@@ -160,6 +167,7 @@ def main():
     ap.add_argument("--blocks", default=",".join(BLOCKS))
     ap.add_argument("--ts", default=",".join(map(str, TS)))
     ap.add_argument("--max-copies", type=int, default=32)
+    ap.add_argument("--grid-orders", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available() or not ops.native_available():

@@ -8,7 +8,11 @@ kernel: one MoE block (MoEMLP.forward: router, experts, mix) of the
 qwen3-30b-a3b and mixtral-8x7b shapes at T = 1, 8, 64, 256 tokens, the bf16
 block as it stands against the W4 block, inside one captured graph (T above
 MoEMLP.DENSE_TOKENS, e.g. --ts 2048, syncs with the host once per call on
-both paths and is timed eagerly instead). Each path
+both paths and is timed eagerly instead; there the W4 block is timed on
+three routes: "w4" the streaming kernel at every T, as before the
+fused-dequant MFMA kernel existed, "w4-64" / "w4-128" that kernel forced to
+64- / 128-row workgroups, and with --grid-orders "w4-64s" / "w4-128s" the same
+in the grid order (slabs, N tiles, experts) instead of N tiles first). Each path
 cycles through enough copies of the block that the bytes a call touches
 exceed the 256 MB LLC twice over, so every call streams its weights from HBM
 as a decode step does; the two paths alternate within each round and the
@@ -79,10 +83,38 @@ def make_block(cfg, w4: bool, gen):
     return blk
 
 
-def bench_kernel(args):
+def quant_paths(fmt: str, T: int, dense_tokens: int, grid_orders: bool):
+    """The routes of a quantized block at T tokens: the streaming kernel
+    alone up to DENSE_TOKENS; above it also the fused-dequant MFMA kernel at
+    both tile heights (suffix s: the slab-major grid order)."""
+    if T <= dense_tokens:
+        return (fmt,)
+    tiles = ("64", "128") + (("64s", "128s") if grid_orders else ())
+    return (fmt,) + tuple(f"{fmt}-{t}" for t in tiles)
+
+
+def run_path(blk, x, path: str):
+    """One forward of blk on the given route. The MFMA route and its tile
+    height are forced through the rules' constants, the block's only way to
+    the kernel; bench_kernel restores them."""
+    fmt, _, tile = path.partition("-")
+    if fmt != "bf16":
+        setattr(blk, fmt.upper() + "A16_MOE_MIN_ROWS", 1 if tile else None)
+    if tile:
+        ops._WQA16_MOE_TILE128_MIN_WGS = 0 if tile.startswith("128") \
+            else 1 << 30
+        ops._WQA16_MOE_SLAB_MAJOR = tile.endswith("s")
+    return blk(x)
+
+
+def bench_kernel(args, fmt="w4", make=None, nbytes=None):
+    """fmt, make, nbytes: the quantized format's name, make_block and
+    expert_bytes (scripts/bench_w8_moe.py passes its own)."""
+    make, nbytes = make or make_block, nbytes or expert_bytes
+    rules = ops._WQA16_MOE_TILE128_MIN_WGS, ops._WQA16_MOE_SLAB_MAJOR
     gen = torch.Generator(device="cuda").manual_seed(0)
     rows = []
-    print(f"{'block':14} {'T':>4} {'path':5} {'copies':>6} {'us':>9} "
+    print(f"{'block':14} {'T':>4} {'path':7} {'copies':>6} {'us':>9} "
           f"{'min..max':>21} {'touched MB':>10}")
     for name in args.blocks.split(","):
         cfg = PRESET_CONFIGS[name]
@@ -92,14 +124,14 @@ def bench_kernel(args):
                             device="cuda", generator=gen)
             # the bf16 decode path streams every expert; the routed W4 path
             # at most the T*k selected ones
-            touched = {"bf16": E * expert_bytes(cfg, False),
-                       "w4": min(E, T * k) * expert_bytes(cfg, True)}
+            touched = {"bf16": E * nbytes(cfg, False),
+                       fmt: min(E, T * k) * nbytes(cfg, True)}
             graphs, ncopy = {}, {}
             blocks = {}
-            for path in ("bf16", "w4"):
+            for path in ("bf16", fmt):
                 n = min(args.max_copies,
                         max(1, -(-2 * LLC_BYTES // touched[path])))
-                blocks[path] = [make_block(cfg, path == "w4", gen)
+                blocks[path] = [make(cfg, path == fmt, gen)
                                 for _ in range(n)]
                 ncopy[path] = n
                 if T > blocks[path][0].DENSE_TOKENS:
@@ -113,20 +145,26 @@ def bench_kernel(args):
                         for b in blocks[path]:
                             b(x)
                 graphs[path] = g
-            res = {"bf16": [], "w4": []}
+            paths = ("bf16",) + quant_paths(
+                fmt, T, blocks[fmt][0].DENSE_TOKENS, args.grid_orders)
+            for path in paths[2:]:  # further routes of the same blocks
+                blocks[path], ncopy[path] = blocks[fmt], ncopy[fmt]
+                touched[path] = touched[fmt]
+            res = {path: [] for path in paths}
             for _ in range(args.rounds):  # alternate the paths every round
-                for path in ("bf16", "w4"):
+                for path in paths:
                     if path in graphs:
                         t = time_graph(graphs[path], ncopy[path],
                                        max(3, 40 // ncopy[path]))
                     else:
                         with torch.no_grad():
-                            t = time_eager(lambda b: b(x), blocks[path],
+                            t = time_eager(lambda b: run_path(b, x, path),
+                                           blocks[path],
                                            max(3 * ncopy[path], 20))
                     res[path].append(t)
             for path, ts in res.items():
                 med = statistics.median(ts)
-                print(f"{name:14} {T:4d} {path:5} {ncopy[path]:6d} {med:9.1f} "
+                print(f"{name:14} {T:4d} {path:7} {ncopy[path]:6d} {med:9.1f} "
                       f"{min(ts):10.1f}..{max(ts):<10.1f}"
                       f"{touched[path] / 1e6:10.1f}", flush=True)
                 rows.append({"block": name, "T": T, "path": path,
@@ -137,6 +175,7 @@ def bench_kernel(args):
                              "rounds": len(ts)})
             del graphs, blocks
             torch.cuda.empty_cache()
+    ops._WQA16_MOE_TILE128_MIN_WGS, ops._WQA16_MOE_SLAB_MAJOR = rules
     return rows
 
 
@@ -224,6 +263,7 @@ def main():
     ap.add_argument("--blocks", default=",".join(BLOCKS))
     ap.add_argument("--ts", default=",".join(map(str, TS)))
     ap.add_argument("--max-copies", type=int, default=32)
+    ap.add_argument("--grid-orders", action="store_true")
     ap.add_argument("--model", default="qwen3-30b-a3b")
     ap.add_argument("--batches", default="1,8,64,256")
     ap.add_argument("--input-len", type=int, default=128)

@@ -7,7 +7,9 @@ kernel: one MoE block (MoEMLP.forward: router, experts, mix) of the
 qwen3-30b-a3b and mixtral-8x7b shapes at T = 1, 8, 64, 256 tokens, the bf16
 block as it stands against the W8 block, inside one captured graph (T above
 MoEMLP.DENSE_TOKENS, e.g. --ts 2048, syncs with the host once per call on
-both paths and is timed eagerly instead). The method is
+both paths and is timed eagerly instead, the W8 block on the streaming
+route "w8" and on the fused-dequant MFMA route "w8-64" / "w8-128", with
+--grid-orders also "w8-64s" / "w8-128s"). The method, and the loop itself, is
 scripts/bench_w4_moe.py's: each path cycles through enough copies of the
 block that the bytes a call touches exceed the 256 MB LLC twice over, the two
 paths alternate within each round, and the table shows the median and
@@ -25,7 +27,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -36,8 +37,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import arks_amd.ops as ops  # noqa: E402
 from arks_amd.config import PRESET_CONFIGS, EngineConfig  # noqa: E402
-from bench_w4 import LLC_BYTES, time_eager, time_graph  # noqa: E402
 from bench_w4_moe import BLOCKS, TS  # noqa: E402
+from bench_w4_moe import bench_kernel as bench_w4_kernel  # noqa: E402
 from bench_w4_moe import make_block as make_bf16_or_w4_block  # noqa: E402
 
 
@@ -76,64 +77,7 @@ def make_block(cfg, w8: bool, gen):
 
 
 def bench_kernel(args):
-    gen = torch.Generator(device="cuda").manual_seed(0)
-    rows = []
-    print(f"{'block':14} {'T':>4} {'path':5} {'copies':>6} {'us':>9} "
-          f"{'min..max':>21} {'touched MB':>10}")
-    for name in args.blocks.split(","):
-        cfg = PRESET_CONFIGS[name]
-        E, k = cfg.num_local_experts, cfg.num_experts_per_tok
-        for T in map(int, args.ts.split(",")):
-            x = torch.randn(T, cfg.hidden_size, dtype=torch.bfloat16,
-                            device="cuda", generator=gen)
-            # the bf16 decode path streams every expert; the routed W8 path
-            # at most the T*k selected ones
-            touched = {"bf16": E * expert_bytes(cfg, False),
-                       "w8": min(E, T * k) * expert_bytes(cfg, True)}
-            graphs, ncopy = {}, {}
-            blocks = {}
-            for path in ("bf16", "w8"):
-                n = min(args.max_copies,
-                        max(1, -(-2 * LLC_BYTES // touched[path])))
-                blocks[path] = [make_block(cfg, path == "w8", gen)
-                                for _ in range(n)]
-                ncopy[path] = n
-                if T > blocks[path][0].DENSE_TOKENS:
-                    continue  # one host sync per call: timed eagerly
-                with torch.no_grad():
-                    for b in blocks[path]:
-                        b(x)
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        for b in blocks[path]:
-                            b(x)
-                graphs[path] = g
-            res = {"bf16": [], "w8": []}
-            for _ in range(args.rounds):  # alternate the paths every round
-                for path in ("bf16", "w8"):
-                    if path in graphs:
-                        t = time_graph(graphs[path], ncopy[path],
-                                       max(3, 40 // ncopy[path]))
-                    else:
-                        with torch.no_grad():
-                            t = time_eager(lambda b: b(x), blocks[path],
-                                           max(3 * ncopy[path], 20))
-                    res[path].append(t)
-            for path, ts in res.items():
-                med = statistics.median(ts)
-                print(f"{name:14} {T:4d} {path:5} {ncopy[path]:6d} {med:9.1f} "
-                      f"{min(ts):10.1f}..{max(ts):<10.1f}"
-                      f"{touched[path] / 1e6:10.1f}", flush=True)
-                rows.append({"block": name, "T": T, "path": path,
-                             "mode": "graph" if path in graphs else "eager",
-                             "copies": ncopy[path], "us_median": med,
-                             "us_min": min(ts), "us_max": max(ts),
-                             "touched_bytes": touched[path],
-                             "rounds": len(ts)})
-            del graphs, blocks
-            torch.cuda.empty_cache()
-    return rows
+    return bench_w4_kernel(args, "w8", make_block, expert_bytes)
 
 
 def build_engine(args, w8: bool, max_seqs: int):
@@ -215,6 +159,7 @@ def main():
     ap.add_argument("--blocks", default=",".join(BLOCKS))
     ap.add_argument("--ts", default=",".join(map(str, TS)))
     ap.add_argument("--max-copies", type=int, default=32)
+    ap.add_argument("--grid-orders", action="store_true")
     ap.add_argument("--model", default="qwen3-30b-a3b")
     ap.add_argument("--batches", default="1,8,64,256")
     ap.add_argument("--input-len", type=int, default=128)
