@@ -67,6 +67,32 @@ class ModelConfig:
     # (modules_to_not_convert / ignored_layers); mxfp4: the export's
     # `exclude` list (module names, fnmatch patterns allowed)
     quant_skip_modules: tuple = ()
+    # DeepSeek-V2/V3 multi-head latent attention (kv_lora_rank > 0) and
+    # their MoE layout; head_dim is qk_rope_head_dim for these models
+    kv_lora_rank: int = 0
+    q_lora_rank: int | None = None
+    qk_nope_head_dim: int = 0
+    qk_rope_head_dim: int = 0
+    v_head_dim: int = 0
+    n_shared_experts: int = 0
+    first_k_dense_replace: int = 0
+    moe_layer_freq: int = 1
+    routed_scaling_factor: float = 1.0
+    scoring_func: str = "softmax"
+    topk_method: str = "greedy"
+    n_group: int = 1
+    topk_group: int = 1
+
+    @property
+    def is_mla(self) -> bool:
+        return self.kv_lora_rank > 0
+
+    def layer_is_moe(self, layer_idx: int) -> bool:
+        if not self.is_mla:
+            return self.num_local_experts > 0
+        return (self.num_local_experts > 0
+                and layer_idx >= self.first_k_dense_replace
+                and layer_idx % self.moe_layer_freq == 0)
 
     def __post_init__(self):
         # Sliding-window attention is implemented end to end: the
@@ -257,7 +283,32 @@ class ModelConfig:
         eos = cfg.get("eos_token_id", 151645)
         if isinstance(eos, list):
             eos = eos[0]
+        mla = {}
+        if arch in ("DeepseekV2ForCausalLM", "DeepseekV3ForCausalLM"):
+            v3 = arch == "DeepseekV3ForCausalLM"
+            mla = dict(
+                kv_lora_rank=cfg.get("kv_lora_rank", 512),
+                q_lora_rank=cfg.get("q_lora_rank", 1536),
+                qk_nope_head_dim=cfg.get("qk_nope_head_dim", 128),
+                qk_rope_head_dim=cfg.get("qk_rope_head_dim", 64),
+                v_head_dim=cfg.get("v_head_dim", 128),
+                n_shared_experts=cfg.get("n_shared_experts") or 0,
+                first_k_dense_replace=cfg.get("first_k_dense_replace", 0),
+                moe_layer_freq=cfg.get("moe_layer_freq", 1),
+                routed_scaling_factor=cfg.get("routed_scaling_factor", 1.0),
+                scoring_func=cfg.get("scoring_func",
+                                     "sigmoid" if v3 else "softmax"),
+                topk_method=cfg.get("topk_method",
+                                    "noaux_tc" if v3 else "greedy"),
+                n_group=cfg.get("n_group") or 1,
+                topk_group=cfg.get("topk_group") or 1,
+            )
+            cfg = dict(cfg, head_dim=mla["qk_rope_head_dim"],
+                       num_experts=cfg.get("n_routed_experts") or 0,
+                       attention_bias=cfg.get("attention_bias", False),
+                       norm_topk_prob=cfg.get("norm_topk_prob", v3))
         return cls(
+            **mla,
             architecture=arch,
             vocab_size=cfg.get("vocab_size", 151936),
             hidden_size=hidden,
@@ -605,6 +656,69 @@ PRESET_CONFIGS: dict[str, ModelConfig] = {
         tie_word_embeddings=True,
         attention_bias=False,
         no_rope_layers=[1, 0],
+        eos_token_id=2,
+        bos_token_id=1,
+    ),
+    # DeepSeek-V2: MLA with a direct q_proj, softmax router, greedy top-k
+    "tiny-deepseek-v2": ModelConfig(
+        architecture="DeepseekV2ForCausalLM",
+        vocab_size=512,
+        hidden_size=128,
+        intermediate_size=256,
+        moe_intermediate_size=64,
+        num_hidden_layers=2,
+        num_attention_heads=16,
+        num_key_value_heads=16,
+        head_dim=64,
+        rope_theta=10000.0,
+        max_position_embeddings=2048,
+        attention_bias=False,
+        num_local_experts=4,
+        num_experts_per_tok=2,
+        norm_topk_prob=False,
+        kv_lora_rank=512,
+        q_lora_rank=None,
+        qk_nope_head_dim=32,
+        qk_rope_head_dim=64,
+        v_head_dim=32,
+        n_shared_experts=2,
+        first_k_dense_replace=1,
+        routed_scaling_factor=1.0,
+        scoring_func="softmax",
+        topk_method="greedy",
+        eos_token_id=2,
+        bos_token_id=1,
+    ),
+    # DeepSeek-V3: q_lora_rank, sigmoid router with a correction bias and
+    # group-limited top-k
+    "tiny-deepseek-v3": ModelConfig(
+        architecture="DeepseekV3ForCausalLM",
+        vocab_size=512,
+        hidden_size=128,
+        intermediate_size=256,
+        moe_intermediate_size=64,
+        num_hidden_layers=3,
+        num_attention_heads=16,
+        num_key_value_heads=16,
+        head_dim=64,
+        rope_theta=10000.0,
+        max_position_embeddings=2048,
+        attention_bias=False,
+        num_local_experts=8,
+        num_experts_per_tok=2,
+        norm_topk_prob=True,
+        kv_lora_rank=512,
+        q_lora_rank=96,
+        qk_nope_head_dim=32,
+        qk_rope_head_dim=64,
+        v_head_dim=32,
+        n_shared_experts=1,
+        first_k_dense_replace=1,
+        routed_scaling_factor=2.5,
+        scoring_func="sigmoid",
+        topk_method="noaux_tc",
+        n_group=4,
+        topk_group=2,
         eos_token_id=2,
         bos_token_id=1,
     ),

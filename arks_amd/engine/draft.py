@@ -49,6 +49,11 @@ class DraftRunner:
             raise ValueError(
                 f"draft vocab {dcfg.vocab_size} != target "
                 f"{target_cfg.vocab_size} (tokenizers must match)")
+        if dcfg.is_mla or target_cfg.is_mla:
+            raise ValueError(
+                "draft-model speculation is not supported with MLA models "
+                "(the draft pool mirrors per-head K/V pages); use "
+                "speculative='ngram'")
         if dcfg.uniform_window() or target_cfg.uniform_window():
             raise ValueError(
                 "draft-model speculation with sliding-window page dropping "

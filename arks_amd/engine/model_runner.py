@@ -47,6 +47,8 @@ class ModelRunner:
             raise ValueError("dtype='float32' runs on device='cpu' only")
         self.dtype = (torch.float32 if engine_cfg.dtype == "float32"
                       else torch.bfloat16)
+        if self.model_cfg.is_mla:
+            self._check_mla_supported()
         torch.manual_seed(engine_cfg.seed)
         self._setup_tunableop()
         from ..models import create_model  # lazy: breaks the import cycle
@@ -73,6 +75,33 @@ class ModelRunner:
         self.use_graphs = (
             self.device.type == "cuda" and not engine_cfg.enforce_eager
         )
+
+    def _check_mla_supported(self) -> None:
+        """What an MLA (DeepSeek-V2/V3) model is not served with, each
+        refused at start-up."""
+        mc, cfg = self.model_cfg, self.cfg
+        if cfg.kv_cache_dtype == "fp8":
+            raise ValueError("kv_cache_dtype='fp8' is not supported with MLA "
+                             "models: the latent cache is bf16")
+        if cfg.enable_lora:
+            raise ValueError("enable_lora is not supported with MLA models")
+        if self.quantization is not None:
+            raise ValueError(
+                f"quantization={self.quantization!r} is not supported with "
+                f"{mc.architecture}: MLA models are served in bf16")
+        if cfg.speculative == "draft":
+            raise ValueError(
+                "speculative='draft' is not supported with MLA models (the "
+                "draft pool mirrors per-head K/V pages); use "
+                "speculative='ngram'")
+        if self.device.type == "cuda" and (
+                mc.kv_lora_rank, mc.qk_rope_head_dim, cfg.block_size) != (
+                ops.MLA_LATENT, ops.MLA_ROPE, 16):
+            raise ValueError(
+                "the gfx950 MLA kernels are built for kv_lora_rank "
+                f"{ops.MLA_LATENT}, qk_rope_head_dim {ops.MLA_ROPE} and pages "
+                f"of 16 tokens, got {mc.kv_lora_rank}, "
+                f"{mc.qk_rope_head_dim} and {cfg.block_size}")
 
     # capture sizes: padded decode batch sizes with their own graphs
     GRAPH_SIZES = [1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128, 192, 256]
@@ -215,13 +244,19 @@ class ModelRunner:
             return self.cfg.kv_cache_blocks
         mc = self.model_cfg
         tp = get_tp_world_size()
-        block_bytes = kv_cache_block_bytes(
-            mc.num_hidden_layers,
-            max(mc.num_key_value_heads // tp, 1),
-            mc.head_dim,
-            self.cfg.block_size,
-            dtype_bytes=1 if self.cfg.kv_cache_dtype == "fp8" else 2,
-        )
+        if mc.is_mla:
+            # one latent row per token on EVERY rank: no per-head division
+            block_bytes = (mc.num_hidden_layers * self.cfg.block_size
+                           * (mc.kv_lora_rank + mc.qk_rope_head_dim)
+                           * (4 if self.dtype == torch.float32 else 2))
+        else:
+            block_bytes = kv_cache_block_bytes(
+                mc.num_hidden_layers,
+                max(mc.num_key_value_heads // tp, 1),
+                mc.head_dim,
+                self.cfg.block_size,
+                dtype_bytes=1 if self.cfg.kv_cache_dtype == "fp8" else 2,
+            )
         if self.device.type == "cuda":
             free, total = torch.cuda.mem_get_info(self.device)
             budget = int(total * self.cfg.gpu_memory_utilization) - (total - free)
@@ -241,13 +276,23 @@ class ModelRunner:
             torch.float8_e4m3fn if self.cfg.kv_cache_dtype == "fp8"
             else self.dtype
         )
-        self.kv_caches = [
-            (
-                torch.zeros(shape, dtype=kv_dtype, device=self.device),
-                torch.zeros(shape, dtype=kv_dtype, device=self.device),
-            )
-            for _ in range(mc.num_hidden_layers)
-        ]
+        if mc.is_mla:
+            # the latent cache: one [blocks, 16, 576] tensor per layer, key
+            # and value at once, the same on every TP rank
+            shape = (self.num_blocks, self.cfg.block_size,
+                     mc.kv_lora_rank + mc.qk_rope_head_dim)
+            self.kv_caches = [
+                torch.zeros(shape, dtype=self.dtype, device=self.device)
+                for _ in range(mc.num_hidden_layers)
+            ]
+        else:
+            self.kv_caches = [
+                (
+                    torch.zeros(shape, dtype=kv_dtype, device=self.device),
+                    torch.zeros(shape, dtype=kv_dtype, device=self.device),
+                )
+                for _ in range(mc.num_hidden_layers)
+            ]
         if self.use_graphs:
             self._init_graph_buffers()
         if self.cfg.enable_prefix_caching:
@@ -261,6 +306,10 @@ class ModelRunner:
         transfer to a decode instance (the reference's PD
         split delegates this to SGLang's disaggregation-mode, reference
         arksdisaggregatedapplication_controller.go:1672-1724)."""
+        if self.model_cfg.is_mla:
+            raise ValueError("disaggregated KV transfer is not supported "
+                             "with MLA models (no wire format for latent "
+                             "pages yet)")
         # sliding-window-dropped pages are -1: clamp to a valid page (the
         # receiver never reads out-of-window content)
         bt = torch.tensor(block_table, dtype=torch.long,
@@ -276,6 +325,10 @@ class ModelRunner:
     def inject_kv(self, block_table: list[int], kv: torch.Tensor) -> None:
         """Scatter a transferred KV tensor (extract_kv layout, full head
         set) into this runner's pages — each TP rank takes its head slice."""
+        if self.model_cfg.is_mla:
+            raise ValueError("disaggregated KV transfer is not supported "
+                             "with MLA models (no wire format for latent "
+                             "pages yet)")
         nkv_local = self.kv_caches[0][0].shape[1]
         world, rank = get_tp_world_size(), get_tp_rank()
         assert kv.shape[0] == len(self.kv_caches) and kv.shape[2] == len(block_table)
@@ -302,7 +355,11 @@ class ModelRunner:
             # the contiguous-varlen kernel is slower and pages are written
             # either way); the CPU reference keeps the contiguous path
             # exercised for fresh prefills.
-            use_extend = (self.device.type == "cuda"
+            # An MLA model has one attention path, over the paged latent
+            # cache: its prefill batches always carry block tables (and no
+            # extend tile tables).
+            mla = self.model_cfg.is_mla
+            use_extend = (self.device.type == "cuda" or mla
                           or any(s.num_cached_tokens > 0 for s in sb.seqs))
             input_ids: list = []  # np.int64 arrays, one per seq
             positions: list = []
@@ -375,7 +432,7 @@ class ModelRunner:
                     )
                 block_tables = bt.to(dev)
                 seq_lens = torch.tensor(kv_lens, dtype=torch.int32, device=dev)
-                ext_tiles = ops.build_extend_tiles(
+                ext_tiles = None if mla else ops.build_extend_tiles(
                     q_lens, kv_lens,
                     self.cfg.kv_cache_dtype == "fp8", dev,
                     num_q_heads=max(

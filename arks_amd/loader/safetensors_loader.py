@@ -28,7 +28,8 @@ def _iter_safetensors(model_path: str):
                 yield name, sf.get_tensor(name)
 
 
-def _iter_chunks(model_path: str, limit_bytes: int, pin: bool):
+def _iter_chunks(model_path: str, limit_bytes: int, pin: bool,
+                 fused_qkv: bool = True):
     """Group tensors into >= limit_bytes chunks with fused-weight partners
     co-resident (load_hf_state_dict needs q/k/v and gate/up together).
     With pin=True each tensor is copied into pinned memory here — done on
@@ -38,7 +39,7 @@ def _iter_chunks(model_path: str, limit_bytes: int, pin: bool):
     for name, t in _iter_safetensors(model_path):
         chunk[name] = t.pin_memory() if pin else t
         chunk_bytes += t.numel() * t.element_size()
-        if chunk_bytes >= limit_bytes and _chunk_complete(chunk):
+        if chunk_bytes >= limit_bytes and _chunk_complete(chunk, fused_qkv):
             yield chunk
             chunk, chunk_bytes = {}, 0
     if chunk:
@@ -101,8 +102,11 @@ def load_model_weights(model, model_path: str, device: torch.device,
     BASELINE.md).
     """
     model.to(device)
+    # an MLA model's q_proj stands alone: it has no k_proj / v_proj partners
+    fused_qkv = not getattr(model, "mla", False)
     if device.type != "cuda":
-        for chunk in _iter_chunks(model_path, chunk_bytes, pin=False):
+        for chunk in _iter_chunks(model_path, chunk_bytes, pin=False,
+                                  fused_qkv=fused_qkv):
             model.load_hf_state_dict(chunk)
         return
 
@@ -148,7 +152,7 @@ def load_model_weights(model, model_path: str, device: torch.device,
                             names[name] = (dt, shape, o0, o1)
                             j += 1
                             if (o1 - span0 >= chunk_bytes
-                                    and _chunk_complete(names)):
+                                    and _chunk_complete(names, fused_qkv)):
                                 break
                         if j == i:  # single tensor larger than the buffer
                             raise RuntimeError(
@@ -163,7 +167,7 @@ def load_model_weights(model, model_path: str, device: torch.device,
                         for name, (dt, shape, o0, o1) in names.items():
                             sl = buf[o0 - span0: o1 - span0]
                             chunk[name] = sl.view(dt).view(shape)
-                        for name in _dangling_names(chunk):
+                        for name in _dangling_names(chunk, fused_qkv):
                             carry[name] = chunk.pop(name).clone()
                         q.put((chunk, buf_id))
                         i = j
@@ -190,7 +194,7 @@ def load_model_weights(model, model_path: str, device: torch.device,
     torch.cuda.synchronize(device)
 
 
-def _dangling_names(chunk) -> set:
+def _dangling_names(chunk, fused_qkv: bool = True) -> set:
     """Names whose fused-weight partner group is incomplete in `chunk`
     (q/k/v and gate/up must be applied together — a group split across a
     file or staging-buffer boundary must carry over, or its weights would
@@ -199,7 +203,7 @@ def _dangling_names(chunk) -> set:
     names = set(chunk)
     out = set()
     for n in names:
-        if "q_proj" in n or "k_proj" in n or "v_proj" in n:
+        if fused_qkv and ("q_proj" in n or "k_proj" in n or "v_proj" in n):
             stem = n.rsplit(".", 2)[0]
             kind = n.rsplit(".", 1)[1]
             if any(f"{stem}.{p}.{kind}" not in names
@@ -214,12 +218,13 @@ def _dangling_names(chunk) -> set:
     return out
 
 
-def _chunk_complete(chunk: dict[str, torch.Tensor]) -> bool:
+def _chunk_complete(chunk: dict[str, torch.Tensor],
+                    fused_qkv: bool = True) -> bool:
     """True when no fused-weight partner is missing (q/k/v and gate/up pairs
     must land in the same chunk)."""
     names = set(chunk)
     for n in names:
-        if "q_proj" in n or "k_proj" in n or "v_proj" in n:
+        if fused_qkv and ("q_proj" in n or "k_proj" in n or "v_proj" in n):
             stem = n.rsplit(".", 2)[0]
             kind = n.rsplit(".", 1)[1]
             for p in ("q_proj", "k_proj", "v_proj"):
@@ -423,6 +428,10 @@ def _random_hf_tensors(cfg, seed: int) -> dict[str, torch.Tensor]:
 
     assert get_tp_world_size() == 1, "save from a TP=1 process"
     model = create_model(cfg)
+    if cfg.is_mla:
+        return {name: t.to(torch.bfloat16)
+                for part in model.random_hf_tensors(seed)
+                for name, t in part.items()}
     model.random_init(seed)
     # Emit HF-layout names (split fused weights back apart).
     out: dict[str, torch.Tensor] = {
@@ -535,6 +544,20 @@ def _write_checkpoint(cfg, out_dir: str, tensors: dict[str, torch.Tensor],
             "shared_expert_intermediate_size":
                 cfg.shared_expert_intermediate_size,
             "norm_topk_prob": cfg.norm_topk_prob,
+        })
+    if cfg.is_mla:
+        for key in ("num_experts", "shared_expert_intermediate_size",
+                    "head_dim"):
+            hf_cfg.pop(key, None)
+        hf_cfg.update({
+            "n_routed_experts": cfg.num_local_experts,
+            "rope_scaling": cfg.rope_scaling,
+            **{k: getattr(cfg, k) for k in (
+                "kv_lora_rank", "q_lora_rank", "qk_nope_head_dim",
+                "qk_rope_head_dim", "v_head_dim", "n_shared_experts",
+                "first_k_dense_replace", "moe_layer_freq",
+                "routed_scaling_factor", "scoring_func", "topk_method",
+                "n_group", "topk_group")},
         })
     hf_cfg.update(extra_config or {})
     with open(os.path.join(out_dir, "config.json"), "w") as f:

@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 from ..config import ModelConfig
+from .deepseek import DeepseekForCausalLM
 from .llama_family import LlamaFamilyForCausalLM
 
 _REGISTRY = {
@@ -17,6 +18,9 @@ _REGISTRY = {
     "Qwen2MoeForCausalLM": LlamaFamilyForCausalLM,  # MoE + shared expert
     # llama arch + NoPE every no_rope_layer_interval-th layer + tied embeds
     "SmolLM3ForCausalLM": LlamaFamilyForCausalLM,
+    # multi-head latent attention over a paged latent cache + DeepSeek MoE
+    "DeepseekV2ForCausalLM": DeepseekForCausalLM,
+    "DeepseekV3ForCausalLM": DeepseekForCausalLM,
 }
 
 

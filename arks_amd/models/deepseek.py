@@ -1,0 +1,397 @@
+"""DeepSeek-V2 / DeepSeek-V3 for the arks_amd engine: multi-head latent
+attention (MLA) over a paged latent KV cache, a dense MLP in the first
+layers and shared + routed experts after them.
+
+Attention runs with absorbed projections: the cache holds one 576-wide row
+per token (RMS-normalised compressed KV | rotated shared rope key, written
+by ops.mla_rope_cache), the query is carried into the latent space through
+W_UK, ops.attention_mla_paged attends over the rows (they are key and value
+at once) and W_UV brings the 512-wide output back to v_head_dim per head. The
+same path serves prefill, prefix-cache extend, speculative verification and
+decode, so every batch of an MLA model carries block tables. The two batched
+matmuls go through the library; the hot path is attn_mla.hip.
+"""
+
+from __future__ import annotations
+
+import dataclasses
+
+import torch
+import torch.nn as nn
+
+from .. import ops
+from ..config import ModelConfig
+from ..engine.forward_batch import ForwardBatch
+from ..parallel.comm import get_tp_rank, get_tp_world_size
+from ..parallel.layers import (
+    ColumnParallelLinear,
+    ParallelLMHead,
+    RowParallelLinear,
+)
+from .llama_family import MLP, LlamaFamilyForCausalLM, MoEMLP, RMSNorm
+
+
+def yarn_mscale(factor: float, mscale: float) -> float:
+    import math
+
+    return 1.0 if factor <= 1 else 0.1 * mscale * math.log(factor) + 1.0
+
+
+class ReplicatedLinear(nn.Module):
+    """Y = X W^T with the whole W on every rank."""
+
+    def __init__(self, in_features: int, out_features: int, dtype):
+        super().__init__()
+        self.weight = nn.Parameter(
+            torch.empty(out_features, in_features, dtype=dtype),
+            requires_grad=False)
+
+    def forward(self, x):
+        return ops.linear_bf16(x, self.weight)
+
+
+class MLAAttention(nn.Module):
+    def __init__(self, cfg: ModelConfig, dtype=torch.bfloat16):
+        super().__init__()
+        tp = get_tp_world_size()
+        H = cfg.num_attention_heads
+        assert H % tp == 0, (H, tp)
+        self.h_local = H // tp
+        self.nope, self.rope = cfg.qk_nope_head_dim, cfg.qk_rope_head_dim
+        self.vdim, self.lat = cfg.v_head_dim, cfg.kv_lora_rank
+        qk = self.nope + self.rope
+        self.scale = qk ** -0.5
+        rs = cfg.rope_scaling or {}
+        if (rs.get("rope_type") or rs.get("type")) == "yarn" \
+                and rs.get("mscale_all_dim"):
+            m = yarn_mscale(float(rs["factor"]), float(rs["mscale_all_dim"]))
+            self.scale *= m * m
+        hid = cfg.hidden_size
+        if cfg.q_lora_rank is None:
+            self.q_proj = ColumnParallelLinear(hid, H * qk, False, dtype)
+        else:
+            self.q_a_proj = ReplicatedLinear(hid, cfg.q_lora_rank, dtype)
+            self.q_a_layernorm = RMSNorm(cfg.q_lora_rank, cfg.rms_norm_eps,
+                                         dtype)
+            self.q_b_proj = ColumnParallelLinear(cfg.q_lora_rank, H * qk,
+                                                 False, dtype)
+        self.kv_a_proj_with_mqa = ReplicatedLinear(hid, self.lat + self.rope,
+                                                   dtype)
+        self.kv_a_layernorm = RMSNorm(self.lat, cfg.rms_norm_eps, dtype)
+        # kv_b_proj, split at load: q_lat = q_nope W_UK, o = o_lat W_UV
+        self.w_uk = nn.Parameter(
+            torch.empty(self.h_local, self.nope, self.lat, dtype=dtype),
+            requires_grad=False)
+        self.w_uv = nn.Parameter(
+            torch.empty(self.h_local, self.lat, self.vdim, dtype=dtype),
+            requires_grad=False)
+        self.o_proj = RowParallelLinear(H * self.vdim, hid, False, dtype)
+
+    def load_kv_b(self, w: torch.Tensor) -> None:
+        """HF kv_b_proj.weight [H * (nope + v), lat] -> this rank's W_UK
+        [h, nope, lat] and W_UV [h, lat, v]."""
+        r = get_tp_rank()
+        w = w.view(-1, self.nope + self.vdim, self.lat)
+        w = w[r * self.h_local:(r + 1) * self.h_local]
+        self.w_uk.data.copy_(w[:, :self.nope].to(self.w_uk.dtype))
+        self.w_uv.data.copy_(
+            w[:, self.nope:].transpose(1, 2).to(self.w_uv.dtype))
+
+    def forward(self, x, batch: ForwardBatch, kv_cache, defer: bool = False):
+        T, h = x.shape[0], self.h_local
+        if hasattr(self, "q_proj"):
+            q = self.q_proj(x)
+        else:
+            q = self.q_b_proj(self.q_a_layernorm(self.q_a_proj(x)))
+        q = q.view(T, h, self.nope + self.rope)
+        q_pe = q[..., self.nope:]           # strided view, rotated in place
+        kv_a = self.kv_a_proj_with_mqa(x)
+        ops.mla_rope_cache(batch.positions, kv_a, self.kv_a_layernorm.weight,
+                           self.kv_a_layernorm.eps, q_pe, self._cos_sin,
+                           kv_cache, batch.slot_mapping)
+        # contiguous operands: strided bmm on transposed views is avoided
+        # throughout this code base (see MoEMLP)
+        q_nope = q[..., :self.nope].transpose(0, 1).contiguous()
+        q_lat = torch.bmm(q_nope, self.w_uk).transpose(0, 1).contiguous()
+        o_lat = ops.attention_mla_paged(
+            q_lat, q_pe, kv_cache, batch.block_tables, batch.seq_lens,
+            self.scale, cu_seqlens=batch.cu_seqlens if batch.is_prefill
+            else None)
+        o = torch.bmm(o_lat.transpose(0, 1).contiguous(), self.w_uv)
+        return self.o_proj(o.transpose(0, 1).reshape(T, h * self.vdim),
+                           defer=defer)
+
+
+class DeepseekMoE(MoEMLP):
+    """Routed experts (MoEMLP's storage and expert-parallel forward) with
+    DeepSeek's routers and ungated shared experts."""
+
+    def __init__(self, cfg: ModelConfig, dtype=torch.bfloat16):
+        super().__init__(cfg, dtype)
+        self.scoring = cfg.scoring_func
+        self.topk_method = cfg.topk_method
+        self.n_group, self.topk_group = cfg.n_group, cfg.topk_group
+        self.routed_scale = cfg.routed_scaling_factor
+        if self.scoring == "sigmoid":
+            self.register_buffer(
+                "e_score_correction_bias",
+                torch.zeros(cfg.num_local_experts, dtype=torch.float32),
+                persistent=False)
+        elif self.topk_method not in ("greedy", "group_limited_greedy"):
+            raise ValueError(f"unsupported topk_method {self.topk_method!r} "
+                             f"with scoring_func {self.scoring!r}")
+        self.shared_experts = None
+        if cfg.n_shared_experts:
+            self.shared_experts = MLP(dataclasses.replace(
+                cfg, intermediate_size=(cfg.n_shared_experts
+                                        * cfg.moe_intermediate_size)), dtype)
+
+    def _group_mask(self, group_scores):
+        """[T, E] mask of the experts in each token's topk_group best
+        groups."""
+        idx = torch.topk(group_scores, self.topk_group, dim=-1,
+                         sorted=False)[1]
+        mask = torch.zeros_like(group_scores).scatter_(1, idx, 1.0)
+        per = self.num_experts // self.n_group
+        return mask.repeat_interleave(per, dim=1) > 0
+
+    def _route(self, x):
+        """V2: softmax scores, greedy or group-limited top-k (the fused
+        routing kernel where it fits). V3: sigmoid scores, the choice made on
+        scores + e_score_correction_bias within the topk_group groups with
+        the best top-2 sums, weights from the plain scores, renormalised.
+        Plain torch ops on [T, E]: no host sync, capture-safe."""
+        logits = torch.nn.functional.linear(x, self.gate).float()
+        E, G = self.num_experts, self.n_group
+        if self.scoring == "softmax":
+            if self.topk_method == "greedy":
+                w, sel = ops.moe_topk(logits, self.top_k, self.norm_topk)
+                return w * self.routed_scale, sel
+            scores = torch.softmax(logits, dim=-1)
+            mask = self._group_mask(scores.view(-1, G, E // G).amax(-1))
+            w, sel = torch.topk(scores.masked_fill(~mask, 0.0), self.top_k,
+                                dim=-1)
+        else:
+            scores = torch.sigmoid(logits)
+            choice = scores + self.e_score_correction_bias
+            top2 = choice.view(-1, G, E // G).topk(2, dim=-1)[0].sum(-1)
+            choice = choice.masked_fill(~self._group_mask(top2),
+                                        float("-inf"))
+            sel = torch.topk(choice, self.top_k, dim=-1)[1]
+            w = scores.gather(1, sel)
+        if self.norm_topk:
+            w = w / (w.sum(dim=-1, keepdim=True) + 1e-20)
+        return w * self.routed_scale, sel.to(torch.int32)
+
+    def forward(self, x):
+        out = super().forward(x)
+        if self.shared_experts is not None:
+            out = out + self.shared_experts(x)
+        return out
+
+
+class DeepseekDecoderLayer(nn.Module):
+    def __init__(self, cfg: ModelConfig, dtype, layer_idx: int):
+        super().__init__()
+        self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, dtype)
+        self.self_attn = MLAAttention(cfg, dtype)
+        self.post_attention_layernorm = RMSNorm(cfg.hidden_size,
+                                                cfg.rms_norm_eps, dtype)
+        self.mlp = (DeepseekMoE(cfg, dtype) if cfg.layer_is_moe(layer_idx)
+                    else MLP(cfg, dtype))
+        self._dense_mlp = isinstance(self.mlp, MLP)
+
+    def forward(self, x, residual, batch: ForwardBatch, kv_cache):
+        if residual is None:
+            residual = x
+            x = self.input_layernorm(x)
+        else:
+            x, residual = self.input_layernorm(x, residual)
+        x = self.self_attn(x, batch, kv_cache, defer=True)
+        x, residual = self.post_attention_layernorm(x, residual)
+        x = (self.mlp(x, batch, defer=True) if self._dense_mlp
+             else self.mlp(x))
+        return x, residual
+
+
+class DeepseekForCausalLM(LlamaFamilyForCausalLM):
+    """DeepseekV2ForCausalLM and DeepseekV3ForCausalLM (bf16 checkpoints).
+    The decoder stack, logits and pooling are the family's; attention, MoE
+    routing and the weight names are DeepSeek's."""
+
+    mla = True
+
+    def __init__(self, cfg: ModelConfig, dtype=torch.bfloat16):
+        nn.Module.__init__(self)
+        if cfg.quant_method is not None:
+            raise ValueError(
+                f"quantized {cfg.architecture} checkpoints "
+                f"({cfg.quant_method}) are not supported yet: MLA models "
+                "are served from bf16 checkpoints")
+        if cfg.sliding_window is not None:
+            raise ValueError("sliding-window attention is not supported "
+                             "with MLA models")
+        self.cfg = cfg
+        self.dtype = dtype
+        self.embed_tokens = nn.Embedding(cfg.vocab_size, cfg.hidden_size,
+                                         dtype=dtype)
+        self.embed_tokens.weight.requires_grad_(False)
+        self.layers = nn.ModuleList(
+            DeepseekDecoderLayer(cfg, dtype, i)
+            for i in range(cfg.num_hidden_layers))
+        self.norm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, dtype)
+        self.lm_head = ParallelLMHead(cfg.hidden_size, cfg.vocab_size, dtype)
+        self.has_lm_head = True
+        self._lm_head_loaded = False
+        cos_sin = self._build_cos_sin()
+        self.register_buffer("rope_cos_sin", cos_sin, persistent=False)
+        for layer in self.layers:
+            layer.self_attn._cos_sin = cos_sin
+
+    # head_dim is qk_rope_head_dim for these models, so the family's
+    # _build_cos_sin / extend_rope_table give the [max_pos, 64] table as is.
+
+    # ------------------------- weight loading -------------------------
+    def load_hf_state_dict(self, tensors: dict[str, torch.Tensor]) -> None:
+        """Load an HF-layout state dict (full tensors; sharded here)."""
+        own = dict(self.named_parameters())
+
+        def put(name, value):
+            p = own[name]
+            assert p.shape == value.shape, (name, p.shape, value.shape)
+            p.data.copy_(value.to(p.dtype))
+
+        for name, w in tensors.items():
+            name = name.removeprefix("model.")
+            if name == "embed_tokens.weight":
+                put(name, w)
+                if self.cfg.tie_word_embeddings:
+                    put("lm_head.weight", self.lm_head.shard(w))
+                    self._lm_head_loaded = True
+            elif name == "lm_head.weight":
+                put(name, self.lm_head.shard(w))
+                self._lm_head_loaded = True
+            elif name == "norm.weight":
+                put(name, w)
+            elif name.startswith("layers."):
+                parts = name.split(".")
+                li = int(parts[1])
+                if li >= len(self.layers):
+                    continue  # multi-token-prediction heads are not served
+                self._load_layer(self.layers[li], f"layers.{li}",
+                                 ".".join(parts[2:]), w, put, tensors)
+
+    def _load_layer(self, layer, pre, sub, w, put, tensors) -> None:
+        attn, mlp = layer.self_attn, layer.mlp
+        mod, _, leaf = sub.rpartition(".")
+        if mod in ("input_layernorm", "post_attention_layernorm",
+                   "self_attn.q_a_layernorm", "self_attn.kv_a_layernorm",
+                   "self_attn.q_a_proj", "self_attn.kv_a_proj_with_mqa"):
+            put(f"{pre}.{sub}", w)
+        elif mod in ("self_attn.q_proj", "self_attn.q_b_proj",
+                     "self_attn.o_proj", "mlp.down_proj",
+                     "mlp.shared_experts.down_proj"):
+            m = layer.get_submodule(mod)
+            put(f"{pre}.{sub}", m.shard(w))
+        elif mod == "self_attn.kv_b_proj":
+            attn.load_kv_b(w)
+        elif mod in ("mlp.gate_proj", "mlp.shared_experts.gate_proj"):
+            # gate and up arrive in the same chunk (the loader keeps fused
+            # partners together)
+            head = mod.rsplit(".", 1)[0]
+            up = tensors[f"model.{pre}.{head}.up_proj.weight"] \
+                if f"model.{pre}.{head}.up_proj.weight" in tensors \
+                else tensors[f"{pre}.{head}.up_proj.weight"]
+            gu = layer.get_submodule(head).gate_up_proj
+            put(f"{pre}.{head}.gate_up_proj.weight", gu.shard_merged(w, up))
+        elif mod in ("mlp.up_proj", "mlp.shared_experts.up_proj"):
+            pass  # loaded with its gate_proj
+        elif sub == "mlp.gate.weight":
+            mlp.gate.data.copy_(w.to(mlp.gate.dtype))
+        elif sub == "mlp.gate.e_score_correction_bias":
+            mlp.e_score_correction_bias.copy_(w.float())
+        elif sub.startswith("mlp.experts."):
+            _, _, e, which, _ = sub.split(".")
+            le = int(e) - mlp.expert_base
+            if 0 <= le < mlp.local_experts:
+                I = mlp.inter  # HF [out, in] -> pre-transposed [in, out]
+                if which == "gate_proj":
+                    mlp.w13.data[le, :, :I].copy_(w.t().to(mlp.w13.dtype))
+                elif which == "up_proj":
+                    mlp.w13.data[le, :, I:].copy_(w.t().to(mlp.w13.dtype))
+                elif which == "down_proj":
+                    mlp.w2.data[le].copy_(w.t().to(mlp.w2.dtype))
+        # rotary_emb.inv_freq etc. are ignored (recomputed)
+
+    def random_hf_tensors(self, seed: int = 0):
+        """Random full HF-layout tensors (f32), one dict for the globals and
+        one per layer, generated deterministically per name so that every TP
+        rank sees slices of the same logical weights."""
+        import zlib
+
+        cfg = self.cfg
+        dev = self.embed_tokens.weight.device
+
+        def gen(name: str, *shape, std: float = 0.02) -> torch.Tensor:
+            s = (seed * 1000003 + zlib.crc32(name.encode())) % (2**63 - 1)
+            g = torch.Generator(device=dev).manual_seed(s)
+            return torch.randn(shape, generator=g, dtype=torch.float32,
+                               device=dev).mul_(std)
+
+        H, I = cfg.hidden_size, cfg.intermediate_size
+        nh, lat, rope = (cfg.num_attention_heads, cfg.kv_lora_rank,
+                         cfg.qk_rope_head_dim)
+        qk = cfg.qk_nope_head_dim + rope
+        glob = {"model.embed_tokens.weight": gen("embed", cfg.vocab_size, H),
+                "model.norm.weight": torch.ones(H)}
+        if not cfg.tie_word_embeddings:
+            glob["lm_head.weight"] = gen("lm_head", cfg.vocab_size, H)
+        yield glob
+        for i in range(cfg.num_hidden_layers):
+            pre = f"model.layers.{i}"
+            sa = f"{pre}.self_attn"
+            t = {
+                f"{pre}.input_layernorm.weight": torch.ones(H),
+                f"{pre}.post_attention_layernorm.weight": torch.ones(H),
+                f"{sa}.kv_a_proj_with_mqa.weight": gen(f"{sa}.kva",
+                                                       lat + rope, H),
+                f"{sa}.kv_a_layernorm.weight": torch.ones(lat),
+                f"{sa}.kv_b_proj.weight": gen(
+                    f"{sa}.kvb", nh * (cfg.qk_nope_head_dim + cfg.v_head_dim),
+                    lat),
+                f"{sa}.o_proj.weight": gen(f"{sa}.o", H, nh * cfg.v_head_dim),
+            }
+            if cfg.q_lora_rank is None:
+                t[f"{sa}.q_proj.weight"] = gen(f"{sa}.q", nh * qk, H)
+            else:
+                r = cfg.q_lora_rank
+                t[f"{sa}.q_a_proj.weight"] = gen(f"{sa}.qa", r, H)
+                t[f"{sa}.q_a_layernorm.weight"] = torch.ones(r)
+                t[f"{sa}.q_b_proj.weight"] = gen(f"{sa}.qb", nh * qk, r)
+
+            def ffn(stem, width):
+                t[f"{stem}.gate_proj.weight"] = gen(f"{stem}.g", width, H)
+                t[f"{stem}.up_proj.weight"] = gen(f"{stem}.u", width, H)
+                t[f"{stem}.down_proj.weight"] = gen(f"{stem}.d", H, width)
+
+            if cfg.layer_is_moe(i):
+                Ie = cfg.moe_intermediate_size
+                # a router wide enough apart that bf16 and f32 runs agree
+                t[f"{pre}.mlp.gate.weight"] = gen(
+                    f"{pre}.gate", cfg.num_local_experts, H, std=1.0)
+                if cfg.scoring_func == "sigmoid":
+                    t[f"{pre}.mlp.gate.e_score_correction_bias"] = gen(
+                        f"{pre}.gate.bias", cfg.num_local_experts, std=0.1)
+                if cfg.n_shared_experts:
+                    ffn(f"{pre}.mlp.shared_experts",
+                        cfg.n_shared_experts * Ie)
+                for e in range(cfg.num_local_experts):
+                    ffn(f"{pre}.mlp.experts.{e}", Ie)
+            else:
+                ffn(f"{pre}.mlp", I)
+            yield t
+
+    @torch.no_grad()
+    def random_init(self, seed: int = 0) -> None:
+        for part in self.random_hf_tensors(seed):  # bounded peak memory
+            self.load_hf_state_dict(part)

@@ -800,8 +800,7 @@ class MoEMLP(nn.Module):
         from ..parallel.comm import tp_all_reduce
 
         T, k = x.shape[0], self.top_k
-        router_logits = torch.nn.functional.linear(x, self.gate).float()
-        weights, selected = ops.moe_topk(router_logits, k, self.norm_topk)
+        weights, selected = self._route(x)
         counts, pairs = ops.moe_route(selected, self.expert_base,
                                       self.local_experts)
         max_rows = (T if T <= self.DENSE_TOKENS
@@ -834,6 +833,13 @@ class MoEMLP(nn.Module):
             out = out + gate * self.shared(x)
         return out
 
+    def _route(self, x):
+        """Router: (weights [T, k] f32, expert ids [T, k] i32). The fused
+        softmax+topk+renorm kernel (ops.moe_topk) replaces a 5-kernel torch
+        chain per layer."""
+        router_logits = torch.nn.functional.linear(x, self.gate).float()
+        return ops.moe_topk(router_logits, self.top_k, self.norm_topk)
+
     def forward(self, x):
         if self.w4 and x.is_cuda:
             return self._forward_routed(
@@ -853,11 +859,7 @@ class MoEMLP(nn.Module):
             self.routed_bf16_calls += 1
             return self._forward_routed(x, ops.moe_bf16_gemm, self.w13,
                                         self.w2)
-        router_logits = torch.nn.functional.linear(x, self.gate).float()
-        # fused softmax+topk+renorm routing kernel (ops.moe_topk) replaces
-        # a 5-kernel torch chain per layer
-        weights, selected = ops.moe_topk(router_logits, self.top_k,
-                                         self.norm_topk)
+        weights, selected = self._route(x)
         if T <= self.DENSE_TOKENS:
             return self._forward_bmm(x, weights, selected)
         return self._forward_sparse(x, weights, selected)

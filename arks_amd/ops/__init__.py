@@ -381,6 +381,95 @@ def attention_decode_paged(
     )
 
 
+# ---- multi-head latent attention (DeepSeek-V2/V3 MLA, attn_mla.hip) ----
+MLA_LATENT = 512   # kv_lora_rank the kernels are built for
+MLA_ROPE = 64      # qk_rope_head_dim the kernels are built for
+# Partial rows (token x head tile x partition) the heuristic can ask for:
+# it splits only below 512 workgroups and stops at the first count that
+# reaches them, so tokens * head tiles * partitions stays under 1024.
+_MLA_WS_ROWS = 1024
+_MLA_WS: dict = {}
+
+
+def _check_mla_cache(kv_cache) -> None:
+    if tuple(kv_cache.shape[1:]) != (16, MLA_LATENT + MLA_ROPE):
+        raise ValueError(
+            "the gfx950 MLA kernels are built for pages of 16 tokens with "
+            f"kv_lora_rank {MLA_LATENT} + qk_rope_head_dim {MLA_ROPE}, got a "
+            f"latent cache of shape {tuple(kv_cache.shape)}")
+
+
+def mla_rope_cache(positions, kv_a, norm_weight, eps: float, q_pe, cos_sin,
+                   kv_cache, slot_mapping) -> None:
+    """One pass per token over the kv_a_proj_with_mqa row kv_a [T, 576] and
+    the strided view q_pe [T, H, 64]: RMSNorm of the first 512 columns,
+    DeepSeek's interleaved-pair RoPE on the last 64 and on every head of q_pe
+    (in place), and the 576-wide row stored to its slot of the latent cache
+    (slot < 0: no cache write, as in reshape_and_cache)."""
+    if kv_a.is_cuda:
+        _check_mla_cache(kv_cache)
+        _native().mla_rope_cache(positions, kv_a, norm_weight, float(eps),
+                                 q_pe, cos_sin, kv_cache, slot_mapping)
+        return
+    ref.mla_rope_cache(positions, kv_a, norm_weight, eps, q_pe, cos_sin,
+                       kv_cache, slot_mapping)
+
+
+def mla_num_partitions(num_tokens: int, num_heads: int, max_blocks: int) -> int:
+    """Split factor of the MLA attention grid, in the style of
+    decode_num_partitions: about 2 workgroups per CU when query tokens x head
+    tiles alone do not give them, at least 8 pages (two per wave) per
+    partition. Thresholds carried over from the decode kernel; what was
+    measured around them is in profiles/mla.md."""
+    base = max(num_tokens * -(-num_heads // 16), 1)
+    nparts = max(1, -(-512 // base))
+    return min(nparts, max(1, max_blocks // 8), 64)
+
+
+def _mla_ws(rows: int, device):
+    """f32 partials (acc[512], m, l, pad) of 16 heads per row. The
+    heuristic's calls all fit one buffer per device that is never replaced,
+    so captured decode graphs keep pointing at live memory; only an explicit
+    num_partitions beyond it gets a buffer of its own."""
+    per_row = 16 * (MLA_LATENT + 4)
+    if rows > _MLA_WS_ROWS:
+        return torch.empty(rows * per_row, dtype=torch.float32, device=device)
+    ws = _MLA_WS.get(device.index)
+    if ws is None:
+        ws = _MLA_WS[device.index] = torch.empty(
+            _MLA_WS_ROWS * per_row, dtype=torch.float32, device=device)
+    return ws
+
+
+def attention_mla_paged(q_lat, q_pe, kv_cache, block_tables, seq_lens,
+                        scale: float, cu_seqlens=None,
+                        num_partitions: int | None = None):
+    """Absorbed-query attention over the paged latent cache, for decode
+    (cu_seqlens None: one query token per sequence) and for query lengths
+    above 1 (prefill, prefix-cache extend, speculative verification).
+    q_lat [T, H, 512] and q_pe [T, H, 64] (may be a strided view) are bf16,
+    seq_lens the total KV length with the new tokens in; returns o_lat
+    [T, H, 512]. Query token i of a sequence with q_len new tokens sees
+    positions < seq_len - q_len + i + 1."""
+    if q_lat.is_cuda:
+        _check_mla_cache(kv_cache)
+        T, H = q_lat.shape[0], q_lat.shape[1]
+        out = torch.empty((T, H, MLA_LATENT), dtype=q_lat.dtype,
+                          device=q_lat.device)
+        if num_partitions is None:
+            num_partitions = mla_num_partitions(T, H, block_tables.shape[1])
+        if num_partitions > 1:
+            part = _mla_ws(T * -(-H // 16) * num_partitions, q_lat.device)
+        else:
+            part = q_lat.new_empty(0, dtype=torch.float32)
+        _native().attention_mla_paged(
+            out, q_lat, q_pe, kv_cache, block_tables, seq_lens, cu_seqlens,
+            float(scale), part, num_partitions)
+        return out
+    return ref.attention_mla_paged(q_lat, q_pe, kv_cache, block_tables,
+                                   seq_lens, scale, cu_seqlens)
+
+
 _EXTEND_WS: dict = {}
 
 

@@ -49,6 +49,19 @@ void arks_attn_decode_paged(void* out, void* part_out, const void* q,
                             int num_kv_heads, int head_dim, int max_blocks,
                             int nparts, int64_t q_stride, int kv_fp8,
                             int window, hipStream_t stream);
+void arks_attn_mla_paged(void* out, void* part_out, const void* q_lat,
+                         const void* q_pe, const void* cache,
+                         const void* block_tables, const void* seq_lens,
+                         const void* cu_seqlens, float scale, int num_tokens,
+                         int num_heads, int num_seqs, int max_blocks,
+                         int num_blocks, int nparts, int64_t qpe_ts,
+                         int64_t qpe_hs, hipStream_t stream);
+void arks_mla_rope_cache(const void* positions, const void* kv_a,
+                         const void* norm_weight, void* q_pe,
+                         const void* cos_sin, void* cache,
+                         const void* slot_mapping, float eps, int num_tokens,
+                         int num_heads, int64_t kv_stride, int64_t qpe_ts,
+                         int64_t qpe_hs, hipStream_t stream);
 void arks_attn_prefill_varlen(void* out, const void* q, const void* k,
                               const void* v, const void* cu_seqlens,
                               const void* tile_info, int ntiles, float scale,
@@ -408,6 +421,124 @@ void attention_decode_paged(torch::Tensor out, torch::Tensor q,
                          (float)scale, num_seqs, num_q_heads, num_kv_heads,
                          head_dim, max_blocks, (int)nparts, q.stride(0),
                          kv_fp8 ? 1 : 0, (int)window, current_stream());
+}
+
+// ---- multi-head latent attention (attn_mla.hip) ----
+// The latent cache: [num_blocks, 16, 576] bf16, 512 compressed-KV columns and
+// 64 rope-key columns per token row.
+static void check_mla_cache(const torch::Tensor& c) {
+  TORCH_CHECK(c.is_cuda() && c.scalar_type() == torch::kBFloat16 &&
+                  c.is_contiguous() && c.dim() == 3 && c.size(0) >= 1 &&
+                  c.size(1) == 16 && c.size(2) == 576,
+              "kv_cache must be a contiguous bf16 [num_blocks, 16, 576] GPU "
+              "tensor (kv_lora_rank 512 + qk_rope_head_dim 64)");
+  TORCH_CHECK(c.size(0) < ((int64_t)1 << 31) / 16, "too many cache blocks");
+}
+
+// q_pe [T, H, 64]: a strided view into the q projection; every head row
+// must be 16-byte aligned.
+static void check_mla_q_pe(const torch::Tensor& q_pe, int64_t T, int64_t H) {
+  TORCH_CHECK(q_pe.is_cuda() && q_pe.scalar_type() == torch::kBFloat16 &&
+                  q_pe.dim() == 3 && q_pe.size(0) == T && q_pe.size(1) == H &&
+                  q_pe.size(2) == 64 && q_pe.stride(2) == 1,
+              "q_pe must be bf16 [T, H, 64] on GPU with a dense last dim");
+  TORCH_CHECK(q_pe.stride(0) % 8 == 0 && q_pe.stride(1) % 8 == 0 &&
+                  q_pe.stride(0) >= 0 && q_pe.stride(1) >= 64 &&
+                  reinterpret_cast<uintptr_t>(q_pe.data_ptr()) % 16 == 0,
+              "q_pe head rows must be 16-byte aligned and not overlap");
+}
+
+void mla_rope_cache(torch::Tensor positions, torch::Tensor kv_a,
+                    torch::Tensor norm_weight, double eps, torch::Tensor q_pe,
+                    torch::Tensor cos_sin, torch::Tensor kv_cache,
+                    torch::Tensor slot_mapping) {
+  check_mla_cache(kv_cache);
+  const int64_t T = kv_a.size(0);
+  TORCH_CHECK(kv_a.is_cuda() && kv_a.scalar_type() == torch::kBFloat16 &&
+                  kv_a.dim() == 2 && kv_a.size(1) == 576 &&
+                  kv_a.stride(1) == 1 && kv_a.stride(0) >= 576 &&
+                  kv_a.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(kv_a.data_ptr()) % 16 == 0,
+              "kv_a must be bf16 [T, 576] on GPU with 16-byte aligned rows");
+  TORCH_CHECK(q_pe.dim() == 3, "q_pe must be [T, H, 64]");
+  const int64_t H = q_pe.size(1);
+  check_mla_q_pe(q_pe, T, H);
+  check_bf16_contig(norm_weight, "norm_weight");
+  TORCH_CHECK(norm_weight.numel() == 512, "norm_weight must have 512 elements");
+  TORCH_CHECK(positions.is_cuda() && positions.scalar_type() == torch::kInt64 &&
+                  positions.is_contiguous() && positions.numel() == T,
+              "positions must be contiguous int64 [T] on GPU");
+  TORCH_CHECK(slot_mapping.is_cuda() &&
+                  slot_mapping.scalar_type() == torch::kInt64 &&
+                  slot_mapping.is_contiguous() && slot_mapping.numel() == T,
+              "slot_mapping must be contiguous int64 [T] on GPU");
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == torch::kFloat32 &&
+                  cos_sin.is_contiguous() && cos_sin.dim() == 2 &&
+                  cos_sin.size(1) == 64,
+              "cos_sin must be contiguous f32 [max_pos, 64] on GPU");
+  arks_mla_rope_cache(positions.data_ptr(), kv_a.data_ptr(),
+                      norm_weight.data_ptr(), q_pe.data_ptr(),
+                      cos_sin.data_ptr(), kv_cache.data_ptr(),
+                      slot_mapping.data_ptr(), (float)eps, (int)T, (int)H,
+                      kv_a.stride(0), q_pe.stride(0), q_pe.stride(1),
+                      current_stream());
+}
+
+void attention_mla_paged(torch::Tensor out, torch::Tensor q_lat,
+                         torch::Tensor q_pe, torch::Tensor kv_cache,
+                         torch::Tensor block_tables, torch::Tensor seq_lens,
+                         c10::optional<torch::Tensor> cu_seqlens, double scale,
+                         torch::Tensor part_out, int64_t nparts) {
+  check_mla_cache(kv_cache);
+  check_bf16_contig(out, "out");
+  check_bf16_contig(q_lat, "q_lat");
+  TORCH_CHECK(q_lat.dim() == 3 && q_lat.size(2) == 512,
+              "q_lat must be [T, H, 512]");
+  const int64_t T = q_lat.size(0), H = q_lat.size(1);
+  TORCH_CHECK(H >= 1 && T <= 65535, "needs H >= 1 and T <= 65535, got T=", T);
+  TORCH_CHECK(out.sizes() == q_lat.sizes(), "out must be [T, H, 512]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q_lat.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0);
+  check_mla_q_pe(q_pe, T, H);
+  TORCH_CHECK(block_tables.is_cuda() &&
+                  block_tables.scalar_type() == torch::kInt32 &&
+                  block_tables.is_contiguous() && block_tables.dim() == 2,
+              "block_tables must be contiguous int32 [S, max_blocks] on GPU");
+  const int64_t S = block_tables.size(0);
+  TORCH_CHECK(S >= 1 && block_tables.size(1) >= 1 &&
+              block_tables.size(1) < ((int64_t)1 << 31) / 16);
+  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.scalar_type() == torch::kInt32 &&
+                  seq_lens.is_contiguous() && seq_lens.numel() == S,
+              "seq_lens must be contiguous int32 [S] on GPU");
+  const void* cu = nullptr;
+  if (cu_seqlens.has_value()) {
+    const torch::Tensor& c = *cu_seqlens;
+    TORCH_CHECK(c.is_cuda() && c.scalar_type() == torch::kInt32 &&
+                    c.is_contiguous() && c.numel() == S + 1,
+                "cu_seqlens must be contiguous int32 [S + 1] on GPU");
+    cu = c.data_ptr();
+  } else {
+    TORCH_CHECK(T == S, "without cu_seqlens every sequence has one query "
+                        "token: T=", T, " S=", S);
+  }
+  TORCH_CHECK(nparts >= 1 && nparts <= 65535, "bad num_partitions ", nparts);
+  if (nparts > 1) {
+    TORCH_CHECK(part_out.is_cuda() &&
+                    part_out.scalar_type() == torch::kFloat32 &&
+                    part_out.is_contiguous() &&
+                    reinterpret_cast<uintptr_t>(part_out.data_ptr()) % 16 == 0 &&
+                    part_out.numel() >=
+                        T * ((H + 15) / 16) * nparts * 16 * (512 + 4),
+                "part_out workspace too small");
+  }
+  arks_attn_mla_paged(out.data_ptr(),
+                      nparts > 1 ? part_out.data_ptr() : nullptr,
+                      q_lat.data_ptr(), q_pe.data_ptr(), kv_cache.data_ptr(),
+                      block_tables.data_ptr(), seq_lens.data_ptr(), cu,
+                      (float)scale, (int)T, (int)H, (int)S,
+                      (int)block_tables.size(1), (int)kv_cache.size(0),
+                      (int)nparts, q_pe.stride(0), q_pe.stride(1),
+                      current_stream());
 }
 
 void attention_prefill_varlen(torch::Tensor out, torch::Tensor q,
@@ -2071,6 +2202,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reshape_and_cache", &reshape_and_cache);
   m.def("rope_and_cache", &rope_and_cache);
   m.def("attention_decode_paged", &attention_decode_paged);
+  m.def("mla_rope_cache", &mla_rope_cache);
+  m.def("attention_mla_paged", &attention_mla_paged);
   m.def("attention_prefill_varlen", &attention_prefill_varlen);
   m.def("attention_extend_paged", &attention_extend_paged);
   m.def("attention_extend_paged2", &attention_extend_paged2);

@@ -84,8 +84,16 @@ def _scaled_inv_freq(inv_freq: torch.Tensor, rope_scaling: dict | None,
         # ramp==0 (high-freq dims) -> extrapolate (keep original);
         # ramp==1 (long wavelengths) -> interpolate (divide by factor)
         out = (inv_freq / factor) * ramp + inv_freq * (1 - ramp)
+        def get_mscale(m: float = 1.0) -> float:
+            return 1.0 if factor <= 1 else 0.1 * m * math.log(factor) + 1.0
+
+        # DeepSeek's YaRN: mscale / mscale_all_dim set the table's factor to
+        # their ratio (HF _compute_yarn_parameters); the softmax scale takes
+        # mscale_all_dim squared (models/deepseek.py)
+        m, m_all = rope_scaling.get("mscale"), rope_scaling.get("mscale_all_dim")
         mscale = float(rope_scaling.get("attention_factor") or
-                       (0.1 * math.log(factor) + 1.0))
+                       (get_mscale(m) / get_mscale(m_all) if m and m_all
+                        else 0.1 * math.log(factor) + 1.0))
         return out, mscale
     return inv_freq, 1.0
 
@@ -970,4 +978,79 @@ def pool_embed(x, residual, weight, eps, segments, carry=None,
         if normalize:
             v = v / v.norm().clamp_min(1e-12)
         out[s] = v
+    return out
+
+
+# ---- multi-head latent attention (DeepSeek-V2/V3 MLA) ----
+# Latent cache: [num_blocks, block_size, kv_lora_rank + qk_rope_head_dim], no
+# head axis; a row is [RMS-normalised compressed KV | rotated shared rope
+# key] and serves every head as key (whole row) and value (the first
+# kv_lora_rank columns). The GPU kernels are built for 512 + 64 and a block
+# size of 16; these references take any sizes.
+
+
+def rope_interleaved(x: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
+    """DeepSeek's rotation of x [T, ..., R] by cs [T, R] (cos | sin per
+    pair): pair (2i, 2i+1) turns with frequency i and stays in place. The
+    same pairing on q and k keeps every q.k equal to HF's "de-interleave,
+    then rotate-half" form, which permutes both the same way."""
+    half = cs.shape[-1] // 2
+    shape = (cs.shape[0],) + (1,) * (x.dim() - 2) + (half,)
+    cos, sin = cs[:, :half].reshape(shape), cs[:, half:].reshape(shape)
+    a, b = x[..., 0::2].float(), x[..., 1::2].float()
+    out = torch.stack((a * cos - b * sin, b * cos + a * sin), dim=-1)
+    return out.flatten(-2).to(x.dtype)
+
+
+def mla_rope_cache(
+    positions: torch.Tensor,    # [T] int64
+    kv_a: torch.Tensor,         # [T, lat + rope] (kv_a_proj_with_mqa rows)
+    norm_weight: torch.Tensor,  # [lat] (kv_a_layernorm)
+    eps: float,
+    q_pe: torch.Tensor,         # [T, H, rope] view, rotated IN PLACE
+    cos_sin: torch.Tensor,      # [max_pos, rope]
+    kv_cache: torch.Tensor,     # [num_blocks, block_size, lat + rope]
+    slot_mapping: torch.Tensor,  # [T] int64, < 0 = no cache write
+) -> None:
+    rope = q_pe.shape[-1]
+    lat = kv_a.shape[-1] - rope
+    cs = cos_sin.float()[positions]
+    q_pe.copy_(rope_interleaved(q_pe, cs))
+    row = torch.cat((rmsnorm(kv_a[:, :lat], norm_weight, eps),
+                     rope_interleaved(kv_a[:, lat:], cs)), dim=-1)
+    keep = slot_mapping >= 0
+    kv_cache.view(-1, lat + rope)[slot_mapping[keep]] = row[keep].to(
+        kv_cache.dtype)
+
+
+def attention_mla_paged(
+    q_lat: torch.Tensor,         # [T, H, lat] (q_nope absorbed through W_UK)
+    q_pe: torch.Tensor,          # [T, H, rope]
+    kv_cache: torch.Tensor,      # [num_blocks, block_size, lat + rope]
+    block_tables: torch.Tensor,  # [S, max_blocks] int32
+    seq_lens: torch.Tensor,      # [S] int32 total KV length (new tokens in)
+    scale: float,
+    cu_seqlens: torch.Tensor | None = None,  # [S + 1]; None: one token each
+) -> torch.Tensor:
+    """Absorbed-query attention over the latent cache: o_lat [T, H, lat].
+    Query token i of a sequence with q_len new tokens sees positions
+    < seq_len - q_len + i + 1."""
+    lat = q_lat.shape[-1]
+    block_size = kv_cache.shape[1]
+    out = torch.empty_like(q_lat)
+    q = torch.cat((q_lat, q_pe), dim=-1).float()
+    for i in range(seq_lens.numel()):
+        s, e = ((i, i + 1) if cu_seqlens is None
+                else (int(cu_seqlens[i]), int(cu_seqlens[i + 1])))
+        L = int(seq_lens[i])
+        nblocks = (L + block_size - 1) // block_size
+        rows = kv_cache[block_tables[i, :nblocks].long()].flatten(0, 1)[:L]
+        rows = rows.float()
+        scores = torch.einsum("qhd,ld->hql", q[s:e], rows) * scale
+        kpos = torch.arange(L, device=q.device)
+        qpos = torch.arange(L - (e - s), L, device=q.device)
+        scores = scores.masked_fill(kpos[None, :] > qpos[:, None],
+                                    float("-inf"))
+        p = torch.softmax(scores, dim=-1)
+        out[s:e] = torch.einsum("hql,ld->qhd", p, rows[:, :lat]).to(out.dtype)
     return out

@@ -114,7 +114,7 @@ def build_engine_config(args):
     if args.enable_lora and args.disaggregation_mode:
         raise SystemExit(
             "--enable-lora with --disaggregation-mode is not supported")
-    return EngineConfig(
+    cfg = EngineConfig(
         model_path=model_path,
         preset=preset,
         served_model_name=args.served_model_name or args.model,
@@ -140,6 +140,11 @@ def build_engine_config(args):
         pooling=args.pooling,
         embedding_normalize=args.embedding_normalize,
     )
+    if args.disaggregation_mode and cfg.model_config().is_mla:
+        raise SystemExit(
+            "--disaggregation-mode is not supported with MLA models (no "
+            "wire format for latent pages yet)")
+    return cfg
 
 
 def main(argv=None):
