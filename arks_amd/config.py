@@ -722,6 +722,39 @@ PRESET_CONFIGS: dict[str, ModelConfig] = {
         eos_token_id=2,
         bos_token_id=1,
     ),
+    # tiny-deepseek-v3 with the nope / v head dims of the real models (128):
+    # the shape the non-absorbed prefill kernel is built for
+    "tiny-deepseek-v3-wide": ModelConfig(
+        architecture="DeepseekV3ForCausalLM",
+        vocab_size=512,
+        hidden_size=128,
+        intermediate_size=256,
+        moe_intermediate_size=64,
+        num_hidden_layers=3,
+        num_attention_heads=16,
+        num_key_value_heads=16,
+        head_dim=64,
+        rope_theta=10000.0,
+        max_position_embeddings=2048,
+        attention_bias=False,
+        num_local_experts=8,
+        num_experts_per_tok=2,
+        norm_topk_prob=True,
+        kv_lora_rank=512,
+        q_lora_rank=96,
+        qk_nope_head_dim=128,
+        qk_rope_head_dim=64,
+        v_head_dim=128,
+        n_shared_experts=1,
+        first_k_dense_replace=1,
+        routed_scaling_factor=2.5,
+        scoring_func="sigmoid",
+        topk_method="noaux_tc",
+        n_group=4,
+        topk_group=2,
+        eos_token_id=2,
+        bos_token_id=1,
+    ),
     "tiny": ModelConfig(  # CPU-test-sized
         architecture="Qwen2ForCausalLM",
         vocab_size=512,
@@ -833,6 +866,14 @@ class EngineConfig:
     # checkpoint's sentence-transformers settings, else last + normalise
     pooling: str = "auto"
     embedding_normalize: str = "auto"
+    # DeepSeek-V2/V3 (MLA) prefill: a sequence with at least this many new
+    # tokens in a prefill step attends non-absorbed over up-projected keys
+    # (attn_mla_prefill.hip) instead of in the latent space; 0 = never.
+    # The crossover behind the default is in profiles/mla.md.
+    mla_prefill_min_tokens: int = 256
+    # cap on the per-forward k_nope + v workspace of that path (512 B per
+    # key row and local head); sequences beyond it stay absorbed
+    mla_prefill_workspace_bytes: int = 1 << 30
 
     def __post_init__(self):
         if self.quantization not in (None, "fp8", "int4", "awq", "mxfp4"):

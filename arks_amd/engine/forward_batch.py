@@ -29,6 +29,10 @@ class ForwardBatch:
     # every adapted layer (ops.build_lora_tiles). None = no adapter rows in
     # this batch, so no LoRA kernel is launched.
     lora_tiles: torch.Tensor | None = None
+    # MLA prefill only: ops.MLAPrefillPlan, the sequences of this batch that
+    # attend non-absorbed over up-projected keys, shared by every layer.
+    # None = every sequence takes the absorbed path.
+    mla_prefill: tuple | None = None
 
     @property
     def num_tokens(self) -> int:

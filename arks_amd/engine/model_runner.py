@@ -238,6 +238,21 @@ class ModelRunner:
             q_lens, [s.lora_slot for s in seqs], self.device
         )
 
+    def _mla_prefill_plan(self, q_lens: list[int], kv_lens: list[int]):
+        """Which sequences of a prefill batch of an MLA model attend
+        non-absorbed (ops.build_mla_prefill_plan); None for any other model,
+        with the path off, or when no sequence qualifies."""
+        min_q = self.cfg.mla_prefill_min_tokens
+        if not self.model_cfg.is_mla or min_q <= 0:
+            return None
+        h_local = max(self.model_cfg.num_attention_heads
+                      // get_tp_world_size(), 1)
+        # k_nope + v of one up-projected row: h_local x (128 + 128) bf16
+        row_bytes = h_local * 512
+        return ops.build_mla_prefill_plan(
+            q_lens, kv_lens, h_local, self.device, min_q,
+            self.cfg.mla_prefill_workspace_bytes // row_bytes)
+
     def profile_num_blocks(self) -> int:
         """Size the KV pool from free HBM after weights (or the override)."""
         if self.cfg.kv_cache_blocks is not None:
@@ -451,6 +466,7 @@ class ModelRunner:
                 ext_tiles=ext_tiles,
                 logits_indices=torch.tensor(logits_idx, dtype=torch.int64, device=dev),
                 lora_tiles=self._lora_tiles(q_lens, sb.seqs),
+                mla_prefill=self._mla_prefill_plan(q_lens, kv_lens),
             )
         # decode
         input_ids = [s.last_token() for s in sb.seqs]

@@ -6,10 +6,17 @@ Attention runs with absorbed projections: the cache holds one 576-wide row
 per token (RMS-normalised compressed KV | rotated shared rope key, written
 by ops.mla_rope_cache), the query is carried into the latent space through
 W_UK, ops.attention_mla_paged attends over the rows (they are key and value
-at once) and W_UV brings the 512-wide output back to v_head_dim per head. The
-same path serves prefill, prefix-cache extend, speculative verification and
-decode, so every batch of an MLA model carries block tables. The two batched
-matmuls go through the library; the hot path is attn_mla.hip.
+at once) and W_UV brings the 512-wide output back to v_head_dim per head.
+That path serves decode, speculative verification and short chunks, so every
+batch of an MLA model carries block tables. The two batched matmuls go
+through the library; the hot path is attn_mla.hip.
+
+Prefill chunks of a model with the DeepSeek head shape (nope 128, rope 64,
+v 128) attend non-absorbed instead: the sequences a batch's
+ops.MLAPrefillPlan selects have their latent rows gathered from the cache and
+up-projected through W_UK / W_UV (the same parameters, no second copy of
+kv_b_proj), and attn_mla_prefill.hip runs causal 192/128 flash attention over
+them. The other sequences of the batch run absorbed on compacted rows.
 """
 
 from __future__ import annotations
@@ -86,6 +93,12 @@ class MLAAttention(nn.Module):
             torch.empty(self.h_local, self.lat, self.vdim, dtype=dtype),
             requires_grad=False)
         self.o_proj = RowParallelLinear(H * self.vdim, hid, False, dtype)
+        # the shape attn_mla_prefill.hip is built for (DeepSeek-V2, V2-Lite
+        # and V3); any other model keeps the absorbed path for every batch
+        self.prefill_path = (
+            (self.nope, self.vdim, self.lat, self.rope)
+            == (ops.MLA_PREFILL_NOPE, ops.MLA_PREFILL_V, ops.MLA_LATENT,
+                ops.MLA_ROPE))
 
     def load_kv_b(self, w: torch.Tensor) -> None:
         """HF kv_b_proj.weight [H * (nope + v), lat] -> this rank's W_UK
@@ -109,17 +122,47 @@ class MLAAttention(nn.Module):
         ops.mla_rope_cache(batch.positions, kv_a, self.kv_a_layernorm.weight,
                            self.kv_a_layernorm.eps, q_pe, self._cos_sin,
                            kv_cache, batch.slot_mapping)
+        plan = batch.mla_prefill if self.prefill_path else None
+        if plan is None:
+            o = self._absorbed(
+                q, kv_cache, batch.block_tables, batch.seq_lens,
+                batch.cu_seqlens if batch.is_prefill else None)
+            return self.o_proj(o.reshape(T, h * self.vdim), defer=defer)
+        # The plan's sequences attend non-absorbed: their latent rows (the
+        # ones mla_rope_cache just wrote, prefix included) are gathered and
+        # up-projected through the two halves of kv_b_proj, k_nope as one
+        # GEMM over all heads and v as one batched matmul whose head-major
+        # result the kernel reads in place.
+        c_kv, k_pe = ops.mla_gather_rows(kv_cache, batch.block_tables,
+                                         plan.cu_seqlens_kv, plan.total_kv)
+        k_nope = ops.linear_bf16(c_kv, self.w_uk.view(h * self.nope, self.lat))
+        v = torch.matmul(c_kv, self.w_uv)          # [h, Tkv, vdim]
+        o = torch.empty((T, h, self.vdim), dtype=q.dtype, device=q.device)
+        ops.attention_mla_prefill(
+            q, k_nope.view(-1, h, self.nope), k_pe, v.transpose(0, 1),
+            batch.cu_seqlens, plan, self.scale, out=o)
+        if plan.rest_rows is not None:
+            # decode rows and short chunks of a mixed batch: absorbed, on
+            # compacted rows
+            o.index_copy_(0, plan.rest_rows, self._absorbed(
+                q.index_select(0, plan.rest_rows), kv_cache,
+                batch.block_tables.index_select(0, plan.rest_seqs),
+                batch.seq_lens.index_select(0, plan.rest_seqs),
+                plan.rest_cu))
+        return self.o_proj(o.view(T, h * self.vdim), defer=defer)
+
+    def _absorbed(self, q, kv_cache, block_tables, seq_lens, cu_seqlens):
+        """Attention in the latent space for q [T, h, nope + rope] (rope part
+        rotated): [T, h, vdim]."""
         # contiguous operands: strided bmm on transposed views is avoided
         # throughout this code base (see MoEMLP)
         q_nope = q[..., :self.nope].transpose(0, 1).contiguous()
         q_lat = torch.bmm(q_nope, self.w_uk).transpose(0, 1).contiguous()
         o_lat = ops.attention_mla_paged(
-            q_lat, q_pe, kv_cache, batch.block_tables, batch.seq_lens,
-            self.scale, cu_seqlens=batch.cu_seqlens if batch.is_prefill
-            else None)
+            q_lat, q[..., self.nope:], kv_cache, block_tables, seq_lens,
+            self.scale, cu_seqlens=cu_seqlens)
         o = torch.bmm(o_lat.transpose(0, 1).contiguous(), self.w_uv)
-        return self.o_proj(o.transpose(0, 1).reshape(T, h * self.vdim),
-                           defer=defer)
+        return o.transpose(0, 1)
 
 
 class DeepseekMoE(MoEMLP):

@@ -470,6 +470,118 @@ def attention_mla_paged(q_lat, q_pe, kv_cache, block_tables, seq_lens,
                                    seq_lens, scale, cu_seqlens)
 
 
+# ---- non-absorbed MLA prefill (attn_mla_prefill.hip) ----
+MLA_PREFILL_NOPE = 128   # qk_nope_head_dim the prefill kernel is built for
+MLA_PREFILL_V = 128      # v_head_dim the prefill kernel is built for
+MLA_PREFILL_KVBLK = 64   # keys per LDS tile
+# q rows per workgroup: 256 (8 waves) once such tiles x local heads give a
+# workgroup per CU, else 128 (4 waves), which doubles the workgroups and
+# halves the reuse of a staged key tile. Measured in profiles/mla.md.
+MLA_PREFILL_FILL_WGS = 256
+
+
+class MLAPrefillPlan(NamedTuple):
+    """Host-built routing of one prefill batch of an MLA model: which
+    sequences run non-absorbed attention over up-projected keys
+    (attention_mla_prefill), and what the absorbed path needs for the rest."""
+    seqs: list            # selected sequence indices
+    cu_seqlens_kv: torch.Tensor  # int32 [S + 1]; unselected: zero length
+    tiles: torch.Tensor   # int32 [ntiles, 2] (seq_idx, q0), deepest first
+    total_kv: int         # rows of the gathered / up-projected tensors
+    qtile: int            # q rows per tile of `tiles`: 128 or 256
+    # the unselected sequences, None when every sequence is selected:
+    rest_rows: torch.Tensor | None  # int64 [Tr] their q rows
+    rest_seqs: torch.Tensor | None  # int64 [Sr] their sequence indices
+    rest_cu: torch.Tensor | None    # int32 [Sr + 1] cu_seqlens of those rows
+
+
+def build_mla_prefill_plan(q_lens: list[int], kv_lens: list[int],
+                           h_local: int, device, min_q: int,
+                           max_kv_rows: int, qtile: int | None = None):
+    """Per-sequence selection for the non-absorbed MLA prefill path, built
+    once per batch. A sequence is selected when it has at least min_q new
+    tokens (min_q <= 0: never) and its keys still fit in max_kv_rows
+    up-projected rows together with the sequences selected before it; decode
+    rows and short verification chunks of a mixed batch stay absorbed, where
+    up-projecting their whole context would be a loss. Returns None when no
+    sequence qualifies. Tiles are sorted by descending key depth, as in
+    build_extend_tiles; qtile None picks the tile height from the grid."""
+    cu_kv, picked, total = [0], [], 0
+    for i, n in enumerate(kv_lens):
+        if 0 < min_q <= q_lens[i] and total + n <= max_kv_rows:
+            picked.append(i)
+            total += n
+        cu_kv.append(total)
+    if not picked:
+        return None
+    if qtile is None:
+        big = sum(-(-q_lens[i] // 256) for i in picked) * max(h_local, 1)
+        qtile = 256 if big >= MLA_PREFILL_FILL_WGS else 128
+    tiles = []
+    for i in picked:
+        off = kv_lens[i] - q_lens[i]
+        for q0 in range(0, q_lens[i], qtile):
+            tiles.append((i, q0, min(kv_lens[i], off + q0 + qtile)))
+    tiles.sort(key=lambda t: -t[2])
+    rest_rows = rest_seqs = rest_cu = None
+    if len(picked) < len(q_lens):
+        rows, rcu = [], [0]
+        rest = sorted(set(range(len(q_lens))) - set(picked))
+        starts = [0]
+        for n in q_lens:
+            starts.append(starts[-1] + n)
+        for i in rest:
+            rows.extend(range(starts[i], starts[i + 1]))
+            rcu.append(rcu[-1] + q_lens[i])
+        rest_rows = torch.tensor(rows, dtype=torch.long, device=device)
+        rest_seqs = torch.tensor(rest, dtype=torch.long, device=device)
+        rest_cu = torch.tensor(rcu, dtype=torch.int32, device=device)
+    return MLAPrefillPlan(
+        picked, torch.tensor(cu_kv, dtype=torch.int32, device=device),
+        torch.tensor([t[:2] for t in tiles], dtype=torch.int32,
+                     device=device).reshape(-1, 2),
+        total, qtile, rest_rows, rest_seqs, rest_cu)
+
+
+def mla_gather_rows(kv_cache, block_tables, cu_seqlens_kv, total_kv: int):
+    """The live latent rows of the sequences with a non-empty range in
+    cu_seqlens_kv, copied out of the paged cache in sequence order:
+    (c_kv [total_kv, 512], k_pe [total_kv, 64])."""
+    if kv_cache.is_cuda:
+        _check_mla_cache(kv_cache)
+        c_kv = torch.empty((total_kv, MLA_LATENT), dtype=kv_cache.dtype,
+                           device=kv_cache.device)
+        k_pe = torch.empty((total_kv, MLA_ROPE), dtype=kv_cache.dtype,
+                           device=kv_cache.device)
+        _native().mla_gather_rows(c_kv, k_pe, kv_cache, block_tables,
+                                  cu_seqlens_kv)
+        return c_kv, k_pe
+    return ref.mla_gather_rows(kv_cache, block_tables, cu_seqlens_kv,
+                               total_kv)
+
+
+def attention_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q,
+                          plan: MLAPrefillPlan, scale: float, out=None):
+    """Causal varlen attention of the plan's sequences over their contiguous
+    up-projected keys and values: q [T, H, 192] (nope | rotated rope, a row
+    stride is honoured), k_nope and v [Tkv, H, 128] with any token and head
+    strides, k_pe [Tkv, 64] shared by the heads; returns out [T, H, 128].
+    Only rows of the plan's sequences are written: the rest of a given `out`
+    keeps its contents (of a fresh one, is uninitialised). Query row i of a
+    sequence sees keys < kv_len - q_len + i + 1."""
+    T, H = q.shape[0], q.shape[1]
+    if out is None:
+        out = torch.empty((T, H, MLA_PREFILL_V), dtype=q.dtype,
+                          device=q.device)
+    if q.is_cuda:
+        _native().attention_mla_prefill(
+            out, q, k_nope, k_pe, v, cu_seqlens_q, plan.cu_seqlens_kv,
+            plan.tiles, plan.qtile, float(scale))
+        return out
+    return ref.attention_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q,
+                                     plan.cu_seqlens_kv, scale, out)
+
+
 _EXTEND_WS: dict = {}
 
 

@@ -27,6 +27,7 @@ SOURCES = [
     os.path.join(CSRC, "attn_extend.hip"),
     os.path.join(CSRC, "attn_extend2.hip"),
     os.path.join(CSRC, "attn_mla.hip"),
+    os.path.join(CSRC, "attn_mla_prefill.hip"),
     os.path.join(CSRC, "quant_fp8.hip"),
     os.path.join(CSRC, "skinny_gemm.hip"),
     os.path.join(CSRC, "w4_gemm.hip"),

@@ -62,6 +62,18 @@ void arks_mla_rope_cache(const void* positions, const void* kv_a,
                          const void* slot_mapping, float eps, int num_tokens,
                          int num_heads, int64_t kv_stride, int64_t qpe_ts,
                          int64_t qpe_hs, hipStream_t stream);
+void arks_attn_mla_prefill(void* out, const void* q, const void* k_nope,
+                           const void* k_pe, const void* v,
+                           const void* cu_seqlens_q, const void* cu_seqlens_kv,
+                           const void* tile_info, int ntiles, int qtile,
+                           float scale, int num_heads, int total_q,
+                           int total_kv, int64_t q_ts, int64_t kn_ts,
+                           int64_t kn_hs, int64_t v_ts, int64_t v_hs,
+                           hipStream_t stream);
+void arks_mla_gather_rows(void* c_kv, void* k_pe, const void* cache,
+                          const void* block_tables, const void* cu_seqlens_kv,
+                          int total_rows, int num_seqs, int max_blocks,
+                          int num_blocks, hipStream_t stream);
 void arks_attn_prefill_varlen(void* out, const void* q, const void* k,
                               const void* v, const void* cu_seqlens,
                               const void* tile_info, int ntiles, float scale,
@@ -539,6 +551,101 @@ void attention_mla_paged(torch::Tensor out, torch::Tensor q_lat,
                       (int)block_tables.size(1), (int)kv_cache.size(0),
                       (int)nparts, q_pe.stride(0), q_pe.stride(1),
                       current_stream());
+}
+
+// ---- non-absorbed MLA prefill (attn_mla_prefill.hip) ----
+static void check_i32_vec(const torch::Tensor& t, int64_t n, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
+                  t.is_contiguous() && t.numel() == n,
+              name, " must be contiguous int32 [", n, "] on GPU");
+}
+
+// [Tkv, H, 128] bf16 with a dense last dim and any 16-byte aligned token and
+// head strides (token-major, or the head-major result of a batched matmul).
+static void check_mla_kv_operand(const torch::Tensor& t, int64_t Tkv, int64_t H,
+                                 const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
+                  t.dim() == 3 && t.size(0) == Tkv && t.size(1) == H &&
+                  t.size(2) == 128 && t.stride(2) == 1,
+              name, " must be bf16 [Tkv, H, 128] on GPU with a dense last dim");
+  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+                  t.stride(0) >= 0 && t.stride(1) >= 0 &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " rows must be 16-byte aligned");
+}
+
+void mla_gather_rows(torch::Tensor c_kv, torch::Tensor k_pe,
+                     torch::Tensor kv_cache, torch::Tensor block_tables,
+                     torch::Tensor cu_seqlens_kv) {
+  check_mla_cache(kv_cache);
+  check_bf16_contig(c_kv, "c_kv");
+  check_bf16_contig(k_pe, "k_pe");
+  TORCH_CHECK(c_kv.dim() == 2 && c_kv.size(1) == 512, "c_kv must be [Tkv, 512]");
+  const int64_t Tkv = c_kv.size(0);
+  TORCH_CHECK(k_pe.dim() == 2 && k_pe.size(0) == Tkv && k_pe.size(1) == 64,
+              "k_pe must be [Tkv, 64]");
+  TORCH_CHECK(Tkv < ((int64_t)1 << 31) / 72, "too many rows to gather");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(c_kv.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(k_pe.data_ptr()) % 16 == 0);
+  TORCH_CHECK(block_tables.is_cuda() &&
+                  block_tables.scalar_type() == torch::kInt32 &&
+                  block_tables.is_contiguous() && block_tables.dim() == 2 &&
+                  block_tables.size(0) >= 1 && block_tables.size(1) >= 1,
+              "block_tables must be contiguous int32 [S, max_blocks] on GPU");
+  const int64_t S = block_tables.size(0);
+  check_i32_vec(cu_seqlens_kv, S + 1, "cu_seqlens_kv");
+  if (Tkv == 0) return;
+  arks_mla_gather_rows(c_kv.data_ptr(), k_pe.data_ptr(), kv_cache.data_ptr(),
+                       block_tables.data_ptr(), cu_seqlens_kv.data_ptr(),
+                       (int)Tkv, (int)S, (int)block_tables.size(1),
+                       (int)kv_cache.size(0), current_stream());
+}
+
+void attention_mla_prefill(torch::Tensor out, torch::Tensor q,
+                           torch::Tensor k_nope, torch::Tensor k_pe,
+                           torch::Tensor v, torch::Tensor cu_seqlens_q,
+                           torch::Tensor cu_seqlens_kv, torch::Tensor tile_info,
+                           int64_t qtile, double scale) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 &&
+                  q.dim() == 3 && q.size(2) == 192 && q.stride(2) == 1 &&
+                  q.stride(1) == 192 && q.stride(0) >= q.size(1) * 192 &&
+                  q.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "q must be bf16 [T, H, 192] on GPU, dense per token, with "
+              "16-byte aligned rows");
+  const int64_t T = q.size(0), H = q.size(1);
+  check_bf16_contig(out, "out");
+  TORCH_CHECK(out.dim() == 3 && out.size(0) == T && out.size(1) == H &&
+                  out.size(2) == 128,
+              "out must be [T, H, 128]");
+  check_bf16_contig(k_pe, "k_pe");
+  TORCH_CHECK(k_pe.dim() == 2 && k_pe.size(1) == 64 &&
+                  reinterpret_cast<uintptr_t>(k_pe.data_ptr()) % 16 == 0,
+              "k_pe must be [Tkv, 64]");
+  const int64_t Tkv = k_pe.size(0);
+  check_mla_kv_operand(k_nope, Tkv, H, "k_nope");
+  check_mla_kv_operand(v, Tkv, H, "v");
+  TORCH_CHECK(T >= 1 && Tkv >= 1 && H >= 1 && T < ((int64_t)1 << 31) &&
+                  Tkv < ((int64_t)1 << 31),
+              "needs T, Tkv, H >= 1");
+  TORCH_CHECK(cu_seqlens_q.numel() == cu_seqlens_kv.numel() &&
+                  cu_seqlens_q.numel() >= 2,
+              "cu_seqlens_q and cu_seqlens_kv must both be [S + 1]");
+  check_i32_vec(cu_seqlens_q, cu_seqlens_q.numel(), "cu_seqlens_q");
+  check_i32_vec(cu_seqlens_kv, cu_seqlens_kv.numel(), "cu_seqlens_kv");
+  TORCH_CHECK(tile_info.is_cuda() && tile_info.scalar_type() == torch::kInt32 &&
+                  tile_info.is_contiguous() && tile_info.dim() == 2 &&
+                  tile_info.size(1) == 2 && tile_info.size(0) >= 1 &&
+                  tile_info.size(0) <= 65535,
+              "tile_info must be contiguous int32 [ntiles, 2] on GPU with "
+              "1..65535 tiles");
+  TORCH_CHECK(qtile == 128 || qtile == 256, "qtile must be 128 or 256");
+  arks_attn_mla_prefill(
+      out.data_ptr(), q.data_ptr(), k_nope.data_ptr(), k_pe.data_ptr(),
+      v.data_ptr(), cu_seqlens_q.data_ptr(), cu_seqlens_kv.data_ptr(),
+      tile_info.data_ptr(), (int)tile_info.size(0), (int)qtile, (float)scale,
+      (int)H, (int)T, (int)Tkv, q.stride(0), k_nope.stride(0),
+      k_nope.stride(1), v.stride(0), v.stride(1), current_stream());
 }
 
 void attention_prefill_varlen(torch::Tensor out, torch::Tensor q,
@@ -2204,6 +2311,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_decode_paged", &attention_decode_paged);
   m.def("mla_rope_cache", &mla_rope_cache);
   m.def("attention_mla_paged", &attention_mla_paged);
+  m.def("mla_gather_rows", &mla_gather_rows);
+  m.def("attention_mla_prefill", &attention_mla_prefill);
   m.def("attention_prefill_varlen", &attention_prefill_varlen);
   m.def("attention_extend_paged", &attention_extend_paged);
   m.def("attention_extend_paged2", &attention_extend_paged2);

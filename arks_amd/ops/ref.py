@@ -1054,3 +1054,58 @@ def attention_mla_paged(
         p = torch.softmax(scores, dim=-1)
         out[s:e] = torch.einsum("hql,ld->qhd", p, rows[:, :lat]).to(out.dtype)
     return out
+
+
+def mla_gather_rows(
+    kv_cache: torch.Tensor,       # [num_blocks, block_size, lat + rope]
+    block_tables: torch.Tensor,   # [S, max_blocks] int32
+    cu_seqlens_kv: torch.Tensor,  # [S + 1] int32, empty range: not gathered
+    total_kv: int,
+    lat: int = 512,
+):
+    """(c_kv [total_kv, lat], k_pe [total_kv, rope]): the live cache rows of
+    every sequence with a non-empty range, in sequence order."""
+    block_size = kv_cache.shape[1]
+    rows = kv_cache.new_empty((total_kv, kv_cache.shape[2]))
+    for i in range(block_tables.shape[0]):
+        s, e = int(cu_seqlens_kv[i]), int(cu_seqlens_kv[i + 1])
+        if e > s:
+            nblocks = (e - s + block_size - 1) // block_size
+            rows[s:e] = kv_cache[block_tables[i, :nblocks].long()].flatten(
+                0, 1)[:e - s]
+    return rows[:, :lat].contiguous(), rows[:, lat:].contiguous()
+
+
+def attention_mla_prefill(
+    q: torch.Tensor,        # [T, H, nope + rope], rope part rotated
+    k_nope: torch.Tensor,   # [Tkv, H, nope] (any strides)
+    k_pe: torch.Tensor,     # [Tkv, rope], shared by the heads
+    v: torch.Tensor,        # [Tkv, H, vdim] (any strides)
+    cu_seqlens_q: torch.Tensor,   # [S + 1]
+    cu_seqlens_kv: torch.Tensor,  # [S + 1], empty range: sequence skipped
+    scale: float,
+    out: torch.Tensor,      # [T, H, vdim]; rows of skipped sequences kept
+) -> torch.Tensor:
+    """Non-absorbed MLA attention over contiguous up-projected keys and
+    values, f32 with a full softmax. Query token i of a sequence with q_len
+    new tokens sees keys < kv_len - q_len + i + 1."""
+    nope = k_nope.shape[-1]
+    for i in range(cu_seqlens_q.numel() - 1):
+        ks, ke = int(cu_seqlens_kv[i]), int(cu_seqlens_kv[i + 1])
+        if ke == ks:
+            continue
+        s, e = int(cu_seqlens_q[i]), int(cu_seqlens_q[i + 1])
+        L = ke - ks
+        qi = q[s:e].float()
+        scores = (torch.einsum("qhd,lhd->hql", qi[..., :nope],
+                               k_nope[ks:ke].float())
+                  + torch.einsum("qhd,ld->hql", qi[..., nope:],
+                                 k_pe[ks:ke].float())) * scale
+        kpos = torch.arange(L, device=q.device)
+        qpos = torch.arange(L - (e - s), L, device=q.device)
+        scores = scores.masked_fill(kpos[None, :] > qpos[:, None],
+                                    float("-inf"))
+        p = torch.softmax(scores, dim=-1)
+        out[s:e] = torch.einsum("hql,lhd->qhd", p,
+                                v[ks:ke].float()).to(out.dtype)
+    return out

@@ -86,6 +86,10 @@ def parse_args(argv=None):
                    default="auto",
                    help="L2-normalise embeddings; auto follows the checkpoint "
                         "(a Normalize module), else true")
+    p.add_argument("--mla-prefill-min-tokens", type=int, default=256,
+                   help="DeepSeek-V2/V3: new tokens from which a sequence's "
+                        "prefill chunk attends non-absorbed over up-projected "
+                        "keys; 0 keeps every batch on the absorbed path")
     # multi-node group flags (LWS leader/worker topology): workers join the
     # leader's torch.distributed rendezvous
     p.add_argument("--leader-address", default=None)
@@ -139,6 +143,7 @@ def build_engine_config(args):
         lora_modules=lora_modules,
         pooling=args.pooling,
         embedding_normalize=args.embedding_normalize,
+        mla_prefill_min_tokens=args.mla_prefill_min_tokens,
     )
     if args.disaggregation_mode and cfg.model_config().is_mla:
         raise SystemExit(
